@@ -295,6 +295,12 @@ class HotPath(object):
         if not self.fused:
             self._k("ratio", L.tap_env_ratio, self.ctx, d, P(e._state), P(self.reward), None, None)
 
+    def outputs(self):
+        """What a caller of the pass receives, batch-first: the state the LAST pass left behind."""
+        o = (self.nw - 1) & 1
+        return dict(reward=self.reward, positions=self.env.positions, stable=self.env.stable, heightmap=self.env.heightmap,
+                    features=self.feat, dynamic=self.dyn[o], current_mask=self.cur, mask=self.maskb[o])
+
     # ---- after the timed region: the state the LAST pass left behind, against the oracle ---------------
     def verify(self, nenv=VERIFY_ENVS):
         O = _oracle()
@@ -362,6 +368,9 @@ class EpisodeHotPath(HotPath):
         P, st = _lib.ptr, self.static[0]
         self._k("episode", self.lib.tap_episode_reward, self.ctx, C.byref(self.desc), self.B, self.n, P(st),
                 st.shape[1], self.nR, P(self.tour), P(self.reward), P(self.pos), P(self.stab))
+
+    def outputs(self):
+        return dict(reward=self.reward, positions=self.pos, stable=self.stab)
 
     def verify(self, nenv=VERIFY_ENVS):
         O = _oracle()
@@ -497,6 +506,11 @@ class RollingHotPath(HotPath):
                         P(dyn_in), P(self.static_last), self.static.shape[1], P(self.tape[n1 + t]), P(mask_in), P(cs_in),
                         P(self.dyn[o]), P(self.csb[o]), P(self.cur), P(self.maskb[o]), P(self.feat), P(self.reward), flags)
             dyn_in, cs_in, mask_in, bits_in = self.dyn[o], self.csb[o], self.maskb[o], self.bitb[o]
+
+    def outputs(self):
+        o = (self.nw - 1) & 1
+        return dict(reward=self.reward, positions=self.env.positions, stable=self.env.stable, heightmap=self.env.heightmap,
+                    features=self.feat, dynamic=self.dyn[o], current_mask=self.cur, mask=self.maskb[o])
 
     def verify(self, nenv=VERIFY_ENVS):
         """(1) every env's calc_ratio against the eager two-launch recording run; (2) a slice against the
@@ -715,6 +729,7 @@ def time_passes(hps, steps, warmup, use_graph, world, repeats=1):
         mine = last_gather["out"][r * c:(r + 1) * c]
         hp.gathered_ok = bool(torch.equal(torch.nan_to_num(mine, nan=-7.0), torch.nan_to_num(acc[:c], nan=-7.0)))
     if rows_on:
+        hp.last_reward = acc[(steps - 1) % ge]                  # the row the last timed pass wrote (run(): rows 0 .. cnt-1)
         hp.reward = acc[0]
         # every pass of the last group(s) against row 0 (NaN = a row no timed pass wrote; NaN rewards of flagged
         # containers compare equal to themselves here)
@@ -1643,6 +1658,32 @@ def roofline_of(hp, config, cfg, rolling, steps, graphs):
     return roof, kernels
 
 
+DUMP_LIMIT = 64 << 20     # bytes of --dump-outputs; above it a fixed, seeded sample of the envs is written
+
+
+def dump_outputs(hp, out_dir):
+    """--dump-outputs: the arrays of hp.outputs() (what the last timed pass computed) as out_dir/<name>.npy, float32
+    (float64 for integers float32 cannot hold).  Every array is batch-first; when the whole set is above DUMP_LIMIT
+    the same seeded sample of envs (sorted indices, in out_dir/env_index.npy) is taken from each."""
+    arrays = {}
+    for name, t in hp.outputs().items():
+        if name == "reward" and getattr(hp, "last_reward", None) is not None:
+            t = hp.last_reward
+        a = t.detach().cpu().numpy()
+        exact32 = a.dtype.kind == "f" and a.dtype.itemsize <= 4 or a.dtype.kind in "biu" and a.dtype.itemsize <= 2
+        arrays[name] = a.astype(np.float32 if exact32 else np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        B = hp.B
+        room = DUMP_LIMIT - 4096 * (len(arrays) + 1)             # .npy headers; env_index costs 8 bytes per env
+        keep = np.sort(np.random.RandomState(0).choice(B, room * B // (total + 8 * B), replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+        arrays["env_index"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def build_hotpath(config, args, rank, dev, batch=None):
     """The pre-allocated pass of one config on this rank's share of the batch -> (hot path, cfg tuple, rolling?)."""
     cfg = CONFIGS[config]
@@ -1771,6 +1812,8 @@ def main():
                     help="c4: 8 192 distinct instances from the device-side perfect-packing generator (~30 s of set-up) instead "
                          "of the 64 instances the reference's own generator wrote (tests/golden/ppsg_2d.npz, SURVEY 8(d)) tiled")
     ap.add_argument("--ppsg-fixture", action="store_true", help="(default since round 5; kept for old command lines)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the headline's last timed pass computed as DIR/<name>.npy (rank 0's envs, at most 64 MB)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1812,6 +1855,8 @@ def main():
     use_graph = not args.no_graph
     dt, graphs = time_passes(hp, args.steps, args.warmup, use_graph, world, repeats=args.repeats)
     hp.env.check()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(hp, args.dump_outputs)                   # before any later reading replays the pass again
     total_steps = B * world * n * args.steps
     value = total_steps / dt
     # every rank checks its own last pass against the oracle; the line says "verified" only if all did

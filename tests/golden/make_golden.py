@@ -24,6 +24,10 @@ Fixtures:
   ppsg2d.npz                         generate.BPP_Generator_2D_easy / generate_blocks_with_GT (2D) under recorded seeds
   ppsg2d_arm.npz                     generate_blocks_with_GT / generate_blocks (2D) with arm_size 2 .. 4 under recorded seeds
   ppsg_2d.npz                        (--only ppsg) 64 instances of the reference's PPSG generator + MACS traces over them
+  reference_diff.npz                 tools.Container full state (voxel grid included) after every step, pack.update_dynamic /
+                                     update_mask and pack.reward ('mul'): the cases of tests/test_oracle_vs_reference.py
+  host_reference.npz                 pack.PACKDataset, the dataset directory names and rolling.RollingDataset: the cases of
+                                     tests/test_host_vs_reference.py
 """
 import argparse
 import itertools
@@ -37,6 +41,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(1, os.path.dirname(os.path.dirname(HERE)))     # the package, for the test modules whose cases are recorded
 import ref_loader  # noqa: E402
 
 warnings.filterwarnings("ignore")
@@ -710,6 +715,119 @@ def make_rolling(tools, generate, shapes=ROLLING_SHAPES, name="rolling.npz", see
     save(name, **out)
 
 
+def _keyed(records):
+    """[(key, {field: array})] -> flat npz dict with a `keys` index (golden_util.key_index)."""
+    out = {"keys": np.asarray([k for k, _ in records])}
+    for i, (_, fields) in enumerate(records):
+        for f, v in fields.items():
+            out["k%d_%s" % (i, f)] = v
+    return out
+
+
+def _narrow(a, dtype):
+    b = np.asarray(a).astype(dtype)
+    assert np.array_equal(b, a), "values do not fit %s" % dtype
+    return b
+
+
+def make_reference_diff(tools, pack):
+    """Every step's full Container state for the runs of tests/test_oracle_vs_reference.py, and its masks / reward cases."""
+    import torch
+    import test_oracle_vs_reference as V
+    records = []
+    for rewards, runs in V.DIFF_CASES.values():
+        for reward in rewards:
+            for cs, n, feat, strategy, episodes, seed, lo, hi, hz in runs:
+                tr = dict(features=[], heightmap=[], positions=[], stable=[], valid=[], empty=[], container=[], ratio=[])
+                for blocks in V.diff_blocks(cs, n, episodes, seed, lo, hi, hz):
+                    r = tools.Container(list(cs), n, reward, feat, packing_strategy=strategy)
+                    steps = {k: [] for k in tr if k != "ratio"}
+                    for t in range(n):
+                        steps["features"].append(np.asarray(r.add_new_block(blocks[t].astype(np.float32))).copy())
+                        steps["heightmap"].append(np.asarray(r.heightmap).copy())
+                        steps["positions"].append(np.asarray(r.positions).copy())
+                        steps["stable"].append(np.asarray(list(r.stable), dtype=bool))
+                        steps["valid"].append(int(r.valid_size))
+                        steps["empty"].append(int(r.empty_size))
+                        steps["container"].append(np.asarray(r.container).copy())
+                    for k, v in steps.items():
+                        tr[k].append(v)
+                    tr["ratio"].append(float(r.calc_ratio()))
+                key = V.diff_key(cs, n, reward, feat, strategy, episodes, seed, lo, hi, hz)
+                records.append((key, dict(features=_narrow(tr["features"], np.int16), heightmap=_narrow(tr["heightmap"], np.int16),
+                                          positions=_narrow(tr["positions"], np.int16), stable=_narrow(tr["stable"], np.uint8),
+                                          valid=_narrow(tr["valid"], np.int32), empty=_narrow(tr["empty"], np.int32),
+                                          container=_narrow(tr["container"], np.int16),
+                                          ratio=np.asarray(tr["ratio"], np.float64))))
+    out = _keyed(records)
+    for shape in V.MASK_SHAPES:
+        dyn, static, mask, ptr = V.mask_inputs(shape)
+        rd = pack.update_dynamic(torch.from_numpy(dyn), torch.from_numpy(static), torch.from_numpy(ptr), "bot", True)
+        rc, rm = pack.update_mask(torch.from_numpy(mask), rd, torch.from_numpy(static), torch.from_numpy(ptr), "bot", True)
+        pre = "masks_%d_%d_%d_" % shape
+        out[pre + "dynamic"], out[pre + "current_mask"], out[pre + "mask"] = rd.numpy(), rc.numpy(), rm.numpy()
+    for D in (2, 3):
+        static, tour, _ = V.reward_mul_inputs(D)
+        out["reward_mul_%dd" % D] = pack.reward(torch.from_numpy(static), torch.from_numpy(tour), "C+P+S-lb-soft", "mul",
+                                                True, 5, 60).numpy()
+    save("reference_diff.npz", **out)
+
+
+def make_host_reference(pack, tmp):
+    """The reference's PACKDataset tensors, dataset directory names and RollingDataset arrays for the cases of
+    tests/test_host_vs_reference.py, on the dataset directories that test writes."""
+    import importlib
+    import test_host_vs_reference as V
+    sys.path.insert(0, ref_loader.REFERENCE_DIR)
+    try:
+        rrolling = importlib.import_module("rolling")
+    finally:
+        sys.path.remove(ref_loader.REFERENCE_DIR)
+    dirs = V.write_dirs(lambda name: tempfile.mkdtemp(prefix=name, dir=tmp))
+    records = []
+    for D in (2, 3):
+        d, d2, N = dirs[D]
+        for input_type, allow_rot in V.INPUT_TYPES:
+            for hm_type in ("diff", "full"):
+                for mix in (None, d2):
+                    key = V.packdataset_key(D, input_type, allow_rot, hm_type, mix is not None)
+                    try:
+                        ref = pack.PACKDataset(d, 10, N, 7, input_type, hm_type, allow_rot, 5, mix_data_file=mix, unit=1)
+                    except Exception as e:
+                        records.append((key, dict(error=np.asarray(type(e).__name__))))
+                        continue
+                    item = ref[5]
+                    rec = dict(static=ref.static.numpy(), dynamic=ref.dynamic.numpy(),
+                               decoder_static_shape=np.asarray(ref.decoder_static.shape),
+                               decoder_dynamic_shape=np.asarray(ref.decoder_dynamic.shape),
+                               len=np.asarray(len(ref)), item5_len=np.asarray(len(item)))
+                    for j, a in enumerate(item):
+                        rec["item5_%d" % j] = a.detach().numpy()
+                    records.append((key, rec))
+        ref = rrolling.RollingDataset(d, 10, 5, V.ROLLING_INSTANCES, D, 3, "bot", "diff", True, 5, 7, 50)
+        ics = ref.initial_containers[:V.ROLLING_INSTANCES]
+        records.append(("rolling|%d" % D, dict(blocks=np.asarray([np.asarray(ic.blocks)[:10] for ic in ics]),
+                                               positions=np.asarray([np.asarray(ic.positions) for ic in ics]),
+                                               decoder_static_shape=np.asarray(ref.decoder_static.shape),
+                                               decoder_dynamic_shape=np.asarray(ref.decoder_dynamic.shape))))
+    d, _, N = dirs[2]
+    ref = pack.PACKDataset(d, 10, N, 3, "bot", "diff", True, 5, unit=0.5, no_precedence=True)
+    records.append(("no_precedence_unit", dict(static=ref.static.numpy(), dynamic=ref.dynamic.numpy(),
+                                               decoder_dynamic_shape=np.asarray(ref.decoder_dynamic.shape))))
+    out = _keyed(records)
+    cwd = os.getcwd()
+    os.chdir(tempfile.mkdtemp(prefix="names", dir=tmp))
+    try:
+        names = []
+        for case in V.DIR_NAME_CASES:
+            V.make_dataset_dirs(*case)
+            names += [repr(x) for x in V.dataset_names(pack, *case)]
+    finally:
+        os.chdir(cwd)
+    out["dir_names"] = np.asarray(names)
+    save("host_reference.npz", **out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", nargs="*", default=None)
@@ -738,6 +856,10 @@ def main():
     if want("rolling_big"): make_rolling(tools, generate, ROLLING_BIG_SHAPES, "rolling_big.npz", seed=78)
     if want("render"): make_render(pack)
     if want("dataset_wide"): make_dataset_wide(pack)
+    if want("reference_diff"): make_reference_diff(tools, pack)
+    if want("host_reference"):
+        with tempfile.TemporaryDirectory() as tmp:
+            make_host_reference(pack, tmp)
     if want("data"):
         with tempfile.TemporaryDirectory() as tmp:
             statics, dynamics, tours = {}, {}, {}

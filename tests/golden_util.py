@@ -11,6 +11,13 @@ def load(name):
     return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
 
 
+def key_index(z, key):
+    """Position of `key` in the `keys` index of a keyed fixture (reference_diff.npz, host_reference.npz)."""
+    keys = [str(k) for k in z["keys"]]
+    assert key in keys, "no recorded case %s" % key
+    return keys.index(key)
+
+
 def cases(name):
     """Yield (meta dict, {blocks, features, heightmaps, positions, stable, valid, empty, ratio, cps})."""
     z = load(name)

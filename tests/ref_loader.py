@@ -1,7 +1,7 @@
 """Loader for the upstream reference (only present in the build container, never on the GPU box).
 
-Used by tests/golden/make_golden.py (fixture generation) and by the `reference`-marked tests that
-compare the oracle live against the reference.  Nothing here is imported by the product.
+Used by tests/golden/make_golden.py (fixture generation) only: the tests compare against the fixtures it
+writes.  Nothing here is imported by the product.
 """
 import math
 import os
