@@ -36,7 +36,7 @@ typedef struct tap_ctx tap_ctx;
 enum {
     TAP_OK = 0,
     TAP_E_INVALID = -1,     /* bad argument */
-    TAP_E_UNSUPPORTED = -2, /* valid in the reference, not implemented here (e.g. > 4096 cells) */
+    TAP_E_UNSUPPORTED = -2, /* valid in the reference, not implemented here (e.g. LB_GREEDY > 16384 cells) */
     TAP_E_HIP = -3,         /* HIP runtime error */
     TAP_E_OVERFLOW = -4,    /* a placement reached above H (reference: IndexError tools.py:2109 /
                                silent clipping tools.py:2169) */
@@ -117,6 +117,7 @@ int tap_env_reset(tap_ctx *ctx, const tap_env_desc *d, void *state, void *stream
  * 64 cells with sides <= 8, one wavefront per container above; block sides <= container sides, else error bit 4);
  * on the wave-per-container paths (LB_GREEDY and MACS 3D above 64 cells) tools.is_stable is evaluated for block
  * footprints up to 16 x 16 (csrc/tap_stable_wide.h beyond the 8 x 8 support masks), larger ones raise error bit 4;
+ * LB_GREEDY containers up to 16384 cells (above 4096: one workgroup per container, the height-map in its LDS);
  * model.py:451-465 is the loop it replaces).
  *   blocks      (B, D) TAP_DT_F32 | TAP_DT_I32, one block per env; f32 is truncated like
  *               block.astype(int) (tools.py:3689)
@@ -203,7 +204,8 @@ int tap_episode_scores(tap_ctx *ctx, const tap_env_desc *d, int B, int n, const 
  * stable_out flag is 1 (generate.py:909-910).  With strategy TAP_MACS: tools.calc_positions_mcs
  * (tools.py:3213-3315).  LB_GREEDY containers of any size (generate.py:908 accepts any --initial_container_width):
  * lane-per-cell groups up to 64 cells, above that one wavefront per container with the height-map in LDS across the n
- * placements (big.hip: k_big_wave_episode; tap_episode_reward / tap_episode_scores take the same path); MACS / MUL
+ * placements (big.hip: k_big_wave_episode; above 4096 cells one workgroup per container, k_big_wg_episode, up to
+ * 16384; tap_episode_reward / tap_episode_scores take the same path); MACS / MUL
  * above 64 cells: TAP_E_UNSUPPORTED, step them with tap_env_step_gather.  reward_out (B,) f32 = -(C+P+S), positions_out
  * (B, n, D) i32, stable_out (B, n) u8, score64_out (B,) f64 = C+P+S -- each nullable.
  * A block with a side < 1 is not part of its list (lists of different length in one batch: the

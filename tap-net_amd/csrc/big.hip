@@ -2,8 +2,9 @@
 // 64 cells, or a 3D side above 8 (the reference builds W x W containers for any --container_width,
 // model.py:279).  Same height-map formulation as tap_place.h, written for ONE THREAD per
 // container walking its own cells -- a correctness path for unusual shapes, not a fast one; every BASELINE
-// shape takes the lane-per-cell kernels.  Limits: W*L <= 4096 cells; 3D block footprints up to 16 x 16 (beyond the 8 x 8
-// support masks: tap_stable_wide.h), larger ones raise error bit 4; 2D blocks of any width.
+// shape takes the lane-per-cell kernels.  Limits: W*L <= 16 384 cells (above 4 096: one workgroup per container, at the
+// end of this file); 3D block footprints up to 16 x 16 (beyond the 8 x 8 support masks: tap_stable_wide.h), larger ones
+// raise error bit 4; 2D blocks of any width.
 #include "tap_common.h"
 #include "tap_place.h"
 #include "tap_stable_wide.h"
@@ -11,12 +12,20 @@
 #include "tap_masks.h"
 #include "tap_transition.h"
 
+#include <type_traits>
+
 // Register budget of the wave-per-container kernels.  The common placement (footprints within the support masks) needs
 // 67 .. 83 VGPRs; the instantiation for wide footprints (tap_stable_wide.h: per-row extremes in 64-bit words inside the
 // candidate loop) 131 .. 149 -- and a kernel is allocated the maximum over its paths, whether a wave takes them or not:
 // with the wide code compiled in, the 10 x 10 step ran at 3 instead of 6 waves per SIMD, 22.9 against 19.8 us (c7,
 // same-source A/B, round 5).  Holding the kernels to 5 waves per SIMD (96 VGPRs) leaves the common path unspilled and
 // makes the rare wide path spill instead.
+// Cells of the one-wavefront and thread-per-container kernels (the fallback's visited set is 64 words; the wave kernels
+// pack x into 12 bits); larger containers, up to TAP_BIG_WG_CELLS (tap_common.h), take the one-workgroup-per-container kernels below.
+constexpr int TAP_BIG_WAVE_CELLS = 4096;
+// threads per container of those kernels, soft / hard rewards (measured at B = 1 024 over 256 / 512 / 1 024: DESIGN.md section 4)
+constexpr int TAP_BIG_WG_THREADS_SOFT = 512, TAP_BIG_WG_THREADS_HARD = 1024;
+
 #ifndef TAP_BIG_REGS
 #define TAP_BIG_REGS __attribute__((amdgpu_waves_per_eu(5, 8)))
 #endif
@@ -606,9 +615,370 @@ __global__ void __launch_bounds__(TAP_BLOCK) TAP_BIG_REGS k_big_wave_episode(Epi
     if (lane == 0) episode_finish(a, env, cnt, gmax, err);
 }
 
+// ---- containers above 4 096 cells: one WORKGROUP per container ---------------------------------------------------------
+// The one-wavefront kernels above hold a container in one wave's LDS tile and the thread-per-container fallback keeps a
+// 4 096-bit visited set, so W*L stopped at 4 096 cells; the reference builds a W x W map for any --container_width,
+// scaled by --unit (model.py:279, pack.py:123).  Here NT = 512 (soft) / 1 024 (hard rewards) threads share one
+// container up to 16 384 cells: its height-map lives in the workgroup's LDS for the whole step (64 KiB at 16 384 cells),
+// every thread takes the cells tid, tid + NT, ... and the selections of big_wave_place_t become a wave-level reduction
+// followed by a cross-wave one through LDS -- double-buffered, so one __syncthreads per round.
+// HARD: one word per position beside the map in LDS (128 KiB at 16 384 cells; big_wg_place_t), from which the corner
+// keys are recomputed, and the height sum under a settling position is summed by the workgroup when the walk stops there
+// -- nothing per cell outside the LDS, so the whole-episode kernel needs no memory of its own either.
+// The 32-bit corner key ((z L + y) 3 + cls) W + x stays below 2^31 at H <= 4 000 and W*L <= TAP_BIG_WG_CELLS.
+
+// cross-wave scratch of one workgroup: two buffers (alternating rounds) of per-wave entries
+struct BigWgRed {
+    double r[2][16];
+    long k[2][16];
+    int v[2][16][5];
+};
+
+template <int NT>
+struct BigWg {
+    static constexpr int NW = NT / 64;
+    BigWgRed *red;
+    int par;     // buffer of the next round (the same on every thread)
+    int wave, lane;
+    // op over the workgroup; every thread gets the result
+    template <class Op>
+    __device__ __forceinline__ int all(int v, Op op)
+    {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o));
+        int *r = &red->v[par][0][0];
+        if (lane == 0) r[wave] = v;
+        __syncthreads();
+        int w = r[0];
+#pragma unroll
+        for (int i = 1; i < NW; ++i) w = op(w, r[i]);
+        par ^= 1;
+        return w;
+    }
+    __device__ __forceinline__ int min(int v) { return all(v, [](int a, int b) { return a < b ? a : b; }); }
+    __device__ __forceinline__ int max(int v) { return all(v, [](int a, int b) { return a > b ? a : b; }); }
+    __device__ __forceinline__ int sum(int v) { return all(v, [](int a, int b) { return a + b; }); }
+    __device__ __forceinline__ int orr(int v) { return all(v, [](int a, int b) { return a | b; }); }
+};
+
+// One LB_GREEDY placement of a container whose height-map `hm` sits in the workgroup's LDS (HARD: followed by cells ints
+// of the per-position word below); every thread calls this.  Same contract as
+// big_wave_place_t: updates the map (and `ghm` when given), valid / empty / stable in `cnt` and the error bits (OR-ed over
+// the workgroup on return); the caller advances cnt.count.  The placement is the same on every thread.
+template <int NT, bool HARD, bool WIDE>
+__device__ __forceinline__ Placement big_wg_place_t(BigWg<NT> &g, const tap_env_desc &d, const uint32_t *lut, int32_t *hm,
+                                                    int32_t *ghm, int gmax, Counters &cnt, int &err, int bx, int by, int bz)
+{
+    const int D = d.D, W = d.W, L = d.L, cells = W * L, tid = threadIdx.x;
+    const BigCtx c = {D, W, L, d.H, d.flags, lut, hm, nullptr};
+    const PlaceCfg cfg = {W, L, d.H, d.flags, lut};
+    const int vol = bx * by * bz;
+    double wr = -1.0;
+    int px = 0, py = 0, pz = 0, pstab = 0, pemp = 0;
+    if (!HARD) {
+        double best = -1.0;
+        long bestkey = LONG_MAX;
+        int bx_ = 0, by_ = 0, bzv = 0, bstab = 0, bemp = 0;
+        for (int cell = tid; cell < cells; cell += NT) {
+            const int x = cell / L, y = cell - x * L;
+            int cls;
+            if (!big_corner(c, x, y, cls)) continue;
+            if (x + bx > W || y + by > L) continue;                              // :2076 (2D: every later corner overflows too), :2255-2256
+            int mx, sum; u64 eq;
+            big_scan<WIDE>(c, x, y, bx, by, mx, eq, sum);
+            const int z = mx;
+            if (z >= d.H) err |= 1;                                            // :2109 would raise IndexError
+            const int stab = z == 0 ? 1 : big_stable<WIDE>(c, x, y, bx, by, z, eq);
+            const int emp = cnt.empty + bx * by * z - sum;
+            const double r = tap_score(cfg, cnt, vol, gmax, z, bz, emp, stab);
+            const long key = big_key(c, x, y, z, cls);
+            if (r > best || (r == best && key < bestkey)) { best = r; bestkey = key; bx_ = x; by_ = y; bzv = z; bstab = stab; bemp = emp; }
+        }
+        // first maximum on (ratio desc, key asc): over the wave, then over the waves
+        double r = best;
+        long k = bestkey;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const double r2 = __hiloint2double(__shfl_xor(__double2hiint(r), o), __shfl_xor(__double2loint(r), o));
+            const long k2 = ((long)__shfl_xor((int)(k >> 32), o) << 32) | (unsigned)__shfl_xor((int)k, o);
+            if (r2 > r || (r2 == r && k2 < k)) { r = r2; k = k2; }
+        }
+        const u64 wm = __ballot(best == r && bestkey == k);                     // keys are unique: one lane (or none placed)
+        const int src = wm ? __ffsll((long long)wm) - 1 : 0;
+        const int v0 = __shfl(bx_, src), v1 = __shfl(by_, src), v2 = __shfl(bzv, src), v3 = __shfl(bstab, src), v4 = __shfl(bemp, src);
+        const int p = g.par;
+        if (g.lane == 0) {
+            g.red->r[p][g.wave] = r; g.red->k[p][g.wave] = k;
+            int *v = g.red->v[p][g.wave];
+            v[0] = v0; v[1] = v1; v[2] = v2; v[3] = v3; v[4] = v4;
+        }
+        __syncthreads();
+        int win = 0;
+        wr = g.red->r[p][0];
+        long wk = g.red->k[p][0];
+        for (int w = 1; w < BigWg<NT>::NW; ++w) {
+            const double r2 = g.red->r[p][w];
+            const long k2 = g.red->k[p][w];
+            if (r2 > wr || (r2 == wr && k2 < wk)) { wr = r2; wk = k2; win = w; }
+        }
+        const int *v = g.red->v[p][win];
+        px = v[0]; py = v[1]; pz = v[2]; pstab = v[3]; pemp = v[4];
+        g.par ^= 1;
+    } else {
+        // big_wave_place_t's walk (tools.py:2100-2121, 2284-2297, 2320-2327): per position one word, then per corner in
+        // key order the first settling, untaken position of its rectangle in the order x * L + y.  The word packs what
+        // both scans need -- (max << 5) | taken << 4 | corner << 3 | class << 1 | stable, -1 out of bounds -- so the
+        // corner keys are recomputed from it (a few integer operations per cell) instead of being kept per cell: the map
+        // and the words are 2 ints per cell of LDS, 128 KiB at 16 384 cells.  max is clamped to 2^25: such a level is
+        // far beyond H <= 4 000 (its key exceeds 2^31 and is never walked, as big_key's clamp does).
+        int32_t *pw = hm + cells;
+        for (int cell = tid; cell < cells; cell += NT) {
+            const int x = cell / L, y = cell - x * L;
+            int w = -1;
+            if (x + bx <= W && y + by <= L) {
+                int mx, sm, cls; u64 eq;
+                big_scan<WIDE>(c, x, y, bx, by, mx, eq, sm);
+                const int st = mx == 0 ? 1 : big_stable<WIDE>(c, x, y, bx, by, mx, eq);
+                const bool corner = big_corner(c, x, y, cls);
+                w = (min(mx, 1 << 25) << 5) | (corner ? 8 | (cls << 1) : 0) | st;
+            }
+            pw[cell] = w;
+        }
+        __syncthreads();
+        long last = -1;
+        for (;;) {
+            long kmin = LONG_MAX;
+            for (int cell = tid; cell < cells; cell += NT) {
+                const int w = pw[cell];
+                if (w < 0 || !(w & 8)) continue;
+                const int x = cell / L, y = cell - x * L;
+                const long k = big_key(c, x, y, w >> 5, (w >> 1) & 3);
+                if (k > last && k < kmin) kmin = k;
+            }
+            const int k32 = g.min(kmin > INT_MAX ? INT_MAX : (int)kmin);
+            if (k32 == INT_MAX) break;
+            last = k32;
+            const int X0 = k32 % W;
+            int t = k32 / W; t /= 3;
+            const int Y0 = t % L, z = t / L;
+            if (z >= d.H) { err |= 1; continue; }                                // :2109 IndexError at the corner's own position
+            int first = INT_MAX;
+            for (int cell = X0 * L + tid; cell < cells; cell += NT) {           // positions x >= X0 only
+                const int y = cell - (cell / L) * L;
+                const int w = pw[cell];
+                if (y >= Y0 && w >= 0 && (w & 17) == 1 && (w >> 5) == z) { first = cell; break; }   // settles at z, untaken
+            }
+            first = g.min(first);
+            if (first == INT_MAX) continue;
+            const int sx = first / L, sy = first - sx * L;
+            int s = 0;
+            for (int f = tid; f < bx * by; f += NT) { const int i = f / by, j = f - i * by; s += hm[(sx + i) * L + sy + j]; }
+            s = g.sum(s);                                                        // (its barrier orders the store below after
+            if (tid == 0) pw[first] |= 16;                                       //  every read of this walk) settled: taken
+            const int semp = cnt.empty + bx * by * z - s;
+            const double r = tap_score(cfg, cnt, vol, gmax, z, bz, semp, 1);
+            if (r > wr) { wr = r; px = sx; py = sy; pz = z; pstab = 1; pemp = semp; }    // first maximum in walk order
+        }
+    }
+    const bool placed = wr > 0.0;
+    err = g.orr(err);
+    if (placed) {                                                                // tools.py:2167-2174
+        for (int f = tid; f < bx * by; f += NT) {
+            const int i = f / by, j = f - i * by;
+            const int cidx = (px + i) * L + py + j;
+            hm[cidx] = pz + bz;
+            if (ghm) ghm[cidx] = pz + bz;
+        }
+        cnt.valid += vol;
+        cnt.empty = pemp;
+        cnt.nstable += pstab;
+        if (pz + bz > d.H) err |= 1;                                           // :2169 numpy clips silently
+    }
+    __syncthreads();
+    Placement res = {0, 0, 0, 0, 0};
+    if (placed) { res.placed = 1; res.x = px; res.y = py; res.z = pz; res.stab = pstab; }
+    return res;
+}
+
+template <int NT, bool HARD>
+__device__ __forceinline__ Placement big_wg_place(BigWg<NT> &g, const tap_env_desc &d, const uint32_t *lut, int32_t *hm,
+                                                  int32_t *ghm, int gmax, Counters &cnt, int &err, int bx, int by, int bz)
+{
+    if (__builtin_expect(big_is_wide(d.D, bx, by), 0))                            // workgroup-uniform, rare
+        return big_wg_place_t<NT, HARD, true>(g, d, lut, hm, ghm, gmax, cnt, err, bx, by, bz);
+    return big_wg_place_t<NT, HARD, false>(g, d, lut, hm, ghm, gmax, cnt, err, bx, by, bz);
+}
+
+// tap_env_step / tap_env_step_gather: one lock-step of container blockIdx.x (gather / block, placement, state and
+// results out, feature), as k_big_step
+template <int NT, bool HARD>
+__global__ void __launch_bounds__(NT) k_big_wg_step(StepArgs a)
+{
+    extern __shared__ int32_t big_lds[];
+    __shared__ BigWgRed red;
+    BigWg<NT> g = {&red, 0, (int)(threadIdx.x >> 6), (int)(threadIdx.x & 63)};
+    const int env = blockIdx.x, tid = threadIdx.x;
+    const int B = a.d.B, D = a.d.D, W = a.d.W, L = a.d.L, cells = W * L;
+    int32_t *hm = big_lds, *ghm = a.v.hm + (size_t)env * cells;
+    int gmax = 0;
+    for (int c = tid; c < cells; c += NT) { const int h = ghm[c]; hm[c] = h; gmax = max(gmax, h); }
+    gmax = g.max(gmax);                                                          // (its barrier publishes the tile)
+    int dims[3] = {1, 1, 1};
+    if (a.static_) {                                                             // model.py:404-412
+        bool badp;
+        const long p = tap_col((long)a.ptr[env], a.nR, badp);
+        for (int k = 0; k < D; ++k) dims[k] = badp ? 0 : (int)a.static_[((size_t)env * a.static_rows + 1 + k) * a.nR + p];
+    } else if (a.blocks_dtype == TAP_DT_F32) {
+        for (int k = 0; k < D; ++k) dims[k] = (int)((const float *)a.blocks)[(size_t)env * D + k];
+    } else {
+        for (int k = 0; k < D; ++k) dims[k] = ((const int32_t *)a.blocks)[(size_t)env * D + k];
+    }
+    const bool act = !a.active || a.active[env] != 0;
+    const int4 cv = reinterpret_cast<const int4 *>(a.v.cnt)[env];
+    Counters cnt = {cv.x, cv.y, cv.z, cv.w};
+    const int bx = dims[0], by = D == 3 ? dims[1] : 1, bz = dims[D - 1];
+    int err = 0;
+    bool do_step = act;
+    if (act && cnt.count >= a.d.n_max) { err |= 2; do_step = false; }
+    if (act && (bx < 1 || by < 1 || bz < 1)) { err |= 4; do_step = false; }
+    if (act && do_step && (D == 3 && (bx > TAP_WIDE_MAX_SIDE || by > TAP_WIDE_MAX_SIDE) && bx <= W && by <= L)) {
+        err |= 4; do_step = false;                                               // footprint beyond the support masks
+    }
+    if (do_step) {                                                               // workgroup-uniform
+        const int step = cnt.count;
+        const Placement pl = big_wg_place<NT, HARD>(g, a.d, a.lut, hm, ghm, gmax, cnt, err, bx, by, bz);
+        cnt.count += 1;                                                          // tools.py:3713
+        if (tid == 0) {
+            reinterpret_cast<int4 *>(a.v.cnt)[env] = make_int4(cnt.valid, cnt.empty, cnt.nstable, cnt.count);
+            int32_t *q = a.v.pos + (size_t)step * D * B + env;
+            q[0] = pl.x;
+            if (D == 3) { q[B] = pl.y; q[2 * (size_t)B] = pl.z; } else q[B] = pl.z;
+            a.v.stable[(size_t)step * B + env] = (uint8_t)pl.stab;
+        }
+    }
+    if (tid == 0 && err) a.v.err[env] |= err;
+    if (a.feature_out) {                                                         // tools.py:3716-3744, threads over the cells
+        float *out = a.feature_out + (size_t)env * a.flen;
+        if (a.d.feature == TAP_FEAT_DIFF) {
+            if (D == 2) { for (int c = tid; c + 1 < W; c += NT) out[c] = (float)(hm[c + 1] - hm[c]); }
+            else
+                for (int c = tid; c < cells; c += NT) {
+                    const int x = c / L, y = c - x * L;
+                    out[c] = (float)(x > 0 ? hm[c] - hm[c - L] : 0);
+                    out[cells + c] = (float)(y > 0 ? hm[c] - hm[c - 1] : 0);
+                }
+        } else {
+            int mn = 0;
+            if (a.d.feature == TAP_FEAT_ZERO) {
+                mn = INT_MAX;
+                for (int c = tid; c < cells; c += NT) mn = min(mn, hm[c]);
+                mn = g.min(mn);
+            }
+            for (int c = tid; c < cells; c += NT) out[c] = (float)(hm[c] - mn);
+        }
+    }
+}
+
+// tap_pack_blocks / tap_episode_reward / tap_episode_scores: a whole episode of container blockIdx.x with its height-map
+// in LDS across the n placements, as k_big_wave_episode (every thread reads the tour entry of the step itself: the
+// same address on all of them)
+template <int NT, bool HARD>
+__global__ void __launch_bounds__(NT) k_big_wg_episode(EpisodeArgs a)
+{
+    extern __shared__ int32_t big_lds[];
+    __shared__ BigWgRed red;
+    BigWg<NT> g = {&red, 0, (int)(threadIdx.x >> 6), (int)(threadIdx.x & 63)};
+    const int env = blockIdx.x, tid = threadIdx.x;
+    const int D = a.d.D, W = a.d.W, L = a.d.L, cells = W * L, n = a.n;
+    int32_t *hm = big_lds;
+    for (int c = tid; c < cells; c += NT) hm[c] = 0;
+    __syncthreads();
+    Counters cnt = {0, 0, 0, 0};
+    int err = 0, gmax = 0;
+    for (int t = 0; t < n; ++t) {
+        int dims[3];
+        const bool in = D == 2 ? episode_block<2>(a, env, t, true, dims, err) : episode_block<3>(a, env, t, true, dims, err);
+        const int bx = dims[0], by = D == 3 ? dims[1] : 1, bz = D == 3 ? dims[2] : dims[1];
+        bool do_step = in;
+        if (in && cnt.count >= a.d.n_max) { err |= 2; do_step = false; }
+        if (in && (bx < 1 || by < 1 || bz < 1)) { err |= 4; do_step = false; }
+        if (do_step && (D == 3 && (bx > TAP_WIDE_MAX_SIDE || by > TAP_WIDE_MAX_SIDE) && bx <= W && by <= L)) {
+            err |= 4; do_step = false;                                            // footprint beyond the support masks
+        }
+        Placement pl = {0, 0, 0, 0, 0};
+        if (do_step) {                                                            // workgroup-uniform
+            pl = big_wg_place<NT, HARD>(g, a.d, a.lut, hm, nullptr, gmax, cnt, err, bx, by, bz);
+            if (pl.placed) gmax = max(gmax, pl.z + bz);
+            cnt.count += 1;                                                       // tools.py:3713
+        }
+        if (tid == 0) {
+            if (a.pos_out) {
+                int32_t *pp = a.pos_out + ((size_t)env * n + t) * D;
+                pp[0] = pl.x;
+                if (D == 3) { pp[1] = pl.y; pp[2] = pl.z; } else pp[1] = pl.z;
+            }
+            if (a.stable_out) a.stable_out[(size_t)env * n + t] = (uint8_t)pl.stab;
+        }
+    }
+    if (tid == 0) episode_finish(a, env, cnt, gmax, err);
+}
+
+// threads per container of the workgroup kernels (A/B runs: TAP_BIG_WG_THREADS = 256 / 512 / 1024, read once)
+static int big_wg_threads(bool hard)
+{
+    static const int forced = [] {
+        const char *e = getenv("TAP_BIG_WG_THREADS");
+        const int v = e ? atoi(e) : 0;
+        return (v == 256 || v == 512 || v == 1024) ? v : 0;
+    }();
+    return forced ? forced : hard ? TAP_BIG_WG_THREADS_HARD : TAP_BIG_WG_THREADS_SOFT;
+}
+
+static size_t big_wg_lds(const tap_env_desc &d) { return (size_t)d.W * d.L * sizeof(int32_t) * ((d.flags & TAP_F_HARD) ? 2 : 1); }
+
+template <class Launch>
+static int big_wg_dispatch(tap_ctx *ctx, const tap_env_desc &d, Launch launch)
+{
+    const size_t lds = big_wg_lds(d);
+    if (lds + sizeof(BigWgRed) > tap_lds_limit(ctx))
+        return tap_fail(ctx, TAP_E_UNSUPPORTED, "%d x %d containers%s: the height-map does not fit a workgroup's LDS", d.W, d.L,
+                        (d.flags & TAP_F_HARD) ? " with hard rewards" : "");
+    const bool hard = (d.flags & TAP_F_HARD) != 0;
+    switch (big_wg_threads(hard)) {
+    case 256: return hard ? launch(std::integral_constant<int, 256>(), std::true_type(), lds) : launch(std::integral_constant<int, 256>(), std::false_type(), lds);
+    case 1024: return hard ? launch(std::integral_constant<int, 1024>(), std::true_type(), lds) : launch(std::integral_constant<int, 1024>(), std::false_type(), lds);
+    default: return hard ? launch(std::integral_constant<int, 512>(), std::true_type(), lds) : launch(std::integral_constant<int, 512>(), std::false_type(), lds);
+    }
+}
+
+static int big_wg_step(tap_ctx *ctx, const StepArgs &a, hipStream_t st)
+{
+    return big_wg_dispatch(ctx, a.d, [&](auto nt, auto hard, size_t lds) -> int {
+        constexpr int NT = decltype(nt)::value;
+        constexpr bool H = decltype(hard)::value;
+        TAP_HIP_CHECK(ctx, tap_allow_lds(k_big_wg_step<NT, H>, lds));
+        hipLaunchKernelGGL((k_big_wg_step<NT, H>), dim3(a.d.B), dim3(NT), lds, st, a);
+        TAP_LAUNCH_CHECK(ctx, "k_big_wg_step");
+        return TAP_OK;
+    });
+}
+
+static int big_wg_episode(tap_ctx *ctx, const EpisodeArgs &a, hipStream_t st)
+{
+    return big_wg_dispatch(ctx, a.d, [&](auto nt, auto hard, size_t lds) -> int {
+        constexpr int NT = decltype(nt)::value;
+        constexpr bool H = decltype(hard)::value;
+        TAP_HIP_CHECK(ctx, tap_allow_lds(k_big_wg_episode<NT, H>, lds));
+        hipLaunchKernelGGL((k_big_wg_episode<NT, H>), dim3(a.B), dim3(NT), lds, st, a);
+        TAP_LAUNCH_CHECK(ctx, "k_big_wg_episode");
+        return TAP_OK;
+    });
+}
+
 int tap_big_episode(tap_ctx *ctx, const EpisodeArgs &a, hipStream_t st)
 {
     if (a.B == 0) return TAP_OK;
+    if (a.d.W * a.d.L > TAP_BIG_WAVE_CELLS) return big_wg_episode(ctx, a, st);   // one workgroup per container
     const bool hard = (a.d.flags & TAP_F_HARD) != 0;
     const size_t tile = (size_t)a.d.W * a.d.L * sizeof(int32_t) * (hard ? 4 : 1);
     int waves = TAP_BLOCK / 64;
@@ -668,6 +1038,7 @@ int tap_big_step(tap_ctx *ctx, const StepArgs &a, void *state, hipStream_t st)
     const int grid = (a.d.B + TAP_BLOCK - 1) / TAP_BLOCK;
     if (grid == 0) return TAP_OK;
     (void)state;
+    if (a.d.W * a.d.L > TAP_BIG_WAVE_CELLS) return big_wg_step(ctx, a, st);     // one workgroup per container
     const bool hard = (a.d.flags & TAP_F_HARD) != 0;
     const size_t tile = (size_t)a.d.W * a.d.L * sizeof(int32_t) * (hard ? 4 : 1);
     int waves = TAP_BLOCK / 64;                                                  // per workgroup: as many as the LDS holds tiles for
@@ -694,7 +1065,7 @@ int tap_big_step(tap_ctx *ctx, const StepArgs &a, void *state, hipStream_t st)
 // placement wavefronts per workgroup of the fused step for this shape, 0 = no fused kernel (the tile does not fit)
 static int big_transition_pw(const tap_ctx *ctx, const tap_env_desc *d, int nR)
 {
-    if (tap_wave_kernels_off() || d->strategy != TAP_LB_GREEDY) return 0;
+    if (tap_wave_kernels_off() || d->strategy != TAP_LB_GREEDY || d->W * d->L > TAP_BIG_WAVE_CELLS) return 0;   // (above: two launches)
     const bool hard = (d->flags & TAP_F_HARD) != 0;
     const size_t tile = (size_t)d->W * d->L * sizeof(int32_t) * (hard ? 4 : 1);
     for (int pw = 4; pw >= 1; pw >>= 1)

@@ -172,8 +172,8 @@ int tap_desc_validate(tap_ctx *ctx, const tap_env_desc *d)
         (d->D == 2 && d->L != 1))
         return tap_fail(ctx, TAP_E_INVALID, "bad descriptor B=%d D=%d W=%d L=%d H=%d n=%d", d->B,
                         d->D, d->W, d->L, d->H, d->n_max);
-    if (tap_is_big(d)) {                                           // one wavefront per container (big.hip)
-        if (d->W * d->L > 4096) return tap_fail(ctx, TAP_E_UNSUPPORTED, "W*L = %d cells > 4096", d->W * d->L);
+    if (tap_is_big(d)) {                                           // one wavefront (above 4 096 cells: one workgroup) per container (big.hip)
+        if (d->W * d->L > TAP_BIG_WG_CELLS) return tap_fail(ctx, TAP_E_UNSUPPORTED, "W*L = %d cells > %d", d->W * d->L, TAP_BIG_WG_CELLS);
     } else if (d->strategy == TAP_LB) {                            // one thread per container (lb.hip)
         if (d->W > 248 || (d->D == 3 && d->L > 248)) return tap_fail(ctx, TAP_E_UNSUPPORTED, "legacy LB: side > 248");
     } else if (tap_is_big_macs(d)) {                               // one wavefront per container (macs_big.hip)

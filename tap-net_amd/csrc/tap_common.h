@@ -111,7 +111,9 @@ struct EnvView {
 
 inline size_t tap_align256(size_t x) { return (x + 255) & ~size_t(255); }
 
-// LB_GREEDY containers beyond the lane-per-cell kernels (more than 64 cells, or a 3D side above 8): big.hip
+// LB_GREEDY containers beyond the lane-per-cell kernels (more than 64 cells, or a 3D side above 8): big.hip, up to
+// TAP_BIG_WG_CELLS cells (above 4 096: one workgroup per container with the height-map in its LDS)
+constexpr int TAP_BIG_WG_CELLS = 16384;
 inline bool tap_is_big(const tap_env_desc *d)
 {
     return d->strategy == TAP_LB_GREEDY && (d->W * d->L > 64 || (d->D == 3 && (d->W > 8 || d->L > 8)));

@@ -55,7 +55,8 @@ def pack_blocks(blocks, container_size, reward_type='C+P+S-lb-hard'):
     c = _lib.ctx(dev)
     try:
         # one launch for every container size (generate.py:908 accepts any --initial_container_width): lane-per-cell
-        # groups up to 64 cells, one wavefront per container above (big.hip: k_big_wave_episode)
+        # groups up to 64 cells, one wavefront per container above (big.hip: k_big_wave_episode), one workgroup per container
+        # above 4 096 cells (k_big_wg_episode, up to 16 384)
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().tap_pack_blocks(c, C.byref(desc), B, n, _lib.ptr(blocks), _lib.ptr(rew),
                                                   _lib.ptr(pos), _lib.ptr(st), None, _lib.stream_of(dev)), c)

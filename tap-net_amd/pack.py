@@ -726,7 +726,7 @@ def reward(static, tour_indices, reward_type, input_type, allow_rot, container_w
     c = _lib.ctx(st.device)
     try:
         # one launch for every container size: lane-per-cell groups up to 64 cells, one wavefront per container with the
-        # height-map in LDS above (big.hip: k_big_wave_episode)
+        # height-map in LDS above (big.hip: k_big_wave_episode; above 4 096 cells one workgroup per container, k_big_wg_episode)
         with torch.cuda.device(st.device):
             _lib.check(_lib.lib().tap_episode_reward(c, C.byref(desc), B, n, _lib.ptr(st), rows, nR,
                                                      _lib.ptr(tour), _lib.ptr(out), None, None,
