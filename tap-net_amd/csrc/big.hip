@@ -1079,24 +1079,19 @@ int tap_big_transition(tap_ctx *ctx, const tap_env_desc *d, const TransArgs &a, 
 {
     const int pw = big_transition_pw(ctx, d, a.m.nR);
     if (pw == 0) return tap_fail(ctx, TAP_E_UNSUPPORTED, "no fused step for this container");
-    const int mode = a.m.bits_in ? 1 : 2;
     const bool hard = (d->flags & TAP_F_HARD) != 0;
     const size_t tile = (size_t)d->W * d->L * sizeof(int32_t) * (hard ? 4 : 1);
     const int sw = (pw + 1) / 2;
     const size_t lds = (size_t)pw * tile + (size_t)sw * 2 * 3 * a.m.nR * sizeof(float);
     const dim3 g((d->B + pw - 1) / pw), blk(64 * (pw + sw));
     if (g.x == 0) return TAP_OK;
-#define TAP_BT(H_, NC_, M_) do { TAP_HIP_CHECK(ctx, tap_allow_lds(k_big_transition<H_, NC_, M_>, lds)); \
-        hipLaunchKernelGGL((k_big_transition<H_, NC_, M_>), g, blk, lds, st, a, pw); } while (0)
-#define TAP_BT_M(H_, NC_) do { if (mode == 1) TAP_BT(H_, NC_, 1); else TAP_BT(H_, NC_, 2); } while (0)
-#define TAP_BT_NC(H_) do { switch (mask_fast_path_cols(a.m)) { case 1: TAP_BT_M(H_, 1); break; case 2: TAP_BT_M(H_, 2); break; \
-        default: TAP_BT_M(H_, 4); break; } } while (0)
-    if (hard) TAP_BT_NC(true); else TAP_BT_NC(false);
-#undef TAP_BT_NC
-#undef TAP_BT_M
-#undef TAP_BT
-    TAP_LAUNCH_CHECK(ctx, "k_big_transition");
-    return TAP_OK;
+    const TapVariant v = tap_stream_variant(TAP_SV_BIG, tap_mask_facts(a.m), TapLaunchFacts{d->D, 64, pw, d->B, d->W, d->L, hard});
+    return tap_launch_variant<TAP_SV_BIG>(ctx, "k_big_transition", v, [&](auto k) -> int {
+        using K = decltype(k);
+        TAP_HIP_CHECK(ctx, tap_allow_lds(k_big_transition<(K::extra != 0), K::nc, K::mode>, lds));
+        hipLaunchKernelGGL((k_big_transition<(K::extra != 0), K::nc, K::mode>), g, blk, lds, st, a, pw);
+        return TAP_OK;
+    });
 }
 
 int tap_big_feature(tap_ctx *ctx, const tap_env_desc *d, const EnvView &v, float *out, int flen, hipStream_t st)

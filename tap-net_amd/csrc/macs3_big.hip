@@ -223,18 +223,16 @@ int tap_macs3_wave_transition(tap_ctx *ctx, const tap_env_desc *d, const TransAr
     if (pw == 0) return tap_fail(ctx, TAP_E_UNSUPPORTED, "no fused step for this container");
     if (!a.s.v.scratch || !a.s.v.occ) return tap_fail(ctx, TAP_E_INVALID, "MACS 3D above 64 cells: the state blob has no scratch section");
     const int tile_u64 = (int)m3w_tile_u64(d->W * d->L, (d->H + 63) / 64, d->n_max, macs3_big_cap(d->n_max));
-    const int mode = a.m.bits_in ? 1 : 2;
     const size_t lds = (size_t)pw * tile_u64 * 8 + (size_t)pw * 3 * a.m.nR * sizeof(float);
     const dim3 g((d->B + pw - 1) / pw), blk(64 * pw);
     if (g.x == 0) return TAP_OK;
-#define TAP_MT(NC_, M_) do { TAP_HIP_CHECK(ctx, tap_allow_lds(k_macs3d_wave_transition<NC_, M_>, lds)); \
-        hipLaunchKernelGGL((k_macs3d_wave_transition<NC_, M_>), g, blk, lds, st, a, pw, tile_u64); } while (0)
-#define TAP_MT_M(NC_) do { if (mode == 1) TAP_MT(NC_, 1); else TAP_MT(NC_, 2); } while (0)
-    switch (mask_fast_path_cols(a.m)) { case 1: TAP_MT_M(1); break; case 2: TAP_MT_M(2); break; default: TAP_MT_M(4); break; }
-#undef TAP_MT_M
-#undef TAP_MT
-    TAP_LAUNCH_CHECK(ctx, "k_macs3d_wave_transition");
-    return TAP_OK;
+    const TapVariant v = tap_stream_variant(TAP_SV_MACS3_WAVE, tap_mask_facts(a.m), TapLaunchFacts{3, 64, pw, d->B, d->W, d->L, false});
+    return tap_launch_variant<TAP_SV_MACS3_WAVE>(ctx, "k_macs3d_wave_transition", v, [&](auto k) -> int {
+        using K = decltype(k);
+        TAP_HIP_CHECK(ctx, tap_allow_lds(k_macs3d_wave_transition<K::nc, K::mode>, lds));
+        hipLaunchKernelGGL((k_macs3d_wave_transition<K::nc, K::mode>), g, blk, lds, st, a, pw, tile_u64);
+        return TAP_OK;
+    });
 }
 
 int tap_macs3_big_step(tap_ctx *ctx, const StepArgs &a, hipStream_t st)

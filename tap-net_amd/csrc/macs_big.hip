@@ -654,18 +654,16 @@ int tap_macs_wave_transition(tap_ctx *ctx, const tap_env_desc *d, const TransArg
     const int pw = macs2d_transition_pw(ctx, d, a.m.nR);
     if (pw == 0) return tap_fail(ctx, TAP_E_UNSUPPORTED, "no fused step for this container");
     const int cap = macs_big_cap(d->W, d->n_max), tile_ints = (int)macs_wave_tile_ints(d->W, cap, d->n_max);
-    const int mode = a.m.bits_in ? 1 : 2;
     const size_t lds = (size_t)pw * tile_ints * sizeof(int32_t) + (size_t)pw * 3 * a.m.nR * sizeof(float);
     const dim3 g((d->B + pw - 1) / pw), blk(64 * pw);
     if (g.x == 0) return TAP_OK;
-#define TAP_MT(NC_, M_) do { TAP_HIP_CHECK(ctx, tap_allow_lds(k_macs2d_wave_transition<NC_, M_>, lds)); \
-        hipLaunchKernelGGL((k_macs2d_wave_transition<NC_, M_>), g, blk, lds, st, a, cap, pw, tile_ints); } while (0)
-#define TAP_MT_M(NC_) do { if (mode == 1) TAP_MT(NC_, 1); else TAP_MT(NC_, 2); } while (0)
-    switch (mask_fast_path_cols(a.m)) { case 1: TAP_MT_M(1); break; case 2: TAP_MT_M(2); break; default: TAP_MT_M(4); break; }
-#undef TAP_MT_M
-#undef TAP_MT
-    TAP_LAUNCH_CHECK(ctx, "k_macs2d_wave_transition");
-    return TAP_OK;
+    const TapVariant v = tap_stream_variant(TAP_SV_MACS_WAVE, tap_mask_facts(a.m), TapLaunchFacts{2, 64, pw, d->B, d->W, d->L, false});
+    return tap_launch_variant<TAP_SV_MACS_WAVE>(ctx, "k_macs2d_wave_transition", v, [&](auto k) -> int {
+        using K = decltype(k);
+        TAP_HIP_CHECK(ctx, tap_allow_lds(k_macs2d_wave_transition<K::nc, K::mode>, lds));
+        hipLaunchKernelGGL((k_macs2d_wave_transition<K::nc, K::mode>), g, blk, lds, st, a, cap, pw, tile_ints);
+        return TAP_OK;
+    });
 }
 
 // -> TAP_OK when launched, TAP_E_UNSUPPORTED (no message) when a container's tile does not fit a wave's share of the LDS

@@ -108,19 +108,12 @@ static int launch_mask_step(tap_ctx *ctx, const MaskArgs &a, hipStream_t st)
     if (grid == 0) return TAP_OK;
     const bool wide = (a.bits_in || mask_builds_bits(a)) && a.rows > 64;     // two words per column
     const size_t lds = (size_t)ENVS_PER_BLOCK * (wide ? 4 : 3) * a.nR * sizeof(float);
-    const int mode = (a.bits_in ? 1 : mask_builds_bits(a) ? 2 : 0) + (wide ? 2 : 0);
-#define TAP_LAUNCH_T(NC_, M_, LDS_) hipLaunchKernelGGL((k_mask_step<NC_, M_>), dim3(grid), dim3(TAP_BLOCK), LDS_, st, TAP_MASK_HOT_ARGS(a), a)
-#define TAP_LAUNCH_M(NC_) do { if (mode == 1) TAP_LAUNCH_T(NC_, 1, lds); else if (mode == 2) TAP_LAUNCH_T(NC_, 2, lds); else if (mode == 3) TAP_LAUNCH_T(NC_, 3, lds); else if (mode == 4) TAP_LAUNCH_T(NC_, 4, lds); else TAP_LAUNCH_T(NC_, 0, lds); } while (0)
-    switch (mask_fast_path_cols(a)) {
-    case 1: TAP_LAUNCH_M(1); break;
-    case 2: TAP_LAUNCH_M(2); break;
-    case 4: TAP_LAUNCH_M(4); break;
-    default: TAP_LAUNCH_T(0, 0, 0); break;
-    }
-#undef TAP_LAUNCH_M
-#undef TAP_LAUNCH_T
-    TAP_LAUNCH_CHECK(ctx, "k_mask_step");
-    return TAP_OK;
+    const TapVariant v = tap_stream_variant(TAP_SV_MASK_STEP, tap_mask_facts(a), TapLaunchFacts{});
+    return tap_launch_variant<TAP_SV_MASK_STEP>(ctx, "k_mask_step", v, [&](auto k) -> int {
+        using K = decltype(k);
+        hipLaunchKernelGGL((k_mask_step<K::nc, K::mode>), dim3(grid), dim3(TAP_BLOCK), K::nc ? lds : 0, st, TAP_MASK_HOT_ARGS(a), a);
+        return TAP_OK;
+    });
 }
 
 static int check_shape(tap_ctx *ctx, int B, int n, int nR, int rows)

@@ -10,6 +10,7 @@
 #include <cstring>
 
 #include "tapenv.h"
+#include "tap_stream_variant.h"
 
 constexpr int TAP_CHK_SLOTS = 64;
 constexpr int TAP_BLOCK = 256; // threads per workgroup (4 wave64)
@@ -74,6 +75,19 @@ inline int tap_fail(tap_ctx *ctx, int code, const char *fmt, ...)
             return tap_fail(ctx, TAP_E_HIP, "launch of %s failed: %s", what,                 \
                             hipGetErrorString(e_));                                          \
     } while (0)
+
+// launches the entry of launcher KIND's table (tap_stream_variant.h) equal to v and checks the launch: launch(k) launches
+// the kernel with k::nc / k::mode / k::extra as template arguments and returns TAP_OK or an error
+template <int KIND, int D = 0, int G = 0, class Launch>
+inline int tap_launch_variant(tap_ctx *ctx, const char *kernel, const TapVariant &v, Launch &&launch)
+{
+    const int rc = tap_variant_dispatch<KIND, D, G>(v, launch);
+    if (rc == TAP_VARIANT_NONE)
+        return tap_fail(ctx, TAP_E_INVALID, "%s: no instantiation for nc %d, mode %d, extra %d", kernel, v.nc, v.mode, v.extra);
+    if (rc != TAP_OK) return rc;
+    TAP_LAUNCH_CHECK(ctx, kernel);
+    return TAP_OK;
+}
 
 
 // A column index handed in by the caller (ptr / tour).  The reference raises IndexError for a value

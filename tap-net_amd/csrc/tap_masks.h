@@ -7,6 +7,8 @@
 #include <type_traits>
 #include <cstdlib>
 
+#include "tap_stream_variant.h"
+
 constexpr size_t TAP_WT_MAX_BYTES = 64u << 20;   // write-through up to this many bytes of fp32 tensor per launch (see store_stream)
 
 struct MaskArgs {
@@ -44,10 +46,15 @@ struct MaskArgs {
 
 inline int tap_write_through(size_t bytes);
 
+// the last preloaded argument of a stream-wave kernel (TAP_MASK_HOT_ARGS / tap_mask_hot): c4_magic in the low 24 bits,
+// sb_mul and sb_add in the two bits at 24 and 26
+constexpr int TAP_HOT_MAGIC_MASK = 0xffffff, TAP_HOT_SB_MUL_SHIFT = 24, TAP_HOT_SB_ADD_SHIFT = 26, TAP_HOT_SB_MASK = 3;
+
 inline MaskArgs mask_finish(MaskArgs a)
 {
     const int c4 = a.nR >> 2;
     a.c4_magic = c4 > 0 ? 65536 / c4 + 1 : 0;
+    static_assert(65536 + 1 <= TAP_HOT_MAGIC_MASK, "c4_magic shares its kernel argument with sb_mul / sb_add (TAP_MASK_HOT_ARGS)");
     a.rp = c4 > 0 ? 64 / c4 : 0;
     a.wt = tap_write_through((size_t)a.B * a.rows * a.nR * sizeof(float));
     // (rotated roles only for write-through launches: the nontemporal form keeps round 4's store loops, see stream_wave_bits)
@@ -108,14 +115,15 @@ __host__ __device__ __forceinline__ bool mask_builds_bits(const MaskArgs &a) { r
 //  scalar-cache round trip in front of every load of the wave; c4_magic <= 2^16 + 1)
 #define TAP_MASK_HOT_ARGS(m) (m).ptr, (m).static_, (m).mask_in,                                                              \
         ((m).bits_in ? static_cast<const void *>((m).bits_in) : static_cast<const void *>((m).dyn_in)), (m).B, (m).nR,       \
-        (m).static_rows, ((m).c4_magic | (((m).sb_mul & 3) << 24) | (((m).sb_add & 3) << 26))
+        (m).static_rows, ((m).c4_magic | (((m).sb_mul & TAP_HOT_SB_MASK) << TAP_HOT_SB_MUL_SHIFT) |                           \
+                          (((m).sb_add & TAP_HOT_SB_MASK) << TAP_HOT_SB_ADD_SHIFT))
 // src_is_bits: compile-time in the callers (MODE == 1 / 3)
 __device__ __forceinline__ MaskArgs tap_mask_hot(const MaskArgs &k, bool src_is_bits, TAP_MASK_HOT_PARAMS)
 {
     MaskArgs m = k;
     m.ptr = h_ptr; m.static_ = h_static; m.mask_in = h_mask_in;
-    m.B = h_B; m.nR = h_nR; m.static_rows = h_static_rows; m.c4_magic = h_c4_magic & 0xffffff;
-    m.sb_mul = (h_c4_magic >> 24) & 3; m.sb_add = (h_c4_magic >> 26) & 3;
+    m.B = h_B; m.nR = h_nR; m.static_rows = h_static_rows; m.c4_magic = h_c4_magic & TAP_HOT_MAGIC_MASK;
+    m.sb_mul = (h_c4_magic >> TAP_HOT_SB_MUL_SHIFT) & TAP_HOT_SB_MASK; m.sb_add = (h_c4_magic >> TAP_HOT_SB_ADD_SHIFT) & TAP_HOT_SB_MASK;
     if (src_is_bits) m.bits_in = static_cast<const unsigned long long *>(h_src);
     else m.dyn_in = static_cast<const float *>(h_src);
     return m;
@@ -1110,4 +1118,11 @@ inline int mask_fast_path_cols(const MaskArgs &a)
     const bool ok = a.dyn_out && a.ptr && a.static_ && a.cs_in && (a.nR % 4 == 0) && a.nR <= 256 && a.rows >= 1 &&
                     ((reinterpret_cast<uintptr_t>(a.dyn_in) | reinterpret_cast<uintptr_t>(a.dyn_out)) % 16 == 0);
     return !ok ? 0 : a.nR <= 64 ? 1 : a.nR <= 128 ? 2 : 4;
+}
+
+// what the choice of a stream-wave kernel's instantiation reads from a launch's arguments (tap_stream_variant.h)
+inline TapMaskFacts tap_mask_facts(const MaskArgs &a)
+{
+    return TapMaskFacts{mask_fast_path_cols(a), a.bits_in ? 1 : mask_builds_bits(a) ? 2 : 0, a.inplace && a.dyn_out,
+                        a.ptr && a.static_ && a.mask_in, a.wt != 0, a.n, a.rows, a.update_rows, a.nR};
 }

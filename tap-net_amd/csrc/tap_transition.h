@@ -19,20 +19,7 @@ struct TransArgs {
 
 // ---- a stream wave: out-of-place copy of SPW consecutive slabs with the chosen rows cleared
 //      (pack.py:370-374), then the column sums + both masks (pack.py:318-329)
-// MODE & 3: 0 = fp32 copy with the column-sum shadow, 1 = on the bit shadow, 2 = first step (shadow built in the launch);
-// MODE & 4 (TAP_MODE_MERGED): the fp32 expansion walks the wave's two slabs as one run of rows (tap_masks.h:
-// stream_wave_bits, where the A/B figures are) instead of slab by slab
-// MODE & 8 / & 16 (TAP_MODE_C4_5 / _15): the window is the reference's own -- n = 10, rows = 30, nR = 20 (2D) / 60 (3D) --
-// and its shape is compiled in (stream_wave_bits_r4: C4S); the launcher checks the shape
-// (both bits, TAP_MODE_C4_10: c4's window, n = 20, rows = 60, nR = 40 -- the MACS 2D step, transition_macs.hip)
-// MODE & 32 (TAP_MODE_INPLACE, with MODE & 3 == 1 only): dyn_out holds the previous step's tensor (MaskArgs::inplace) --
-// the stream waves write the cleared rows' zeros instead of expanding the slab
-// MODE & 64 (TAP_MODE_FULL, with MODE & 3 == 1 and a compiled-in shape only): ptr, static and mask_in are all given and B is
-// a multiple of the workgroup's envs -- the stream wave carries no code for absent inputs or idle slabs (tap_masks.h: FULL)
-constexpr int TAP_MODE_MERGED = 4, TAP_MODE_C4_5 = 8, TAP_MODE_C4_15 = 16, TAP_MODE_C4_10 = 24, TAP_MODE_INPLACE = 32, TAP_MODE_FULL = 64;
-__host__ __device__ constexpr int tap_mode_shape(int D) { return D == 2 ? TAP_MODE_C4_5 : TAP_MODE_C4_15; }
-inline bool tap_mode_shape_ok(const MaskArgs &m, int D) { return m.n == 10 && m.rows == 30 && m.update_rows == 3 && m.nR == (D == 2 ? 20 : 60); }
-inline bool tap_mode_shape20_ok(const MaskArgs &m) { return m.n == 20 && m.rows == 60 && m.update_rows == 3 && m.nR == 40; }
+// MODE: the bits of tap_stream_variant.h (TAP_MODE_*), chosen by tap_stream_variant()
 template <int SPW, int NC, int MODE_>
 __device__ __forceinline__ void trans_stream_wave(const MaskArgs &m, int senv0, int lane, float *lds)
 {

@@ -140,42 +140,13 @@ static int launch_transition_v(tap_ctx *ctx, const TransArgs &a, hipStream_t st)
     const int grid = (a.s.d.B + EPB - 1) / EPB;
     if (grid == 0) return TAP_OK;
     const size_t lds = (size_t)EPB * 3 * a.m.nR * sizeof(float);
-    const int mode = a.m.bits_in ? 1 : mask_builds_bits(a.m) ? 2 : 0;
-#define TAP_LAUNCH_K(NC_, M_, LDS_) hipLaunchKernelGGL((k_transition<D, G, NC_, SW, M_>), dim3(grid), dim3(THREADS), LDS_, st, TAP_MASK_HOT_ARGS(a.m), a)
-    // the reference's own window (n = 10: rows = 30, nR = 20 / 60) on the bit shadow runs the instantiation with its shape
-    // compiled in (tap_transition.h: TAP_MODE_C4_*)
-    const bool shaped = tap_mode_shape_ok(a.m, D);
-    // ... and, for a step on a shadow the caller hands in, without the code for absent inputs and idle slabs when there are none
-#ifdef TAP_NO_FULL                                            // A/B builds
-    const bool full = false;
-#else
-    const bool full = mode == 1 && a.m.ptr && a.m.static_ && a.m.mask_in && a.s.d.B % EPB == 0;
-#endif
-#define TAP_LAUNCH_T(NC_, M_, LDS_) do { if constexpr ((NC_) == 1 && ((M_) & 3) == 1) { \
-            if (shaped && full) TAP_LAUNCH_K(NC_, ((M_) | tap_mode_shape(D) | TAP_MODE_FULL), LDS_); \
-            else if (shaped) TAP_LAUNCH_K(NC_, ((M_) | tap_mode_shape(D)), LDS_); else TAP_LAUNCH_K(NC_, M_, LDS_); } \
-        else if constexpr ((NC_) == 1 && ((M_) & 3) != 0) { if (shaped) TAP_LAUNCH_K(NC_, ((M_) | tap_mode_shape(D)), LDS_); else TAP_LAUNCH_K(NC_, M_, LDS_); } \
-        else TAP_LAUNCH_K(NC_, M_, LDS_); } while (0)
-    // 2D windows (nR = 2n columns: five store instructions per run at c2) take the run-of-rows expansion while the stores
-    // are write-through; 3D windows and every launch beyond the write-through limit keep the slab-by-slab loops
-    const bool merged = D == 2 && a.m.wt != 0;
-    // the caller's dyn_out already holds the previous step's tensor (a stepper on ONE dyn buffer): only the cleared rows are written
-    const bool inpl = mode == 1 && a.m.inplace && a.m.dyn_out;
-#define TAP_LAUNCH_M(NC_, LDS_) do { if (inpl) TAP_LAUNCH_T(NC_, (1 | TAP_MODE_INPLACE), LDS_); \
-        else if (mode == 1) { if (D == 2 && merged) TAP_LAUNCH_T(NC_, (D == 2 ? 5 : 1), LDS_); else TAP_LAUNCH_T(NC_, 1, LDS_); } \
-        else if (mode == 2) { if (D == 2 && merged) TAP_LAUNCH_T(NC_, (D == 2 ? 6 : 2), LDS_); else TAP_LAUNCH_T(NC_, 2, LDS_); } else TAP_LAUNCH_T(NC_, 0, LDS_); } while (0)
-    switch (mask_fast_path_cols(a.m)) {
-    case 1: TAP_LAUNCH_M(1, lds); break;
-    case 2: TAP_LAUNCH_M(2, lds); break;
-    case 4: TAP_LAUNCH_M(4, lds); break;
-    default: TAP_LAUNCH_T(0, 0, 0); break;
-    }
-#undef TAP_LAUNCH_M
-#undef TAP_LAUNCH_T
-#undef TAP_LAUNCH_K
-    (void)shaped; (void)inpl; (void)full;
-    TAP_LAUNCH_CHECK(ctx, "k_transition");
-    return TAP_OK;
+    const TapVariant v = tap_stream_variant(TAP_SV_TRANSITION, tap_mask_facts(a.m), TapLaunchFacts{D, G, EPB, a.s.d.B, 0, 0, false});
+    return tap_launch_variant<TAP_SV_TRANSITION, D, G>(ctx, "k_transition", v, [&](auto k) -> int {
+        using K = decltype(k);
+        hipLaunchKernelGGL((k_transition<D, G, K::nc, SW, K::mode>), dim3(grid), dim3(THREADS), K::nc ? lds : 0, st,
+                           TAP_MASK_HOT_ARGS(a.m), a);
+        return TAP_OK;
+    });
 }
 
 template <int D, int G> static int launch_transition(tap_ctx *ctx, const TransArgs &a, hipStream_t st)

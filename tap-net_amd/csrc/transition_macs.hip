@@ -118,30 +118,6 @@ __global__ void __launch_bounds__((TransGeom<G, TAP_MACS_SW>::THREADS)) k_transi
 // -DTAP_M3_SPREAD (A/B builds): ONE container per placement wave at G = 32 -- the wave's second lane group idles on an
 // out-of-range env -- so that B = 4096 puts four placement waves on a SIMD instead of two, each running only its own
 // container's loop trips.
-// Loop form of the fp32 expansion in the MACS steps' stream waves: 5 / 6 = shadow (given / built) | TAP_MODE_MERGED, the
-// run-of-rows loop; 1 / 2 = slab by slab.  Round 6, same session, two runs each (profiles/r06_macs_merge_ab.txt), M env-steps/s,
-// run-of-rows against slab-by-slab: MACS 2D (c4's shape) 518.6 / 518.0 against 508.7 / 511.8 at B = 8 192, 461.8 / 482.5
-// against 467.7 / 482.8 at 32 768 (nontemporal stores from here on), 533.4 / 526.0 against 518.8 / 519.6 at 131 072 -- the
-// run-of-rows loop at every batch, unlike the LB_GREEDY step (transition.hip), whose 2D windows lose 15-20 % with it once
-// the stores are nontemporal; MACS 3D (c6's shape, nR = 60) 139.8 / 139.7 against 139.9 / 140.1 at B = 4 096, 195.2 / 195.6
-// against 197.2 / 197.8 at 32 768, 222.9 / 222.9 against 225.8 / 225.8 at 131 072 -- slab by slab, as for the LB_GREEDY
-// step's 3D windows.  -DTAP_MACS_NOMERGE / -DTAP_MACS_MERGE_ALL force one form everywhere (A/B builds).
-#if defined(TAP_MACS_NOMERGE)
-#define TAP_MACS_M1 1
-#define TAP_MACS_M2 2
-#define TAP_MACS3_M1 1
-#define TAP_MACS3_M2 2
-#elif defined(TAP_MACS_MERGE_ALL)
-#define TAP_MACS_M1 5
-#define TAP_MACS_M2 6
-#define TAP_MACS3_M1 5
-#define TAP_MACS3_M2 6
-#else
-#define TAP_MACS_M1 5
-#define TAP_MACS_M2 6
-#define TAP_MACS3_M1 1
-#define TAP_MACS3_M2 2
-#endif
 #ifdef TAP_M3_SPREAD
 template <int G> struct M3Spread { static constexpr bool on = G == 32; };
 #else
@@ -192,27 +168,13 @@ template <int G> static int launch_transition_macs3(tap_ctx *ctx, const TransArg
     const size_t lds = (size_t)EPB * 3 * a.m.nR * sizeof(float) +
                        (size_t)M3Geo<G>::GROUPS * macs3_group_words(G, a.s.d.n_max, a.s.d.H) * sizeof(int);
     if (lds > tap_lds_limit(ctx)) return tap_fail(ctx, TAP_E_UNSUPPORTED, "transition(MACS 3D): %zu bytes of LDS needed", lds);
-    const int mode = a.m.bits_in ? 1 : mask_builds_bits(a.m) ? 2 : 0;
-    // the reference's own 3D container (5 x 5, BASELINE c6; a 32-lane group) runs the instantiation with compile-time sides
-    const bool wl5 = G == 32 && a.s.d.W == 5 && a.s.d.L == 5;
-#define TAP_LAUNCH_W(NC_, M_, LDS_, WL_) do { TAP_HIP_CHECK(ctx, tap_allow_lds(k_transition_macs3<G, NC_, M_, WL_>, LDS_)); \
-        hipLaunchKernelGGL((k_transition_macs3<G, NC_, M_, WL_>), dim3(grid), dim3(THREADS), LDS_, st, a); } while (0)
-#define TAP_LAUNCH_T(NC_, M_, LDS_) do { if constexpr (G == 32) { if (wl5) TAP_LAUNCH_W(NC_, M_, LDS_, 5); else TAP_LAUNCH_W(NC_, M_, LDS_, 0); } \
-        else TAP_LAUNCH_W(NC_, M_, LDS_, 0); } while (0)
-    const bool inpl = mode == 1 && a.m.inplace && a.m.dyn_out;        // tap_masks.h: MaskArgs::inplace
-#define TAP_LAUNCH_M(NC_, LDS_) do { if (inpl) TAP_LAUNCH_T(NC_, (1 | TAP_MODE_INPLACE), LDS_); else if (mode == 1) TAP_LAUNCH_T(NC_, TAP_MACS3_M1, LDS_); else if (mode == 2) TAP_LAUNCH_T(NC_, TAP_MACS3_M2, LDS_); else TAP_LAUNCH_T(NC_, 0, LDS_); } while (0)
-    switch (mask_fast_path_cols(a.m)) {
-    case 1: TAP_LAUNCH_M(1, lds); break;
-    case 2: TAP_LAUNCH_M(2, lds); break;
-    case 4: TAP_LAUNCH_M(4, lds); break;
-    default: TAP_LAUNCH_T(0, 0, lds); break;
-    }
-#undef TAP_LAUNCH_M
-#undef TAP_LAUNCH_T
-#undef TAP_LAUNCH_W
-    (void)wl5; (void)inpl;
-    TAP_LAUNCH_CHECK(ctx, "k_transition_macs3");
-    return TAP_OK;
+    const TapVariant v = tap_stream_variant(TAP_SV_MACS3, tap_mask_facts(a.m), TapLaunchFacts{3, G, EPB, a.s.d.B, a.s.d.W, a.s.d.L, false});
+    return tap_launch_variant<TAP_SV_MACS3, 3, G>(ctx, "k_transition_macs3", v, [&](auto k) -> int {
+        using K = decltype(k);
+        TAP_HIP_CHECK(ctx, tap_allow_lds(k_transition_macs3<G, K::nc, K::mode, K::extra>, lds));
+        hipLaunchKernelGGL((k_transition_macs3<G, K::nc, K::mode, K::extra>), dim3(grid), dim3(THREADS), lds, st, a);
+        return TAP_OK;
+    });
 }
 
 int tap_macs_validate(tap_ctx *ctx, const tap_env_desc &d); // macs.hip
@@ -225,29 +187,13 @@ template <int G> static int launch_transition_macs(tap_ctx *ctx, const TransArgs
     const size_t lds = (size_t)EPB * 3 * a.m.nR * sizeof(float) +
                        (size_t)EPB * macs_group_words(G, a.s.d.H, a.s.d.n_max, a.s.d.W) * sizeof(int);
     if (lds > tap_lds_limit(ctx)) return tap_fail(ctx, TAP_E_UNSUPPORTED, "transition(MACS): %zu bytes of LDS needed", lds);
-    const int mode = a.m.bits_in ? 1 : mask_builds_bits(a.m) ? 2 : 0;
-    // BASELINE configs[3] (c4: W = 7, windows of 20 nodes) on the bit shadow runs the instantiation with the width and
-    // the window's shape compiled in
-    const bool c4shape = G == 8 && a.s.d.W == 7 && tap_mode_shape20_ok(a.m);
-#define TAP_LAUNCH_K(NC_, M_, LDS_, WC_) do { TAP_HIP_CHECK(ctx, tap_allow_lds(k_transition_macs<G, NC_, M_, WC_>, LDS_)); \
-        hipLaunchKernelGGL((k_transition_macs<G, NC_, M_, WC_>), dim3(grid), dim3(THREADS), LDS_, st, a); } while (0)
-#define TAP_LAUNCH_T(NC_, M_, LDS_) do { if constexpr (G == 8 && (NC_) == 1 && ((M_) & 3) != 0) { \
-            if (c4shape) TAP_LAUNCH_K(NC_, ((M_) | TAP_MODE_C4_10), LDS_, 7); else TAP_LAUNCH_K(NC_, M_, LDS_, 0); } \
-        else TAP_LAUNCH_K(NC_, M_, LDS_, 0); } while (0)
-    const bool inpl = mode == 1 && a.m.inplace && a.m.dyn_out;        // tap_masks.h: MaskArgs::inplace
-#define TAP_LAUNCH_M(NC_, LDS_) do { if (inpl) TAP_LAUNCH_T(NC_, (1 | TAP_MODE_INPLACE), LDS_); else if (mode == 1) TAP_LAUNCH_T(NC_, TAP_MACS_M1, LDS_); else if (mode == 2) TAP_LAUNCH_T(NC_, TAP_MACS_M2, LDS_); else TAP_LAUNCH_T(NC_, 0, LDS_); } while (0)
-    switch (mask_fast_path_cols(a.m)) {
-    case 1: TAP_LAUNCH_M(1, lds); break;
-    case 2: TAP_LAUNCH_M(2, lds); break;
-    case 4: TAP_LAUNCH_M(4, lds); break;
-    default: TAP_LAUNCH_T(0, 0, lds); break;
-    }
-#undef TAP_LAUNCH_M
-#undef TAP_LAUNCH_T
-#undef TAP_LAUNCH_K
-    (void)c4shape; (void)inpl;
-    TAP_LAUNCH_CHECK(ctx, "k_transition_macs");
-    return TAP_OK;
+    const TapVariant v = tap_stream_variant(TAP_SV_MACS, tap_mask_facts(a.m), TapLaunchFacts{2, G, EPB, a.s.d.B, a.s.d.W, a.s.d.L, false});
+    return tap_launch_variant<TAP_SV_MACS, 2, G>(ctx, "k_transition_macs", v, [&](auto k) -> int {
+        using K = decltype(k);
+        TAP_HIP_CHECK(ctx, tap_allow_lds(k_transition_macs<G, K::nc, K::mode, K::extra>, lds));
+        hipLaunchKernelGGL((k_transition_macs<G, K::nc, K::mode, K::extra>), dim3(grid), dim3(THREADS), lds, st, a);
+        return TAP_OK;
+    });
 }
 
 
