@@ -89,6 +89,16 @@ int tap_ctx_create(int device, tap_ctx **out);
 void tap_ctx_destroy(tap_ctx *ctx);
 const char *tap_last_error(const tap_ctx *ctx);
 
+/* Launch record of the precedence-update ("stream wave") kernels, for tests: every launch through the variant selector
+ * (tap_stream_variant.h) counts one hit on the context under the key (kind, D, G, nc, mode, extra, wt) -- kind a
+ * TapStreamKind, D / G the window dimension and lane group of the launcher's dispatch (0 where its table ignores them),
+ * (nc, mode, extra) the instantiation, wt 1 for write-through stores, 0 for nontemporal ones.  A launch captured into a
+ * hipGraph counts once, at capture.  tap_variant_hits writes up to `cap` rows of 8 ints (the key, then the count) and
+ * returns the number of rows the record holds (TAP_E_INVALID if a key found no slot since the last reset);
+ * tap_variant_hits_reset empties it. */
+int tap_variant_hits(tap_ctx *ctx, int32_t *out, int cap);
+int tap_variant_hits_reset(tap_ctx *ctx);
+
 /* ---- tools.Container, batched --------------------------------------------------------- */
 
 /* Fill `d` from the arguments of tools.Container.__init__ (tools.py:3611-3661), performing its

@@ -65,6 +65,8 @@ _PROTOS = {
     "tap_ctx_create": (_i, [_i, C.POINTER(_vp)]),
     "tap_ctx_destroy": (None, [_vp]),
     "tap_last_error": (C.c_char_p, [_vp]),
+    "tap_variant_hits": (_i, [_vp, C.POINTER(C.c_int32), _i]),
+    "tap_variant_hits_reset": (_i, [_vp]),
     "tap_env_desc_init": (_i, [C.POINTER(EnvDesc), _i, _i, C.POINTER(C.c_int32), _i,
                                C.c_char_p, C.c_char_p, C.c_char_p]),
     "tap_env_state_bytes": (_sz, [C.POINTER(EnvDesc)]),
@@ -178,6 +180,28 @@ def ctx(device):
                     raise TapError(st, lib().tap_status_string(st).decode())
                 c = _ctxs[idx] = h
     return c
+
+
+def variant_hits(device):
+    """The launch record of the stream-wave kernels on ``device``'s context (tapenv.h: tap_variant_hits): a dict
+    {(kind, D, G, nc, mode, extra, wt): launches}."""
+    c = ctx(device)
+    n = lib().tap_variant_hits(c, None, 0)
+    check(n if n < 0 else TAP_OK, c)
+    out = (C.c_int32 * (8 * max(n, 1)))()
+    n = lib().tap_variant_hits(c, out, n)
+    rows = [tuple(out[8 * i:8 * i + 8]) for i in range(n)]
+    return {r[:7]: r[7] for r in rows}
+
+
+def variant_keys(device):
+    """The set of (kind, D, G, nc, mode, extra, wt) launched on ``device`` since the last reset."""
+    return set(variant_hits(device))
+
+
+def variant_hits_reset(device):
+    c = ctx(device)
+    check(lib().tap_variant_hits_reset(c), c)
 
 
 def check(status, context):

@@ -1086,7 +1086,7 @@ int tap_big_transition(tap_ctx *ctx, const tap_env_desc *d, const TransArgs &a, 
     const dim3 g((d->B + pw - 1) / pw), blk(64 * (pw + sw));
     if (g.x == 0) return TAP_OK;
     const TapVariant v = tap_stream_variant(TAP_SV_BIG, tap_mask_facts(a.m), TapLaunchFacts{d->D, 64, pw, d->B, d->W, d->L, hard});
-    return tap_launch_variant<TAP_SV_BIG>(ctx, "k_big_transition", v, [&](auto k) -> int {
+    return tap_launch_variant<TAP_SV_BIG>(ctx, "k_big_transition", v, a.m.wt, [&](auto k) -> int {
         using K = decltype(k);
         TAP_HIP_CHECK(ctx, tap_allow_lds(k_big_transition<(K::extra != 0), K::nc, K::mode>, lds));
         hipLaunchKernelGGL((k_big_transition<(K::extra != 0), K::nc, K::mode>), g, blk, lds, st, a, pw);

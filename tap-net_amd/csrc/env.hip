@@ -83,6 +83,28 @@ extern "C" void tap_ctx_destroy(tap_ctx *ctx)
     delete ctx;
 }
 
+extern "C" int tap_variant_hits(tap_ctx *ctx, int32_t *out, int cap)
+{
+    if (!ctx || (cap > 0 && !out) || cap < 0) return TAP_E_INVALID;
+    std::lock_guard<std::mutex> g(ctx->hit_lock);
+    if (ctx->hits_full) return tap_fail(ctx, TAP_E_INVALID, "launch record full: more than %d keys", TAP_VARIANT_HIT_SLOTS);
+    const int n = ctx->nhits < cap ? ctx->nhits : cap;
+    for (int i = 0; i < n; ++i) {
+        memcpy(out + 8 * i, ctx->hits[i].key, sizeof(ctx->hits[i].key));
+        out[8 * i + 7] = ctx->hits[i].count;
+    }
+    return ctx->nhits;
+}
+
+extern "C" int tap_variant_hits_reset(tap_ctx *ctx)
+{
+    if (!ctx) return TAP_E_INVALID;
+    std::lock_guard<std::mutex> g(ctx->hit_lock);
+    ctx->nhits = 0;
+    ctx->hits_full = false;
+    return TAP_OK;
+}
+
 // tools.is_stable (tools.py:710-765) on explicit support masks -- see tapenv.h
 __global__ void __launch_bounds__(TAP_BLOCK) k_stable3d_eval(int bx, int by, const unsigned long long *masks, int n,
                                                              const uint32_t *lut, uint8_t *out)

@@ -658,7 +658,7 @@ int tap_macs_wave_transition(tap_ctx *ctx, const tap_env_desc *d, const TransArg
     const dim3 g((d->B + pw - 1) / pw), blk(64 * pw);
     if (g.x == 0) return TAP_OK;
     const TapVariant v = tap_stream_variant(TAP_SV_MACS_WAVE, tap_mask_facts(a.m), TapLaunchFacts{2, 64, pw, d->B, d->W, d->L, false});
-    return tap_launch_variant<TAP_SV_MACS_WAVE>(ctx, "k_macs2d_wave_transition", v, [&](auto k) -> int {
+    return tap_launch_variant<TAP_SV_MACS_WAVE>(ctx, "k_macs2d_wave_transition", v, a.m.wt, [&](auto k) -> int {
         using K = decltype(k);
         TAP_HIP_CHECK(ctx, tap_allow_lds(k_macs2d_wave_transition<K::nc, K::mode>, lds));
         hipLaunchKernelGGL((k_macs2d_wave_transition<K::nc, K::mode>), g, blk, lds, st, a, cap, pw, tile_ints);

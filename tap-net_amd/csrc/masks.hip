@@ -109,7 +109,7 @@ static int launch_mask_step(tap_ctx *ctx, const MaskArgs &a, hipStream_t st)
     const bool wide = (a.bits_in || mask_builds_bits(a)) && a.rows > 64;     // two words per column
     const size_t lds = (size_t)ENVS_PER_BLOCK * (wide ? 4 : 3) * a.nR * sizeof(float);
     const TapVariant v = tap_stream_variant(TAP_SV_MASK_STEP, tap_mask_facts(a), TapLaunchFacts{});
-    return tap_launch_variant<TAP_SV_MASK_STEP>(ctx, "k_mask_step", v, [&](auto k) -> int {
+    return tap_launch_variant<TAP_SV_MASK_STEP>(ctx, "k_mask_step", v, a.wt, [&](auto k) -> int {
         using K = decltype(k);
         hipLaunchKernelGGL((k_mask_step<K::nc, K::mode>), dim3(grid), dim3(TAP_BLOCK), K::nc ? lds : 0, st, TAP_MASK_HOT_ARGS(a), a);
         return TAP_OK;

@@ -8,12 +8,22 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 
 #include "tapenv.h"
 #include "tap_stream_variant.h"
 
 constexpr int TAP_CHK_SLOTS = 64;
 constexpr int TAP_BLOCK = 256; // threads per workgroup (4 wave64)
+
+// launches of the stream-wave kernels per instantiation (tap_launch_variant; tapenv.h: tap_variant_hits): the key is
+// (kind, D, G, nc, mode, extra, wt), D / G = 0 where the launcher's table ignores them
+// (314 instantiations, each with wt = 0 and 1: at most 628 keys)
+constexpr int TAP_VARIANT_HIT_SLOTS = 1024;
+struct TapVariantHit {
+    int32_t key[7];
+    int32_t count;
+};
 
 struct tap_ctx {
     int device;
@@ -22,7 +32,24 @@ struct tap_ctx {
     unsigned chk_next;  //   next slot
     size_t lds_limit;   // LDS a workgroup may allocate on this device (gfx950: 160 KiB per CU), queried at create
     char err[512];
+    std::mutex hit_lock;
+    int nhits;
+    bool hits_full;     // a key found no slot: tap_variant_hits reports it
+    TapVariantHit hits[TAP_VARIANT_HIT_SLOTS];
 };
+
+// counts one launch of an instantiation (host only: a launch captured into a hipGraph counts once, at capture)
+inline void tap_variant_hit(tap_ctx *ctx, int kind, int D, int G, const TapVariant &v, int wt)
+{
+    if (!ctx) return;
+    const int32_t key[7] = {kind, D, G, v.nc, v.mode, v.extra, wt ? 1 : 0};
+    std::lock_guard<std::mutex> g(ctx->hit_lock);
+    for (int i = 0; i < ctx->nhits; ++i)
+        if (memcmp(ctx->hits[i].key, key, sizeof(key)) == 0) { ctx->hits[i].count += 1; return; }
+    if (ctx->nhits == TAP_VARIANT_HIT_SLOTS) { ctx->hits_full = true; return; }
+    memcpy(ctx->hits[ctx->nhits].key, key, sizeof(key));
+    ctx->hits[ctx->nhits++].count = 1;
+}
 
 // LDS budget of one workgroup: what the device reports (hipDeviceAttributeMaxSharedMemoryPerBlock; 160 KiB on
 // gfx950), never the 64 KiB of earlier CDNA parts
@@ -77,15 +104,17 @@ inline int tap_fail(tap_ctx *ctx, int code, const char *fmt, ...)
     } while (0)
 
 // launches the entry of launcher KIND's table (tap_stream_variant.h) equal to v and checks the launch: launch(k) launches
-// the kernel with k::nc / k::mode / k::extra as template arguments and returns TAP_OK or an error
+// the kernel with k::nc / k::mode / k::extra as template arguments and returns TAP_OK or an error; wt = the launch's
+// MaskArgs::wt, which the launch record (tap_variant_hit) keeps beside the entry
 template <int KIND, int D = 0, int G = 0, class Launch>
-inline int tap_launch_variant(tap_ctx *ctx, const char *kernel, const TapVariant &v, Launch &&launch)
+inline int tap_launch_variant(tap_ctx *ctx, const char *kernel, const TapVariant &v, int wt, Launch &&launch)
 {
     const int rc = tap_variant_dispatch<KIND, D, G>(v, launch);
     if (rc == TAP_VARIANT_NONE)
         return tap_fail(ctx, TAP_E_INVALID, "%s: no instantiation for nc %d, mode %d, extra %d", kernel, v.nc, v.mode, v.extra);
     if (rc != TAP_OK) return rc;
     TAP_LAUNCH_CHECK(ctx, kernel);
+    tap_variant_hit(ctx, KIND, D, G, v, wt);
     return TAP_OK;
 }
 

@@ -141,7 +141,7 @@ static int launch_transition_v(tap_ctx *ctx, const TransArgs &a, hipStream_t st)
     if (grid == 0) return TAP_OK;
     const size_t lds = (size_t)EPB * 3 * a.m.nR * sizeof(float);
     const TapVariant v = tap_stream_variant(TAP_SV_TRANSITION, tap_mask_facts(a.m), TapLaunchFacts{D, G, EPB, a.s.d.B, 0, 0, false});
-    return tap_launch_variant<TAP_SV_TRANSITION, D, G>(ctx, "k_transition", v, [&](auto k) -> int {
+    return tap_launch_variant<TAP_SV_TRANSITION, D, G>(ctx, "k_transition", v, a.m.wt, [&](auto k) -> int {
         using K = decltype(k);
         hipLaunchKernelGGL((k_transition<D, G, K::nc, SW, K::mode>), dim3(grid), dim3(THREADS), K::nc ? lds : 0, st,
                            TAP_MASK_HOT_ARGS(a.m), a);

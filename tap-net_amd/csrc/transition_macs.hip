@@ -169,7 +169,7 @@ template <int G> static int launch_transition_macs3(tap_ctx *ctx, const TransArg
                        (size_t)M3Geo<G>::GROUPS * macs3_group_words(G, a.s.d.n_max, a.s.d.H) * sizeof(int);
     if (lds > tap_lds_limit(ctx)) return tap_fail(ctx, TAP_E_UNSUPPORTED, "transition(MACS 3D): %zu bytes of LDS needed", lds);
     const TapVariant v = tap_stream_variant(TAP_SV_MACS3, tap_mask_facts(a.m), TapLaunchFacts{3, G, EPB, a.s.d.B, a.s.d.W, a.s.d.L, false});
-    return tap_launch_variant<TAP_SV_MACS3, 3, G>(ctx, "k_transition_macs3", v, [&](auto k) -> int {
+    return tap_launch_variant<TAP_SV_MACS3, 3, G>(ctx, "k_transition_macs3", v, a.m.wt, [&](auto k) -> int {
         using K = decltype(k);
         TAP_HIP_CHECK(ctx, tap_allow_lds(k_transition_macs3<G, K::nc, K::mode, K::extra>, lds));
         hipLaunchKernelGGL((k_transition_macs3<G, K::nc, K::mode, K::extra>), dim3(grid), dim3(THREADS), lds, st, a);
@@ -188,7 +188,7 @@ template <int G> static int launch_transition_macs(tap_ctx *ctx, const TransArgs
                        (size_t)EPB * macs_group_words(G, a.s.d.H, a.s.d.n_max, a.s.d.W) * sizeof(int);
     if (lds > tap_lds_limit(ctx)) return tap_fail(ctx, TAP_E_UNSUPPORTED, "transition(MACS): %zu bytes of LDS needed", lds);
     const TapVariant v = tap_stream_variant(TAP_SV_MACS, tap_mask_facts(a.m), TapLaunchFacts{2, G, EPB, a.s.d.B, a.s.d.W, a.s.d.L, false});
-    return tap_launch_variant<TAP_SV_MACS, 2, G>(ctx, "k_transition_macs", v, [&](auto k) -> int {
+    return tap_launch_variant<TAP_SV_MACS, 2, G>(ctx, "k_transition_macs", v, a.m.wt, [&](auto k) -> int {
         using K = decltype(k);
         TAP_HIP_CHECK(ctx, tap_allow_lds(k_transition_macs<G, K::nc, K::mode, K::extra>, lds));
         hipLaunchKernelGGL((k_transition_macs<G, K::nc, K::mode, K::extra>), dim3(grid), dim3(THREADS), lds, st, a);
