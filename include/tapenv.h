@@ -96,6 +96,18 @@ const char *tap_last_error(const tap_ctx *ctx);
  * hipGraph counts once, at capture.  tap_variant_hits writes up to `cap` rows of 8 ints (the key, then the count) and
  * returns the number of rows the record holds (TAP_E_INVALID if a key found no slot since the last reset);
  * tap_variant_hits_reset empties it. */
+/* The whole-episode and rolling kernels count on the same record, under kinds 16 .. 21 (tap_common.h: TapHitKind), after
+ * the stream-wave kinds 0 .. 6.  Their keys, fields (kind, D, G, nc, mode, extra, wt):
+ *   16 k_episode<D, G, SOFT>                      (16, D, G, SOFT, 0, 0, 0)
+ *   17 k_episode_macs2<G, WIDE>                   (17, 2, G, WIDE, 0, 0, 0)
+ *   18 k_episode_macs3<G, WL>                     (18, 3, G, WL, 0, 0, 0)        WL = 5 for the 5 x 5 form, else 0
+ *   19 k_rolling_step<D, G, CH> / _soft           (19, D, G, SOFT, CH, 0, wt)    SOFT 1 = k_rolling_step_soft; CH -2, 0, 10
+ *   20 k_rolling_window<D, CH>                    (20, D, 0, 0, CH, 0, wt)       CH -2, 0, 10
+ *      k_rolling_window_wide<D, NW>               (20, D, 0, 1, NW, 0, wt)       NW 3, 4
+ *      k_rolling_window_big<D, MW>                (20, D, 0, 2, 0, MW, wt)       MW mask words 4, 16, 64
+ *   21 k_rolling_init<D>                          (21, D, 0, 0, 0, 0, 0)
+ *      k_rolling_init_big<D, MW>                  (21, D, 0, 1, 0, MW, 0)
+ * wt is the launch's RollArgs::wt (the window's fp32 stores; the init kernels store none), 0 for the episode kernels. */
 int tap_variant_hits(tap_ctx *ctx, int32_t *out, int cap);
 int tap_variant_hits_reset(tap_ctx *ctx);
 

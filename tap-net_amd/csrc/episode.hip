@@ -76,6 +76,7 @@ template <int D, int G> static int launch_episode(tap_ctx *ctx, const EpisodeArg
     if (a.d.flags & TAP_F_HARD) hipLaunchKernelGGL((k_episode<D, G, false>), dim3(grid), dim3(TAP_BLOCK), 0, st, a);
     else hipLaunchKernelGGL((k_episode<D, G, true>), dim3(grid), dim3(TAP_BLOCK), 0, st, a);
     TAP_LAUNCH_CHECK(ctx, "k_episode");
+    tap_variant_hit(ctx, TAP_HIT_EPISODE, D, G, TapVariant{(a.d.flags & TAP_F_HARD) ? 0 : 1, 0, 0}, 0);
     return TAP_OK;
 }
 
@@ -150,6 +151,7 @@ template <int G, bool WIDE> static int launch_episode_macs2(tap_ctx *ctx, const 
     TAP_HIP_CHECK(ctx, tap_allow_lds(k_episode_macs2<G, WIDE>, lds));
     hipLaunchKernelGGL((k_episode_macs2<G, WIDE>), dim3(grid), dim3(threads), lds, st, a);
     TAP_LAUNCH_CHECK(ctx, "k_episode_macs2");
+    tap_variant_hit(ctx, TAP_HIT_EPISODE_MACS2, 2, G, TapVariant{WIDE ? 1 : 0, 0, 0}, 0);
     return TAP_OK;
 }
 
@@ -223,12 +225,14 @@ template <int G> static int launch_episode_macs3(tap_ctx *ctx, const EpisodeArgs
             TAP_HIP_CHECK(ctx, tap_allow_lds(k_episode_macs3<G, 5>, lds));
             hipLaunchKernelGGL((k_episode_macs3<G, 5>), dim3(grid), dim3(threads), lds, st, a);
             TAP_LAUNCH_CHECK(ctx, "k_episode_macs3");
+            tap_variant_hit(ctx, TAP_HIT_EPISODE_MACS3, 3, G, TapVariant{5, 0, 0}, 0);
             return TAP_OK;
         }
     }
     TAP_HIP_CHECK(ctx, tap_allow_lds(k_episode_macs3<G>, lds));
     hipLaunchKernelGGL(k_episode_macs3<G>, dim3(grid), dim3(threads), lds, st, a);
     TAP_LAUNCH_CHECK(ctx, "k_episode_macs3");
+    tap_variant_hit(ctx, TAP_HIT_EPISODE_MACS3, 3, G, TapVariant{0, 0, 0}, 0);
     return TAP_OK;
 }
 

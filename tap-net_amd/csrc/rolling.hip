@@ -1346,11 +1346,13 @@ extern "C" int tap_rolling_init(tap_ctx *ctx, int B, int D, int N, const int32_t
         if (D == 2) TAP_ROLL_INIT(2); else TAP_ROLL_INIT(3);
 #undef TAP_ROLL_INIT
         TAP_LAUNCH_CHECK(ctx, "k_rolling_init_big");
+        tap_variant_hit(ctx, TAP_HIT_ROLL_INIT, D, 0, TapVariant{1, 0, N <= 256 ? 4 : N <= 1024 ? 16 : 64}, 0);
         return TAP_OK;
     }
     if (D == 2) hipLaunchKernelGGL(k_rolling_init<2>, dim3(grid), dim3(TAP_BLOCK), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(k_rolling_init<3>, dim3(grid), dim3(TAP_BLOCK), 0, (hipStream_t)stream, a);
     TAP_LAUNCH_CHECK(ctx, "k_rolling_init");
+    tap_variant_hit(ctx, TAP_HIT_ROLL_INIT, D, 0, TapVariant{0, 0, 0}, 0);
     return TAP_OK;
 }
 
@@ -1403,6 +1405,7 @@ static int rolling_window_impl(tap_ctx *ctx, int B, int D, int N, int child, con
         if (D == 2) TAP_ROLL_WIDE(2); else TAP_ROLL_WIDE(3);
 #undef TAP_ROLL_WIDE
         TAP_LAUNCH_CHECK(ctx, "k_rolling_window(wide)");
+        tap_variant_hit(ctx, TAP_HIT_ROLL_WINDOW, D, 0, nw == 2 ? TapVariant{0, ROLL_CH_WIDE, 0} : TapVariant{1, nw, 0}, a.wt);
         return TAP_OK;
     }
     if (N > 64) {                                                     // one thread per instance
@@ -1415,6 +1418,7 @@ static int rolling_window_impl(tap_ctx *ctx, int B, int D, int N, int child, con
         if (D == 2) TAP_ROLL_BIG(2); else TAP_ROLL_BIG(3);
 #undef TAP_ROLL_BIG
         TAP_LAUNCH_CHECK(ctx, "k_rolling_window_big");
+        tap_variant_hit(ctx, TAP_HIT_ROLL_WINDOW, D, 0, TapVariant{2, 0, N <= 256 ? 4 : N <= 1024 ? 16 : 64}, a.wt);
         return TAP_OK;
     }
     const bool fast = roll_fast_ok(D, child);
@@ -1426,6 +1430,7 @@ static int rolling_window_impl(tap_ctx *ctx, int B, int D, int N, int child, con
         else hipLaunchKernelGGL((k_rolling_window<3, 0>), dim3(grid), dim3(TAP_BLOCK), 0, (hipStream_t)stream, ROLL_HOT_ARGS(a), a);
     }
     TAP_LAUNCH_CHECK(ctx, "k_rolling_window");
+    tap_variant_hit(ctx, TAP_HIT_ROLL_WINDOW, D, 0, TapVariant{0, fast ? 10 : 0, 0}, a.wt);
     return TAP_OK;
 }
 
@@ -1447,6 +1452,8 @@ template <int D, int G> static int launch_rolling_step(tap_ctx *ctx, const RollS
         else hipLaunchKernelGGL((k_rolling_step_soft<D, G, 0>), dim3(grid), dim3(THREADS), 0, st, ROLL_HOT_ARGS(a.r), a);
     }
     TAP_LAUNCH_CHECK(ctx, "k_rolling_step");
+    const int ch = a.r.N > 64 ? ROLL_CH_WIDE : roll_fast_ok(D, a.r.child) ? 10 : 0;
+    tap_variant_hit(ctx, TAP_HIT_ROLL_STEP, D, G, TapVariant{!hard && a.r.N <= 64 ? 1 : 0, ch, 0}, a.r.wt);
     return TAP_OK;
 }
 

@@ -16,10 +16,19 @@
 constexpr int TAP_CHK_SLOTS = 64;
 constexpr int TAP_BLOCK = 256; // threads per workgroup (4 wave64)
 
-// launches of the stream-wave kernels per instantiation (tap_launch_variant; tapenv.h: tap_variant_hits): the key is
-// (kind, D, G, nc, mode, extra, wt), D / G = 0 where the launcher's table ignores them
-// (314 instantiations, each with wt = 0 and 1: at most 628 keys)
+// launches per instantiation (tapenv.h: tap_variant_hits): the key is (kind, D, G, nc, mode, extra, wt).  The stream-wave
+// kernels (tap_launch_variant) count under their TapStreamKind, D / G = 0 where the launcher's table ignores them; the
+// whole-episode and rolling kernels under TapHitKind below.  314 stream-wave instantiations with wt = 0 and 1 (628 keys)
+// + 25 episode (wt 0) + 40 fused rolling steps and 16 window kernels with both wt + 8 init kernels: at most 773 keys
 constexpr int TAP_VARIANT_HIT_SLOTS = 1024;
+enum TapHitKind {               // (tapenv.h documents the fields of each)
+    TAP_HIT_EPISODE = 16,       // k_episode<D, G, SOFT>                      (episode.hip: launch_episode)
+    TAP_HIT_EPISODE_MACS2,      // k_episode_macs2<G, WIDE>                   (episode.hip: launch_episode_macs2)
+    TAP_HIT_EPISODE_MACS3,      // k_episode_macs3<G, WL>                     (episode.hip: launch_episode_macs3)
+    TAP_HIT_ROLL_STEP,          // k_rolling_step<D, G, CH> / _soft           (rolling.hip: launch_rolling_step)
+    TAP_HIT_ROLL_WINDOW,        // k_rolling_window / _wide / _big            (rolling.hip: rolling_window_impl)
+    TAP_HIT_ROLL_INIT,          // k_rolling_init / _big                      (rolling.hip: tap_rolling_init)
+};
 struct TapVariantHit {
     int32_t key[7];
     int32_t count;
@@ -43,6 +52,7 @@ inline void tap_variant_hit(tap_ctx *ctx, int kind, int D, int G, const TapVaria
 {
     if (!ctx) return;
     const int32_t key[7] = {kind, D, G, v.nc, v.mode, v.extra, wt ? 1 : 0};
+    static_assert((int)TAP_SV_KINDS <= (int)TAP_HIT_EPISODE, "launch-record kinds overlap");
     std::lock_guard<std::mutex> g(ctx->hit_lock);
     for (int i = 0; i < ctx->nhits; ++i)
         if (memcmp(ctx->hits[i].key, key, sizeof(key)) == 0) { ctx->hits[i].count += 1; return; }
