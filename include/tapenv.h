@@ -54,8 +54,16 @@ enum {
     TAP_F_USE_P = 1 << 1,    /* 'P' in reward_type             tools.py:2135 */
     TAP_F_USE_S = 1 << 2,    /* 'S' in reward_type             tools.py:2138 */
     TAP_F_MCS_ZERO = 1 << 3, /* reward_type.startswith('mcs')  tools.py:2709 */
-    TAP_F_MCS_TIE = 1 << 4   /* 'mcs' in reward_type           tools.py:2718 */
+    TAP_F_MCS_TIE = 1 << 4,  /* 'mcs' in reward_type           tools.py:2718 */
+    /* place-at semantics (tap_env_desc_set_place_at; never set by tap_env_desc_init) */
+    TAP_F_AT_CONTAINER = 1 << 5,
+    TAP_F_AT_NET = 1 << 6
 };
+
+/* semantics of tap_env_step_at*: the two seams of the learned local pack-net (reward types C+P+S-SL-soft /
+ * C+P+S-RL-soft) that drop a block at a caller-chosen column */
+enum { TAP_AT_CONTAINER = 1 /* tools.Container.add_new_block_at, tools.py:3746-3822 (DRL_L, model.py:1211) */,
+       TAP_AT_NET = 2 /* tools.calc_one_position_net, tools.py:3371-3461 (calc_positions_net, pack.reward / render) */ };
 
 /* Container.calc_ratio formula, tools.py:3907-3966 */
 enum {
@@ -96,7 +104,7 @@ const char *tap_last_error(const tap_ctx *ctx);
  * hipGraph counts once, at capture.  tap_variant_hits writes up to `cap` rows of 8 ints (the key, then the count) and
  * returns the number of rows the record holds (TAP_E_INVALID if a key found no slot since the last reset);
  * tap_variant_hits_reset empties it. */
-/* The whole-episode and rolling kernels count on the same record, under kinds 16 .. 21 (tap_common.h: TapHitKind), after
+/* The whole-episode and rolling kernels count on the same record, under kinds 16 .. 22 (tap_common.h: TapHitKind), after
  * the stream-wave kinds 0 .. 6.  Their keys, fields (kind, D, G, nc, mode, extra, wt):
  *   16 k_episode<D, G, SOFT>                      (16, D, G, SOFT, 0, 0, 0)
  *   17 k_episode_macs2<G, WIDE>                   (17, 2, G, WIDE, 0, 0, 0)
@@ -107,6 +115,7 @@ const char *tap_last_error(const tap_ctx *ctx);
  *      k_rolling_window_big<D, MW>                (20, D, 0, 2, 0, MW, wt)       MW mask words 4, 16, 64
  *   21 k_rolling_init<D>                          (21, D, 0, 0, 0, 0, 0)
  *      k_rolling_init_big<D, MW>                  (21, D, 0, 1, 0, MW, 0)
+ *   22 k_place_at<G, NET>                         (22, 2, G, SEM, GATHER, 0, 0)  SEM a TAP_AT_*, GATHER 1 = _gather
  * wt is the launch's RollArgs::wt (the window's fp32 stores; the init kernels store none), 0 for the episode kernels. */
 int tap_variant_hits(tap_ctx *ctx, int32_t *out, int cap);
 int tap_variant_hits_reset(tap_ctx *ctx);
@@ -120,6 +129,12 @@ int tap_variant_hits_reset(tap_ctx *ctx);
 int tap_env_desc_init(tap_env_desc *d, int B, int D, const int32_t *container_size, int blocks_num,
                       const char *reward_type, const char *heightmap_type,
                       const char *packing_strategy);
+
+/* Place-at semantics for `d` (TAP_AT_CONTAINER | TAP_AT_NET, 0 = none): sets the TAP_F_AT_* bits of d->flags.  A
+ * flagged descriptor is stepped by tap_env_step_at* only (tap_env_step* return TAP_E_INVALID for it) and its state
+ * blob carries one more section, B x W int32 block cells per column, at its end.  2D only (TAP_E_INVALID for D = 3).
+ * Host only. */
+int tap_env_desc_set_place_at(tap_env_desc *d, int semantics);
 
 /* bytes of device memory the caller must provide for the state blob (256-byte aligned) */
 size_t tap_env_state_bytes(const tap_env_desc *d);
@@ -155,6 +170,25 @@ int tap_env_step(tap_ctx *ctx, const tap_env_desc *d, void *state, const void *b
 int tap_env_step_gather(tap_ctx *ctx, const tap_env_desc *d, void *state, const float *static_,
                         int static_rows, int nR, const int64_t *ptr, const uint8_t *active,
                         float *feature_out, void *stream);
+
+/* The pack-net placement (tools.Container.add_new_block_at, tools.py:3746-3822 / tools.calc_one_position_net,
+ * tools.py:3371-3461, by the descriptor's TAP_F_AT_* semantics) for all B envs: block b goes to column pos_x[b]
+ * (B,) int64, clamped to W - w like the reference's `while x + w > W: x -= 1`; z = max(heightmap[x:x+w]).
+ * TAP_AT_CONTAINER: stable always (the reference tests the support row after filling it), empty_size += the filled
+ * cells under the block counted again at every step (sum_c z - block cells of column c); TAP_AT_NET: stability of
+ * the support row before the fill (tools.is_stable_2d), empty_size = sum(heightmap) - valid_size.  A column < 0 or a
+ * block wider than W: error bit 4, not placed; z + h > H: error bit 1 (the reference clips silently), placed.
+ * blocks / blocks_dtype / static_ / ptr / active / feature_out as tap_env_step / tap_env_step_gather.
+ *   pnet_out   (B, 1, W) f32 or NULL: the pack-net's input for the NEXT step, from the state just written, in form
+ *              pnet_form: TAP_FEAT_FULL (the raw height-map, tools.py:3407), TAP_FEAT_ZERO (minus its minimum) or
+ *              TAP_FEAT_DIFF (hm[c+1] - hm[c] with a trailing 0, length W: DRL_L's transform, model.py:1188-1192)
+ * TAP_E_INVALID for an unflagged descriptor or D = 3; TAP_E_UNSUPPORTED for W > 64.  One launch (lane per column). */
+int tap_env_step_at(tap_ctx *ctx, const tap_env_desc *d, void *state, const void *blocks, int blocks_dtype,
+                    const uint8_t *active, float *feature_out, const int64_t *pos_x, float *pnet_out, int pnet_form,
+                    void *stream);
+int tap_env_step_at_gather(tap_ctx *ctx, const tap_env_desc *d, void *state, const float *static_, int static_rows,
+                           int nR, const int64_t *ptr, const uint8_t *active, float *feature_out, const int64_t *pos_x,
+                           float *pnet_out, int pnet_form, void *stream);
 
 /* tools.Container.get_heightmap (tools.py:3824-3856): the feature of the current state */
 int tap_env_feature(tap_ctx *ctx, const tap_env_desc *d, const void *state, float *feature_out,

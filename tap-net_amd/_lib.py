@@ -20,6 +20,10 @@ TAP_DT_F32, TAP_DT_I32 = 0, 1
 TAP_R_C, TAP_R_CxS, TAP_R_CP, TAP_R_CPxS, TAP_R_CPS, TAP_R_2CPS, TAP_R_CxPxS, TAP_R_CP_HALF = range(8)
 TAP_T_FRESH, TAP_T_RATIO = 1, 2
 TAP_SB_INITIAL_MASK, TAP_SB_CONTINUE = 1, 2
+TAP_FEAT_FULL, TAP_FEAT_ZERO, TAP_FEAT_DIFF = 0, 1, 2
+TAP_AT_CONTAINER, TAP_AT_NET = 1, 2
+TAP_F_AT_CONTAINER, TAP_F_AT_NET = 1 << 5, 1 << 6
+TAP_HIT_PLACE_AT = 22
 
 
 _vp_t = C.c_void_p
@@ -69,11 +73,14 @@ _PROTOS = {
     "tap_variant_hits_reset": (_i, [_vp]),
     "tap_env_desc_init": (_i, [C.POINTER(EnvDesc), _i, _i, C.POINTER(C.c_int32), _i,
                                C.c_char_p, C.c_char_p, C.c_char_p]),
+    "tap_env_desc_set_place_at": (_i, [C.POINTER(EnvDesc), _i]),
     "tap_env_state_bytes": (_sz, [C.POINTER(EnvDesc)]),
     "tap_env_feature_len": (_i, [C.POINTER(EnvDesc)]),
     "tap_env_reset": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp]),
     "tap_env_step": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _i, _vp, _vp, _vp]),
     "tap_env_step_gather": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "tap_env_step_at": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "tap_env_step_at_gather": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "tap_env_feature": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp]),
     "tap_env_ratio": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp, _vp, _vp]),
     "tap_env_export": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -238,6 +245,20 @@ def ptr(t):
     if not t.is_cuda:
         raise TapError(TAP_E_INVALID, "tensor on %s passed to a device entry point (move it to the GPU first)" % (t.device,))
     return _vp(t.data_ptr())
+
+
+PLACE_AT = {None: 0, 'container': TAP_AT_CONTAINER, 'net': TAP_AT_NET}
+PNET_FORMS = {'full': TAP_FEAT_FULL, 'zero': TAP_FEAT_ZERO, 'diff': TAP_FEAT_DIFF}
+
+
+def set_place_at(desc, place_at):
+    """tap_env_desc_set_place_at: place_at None | 'container' | 'net' (tapenv.h)."""
+    if place_at not in PLACE_AT:
+        raise ValueError("place_at must be None, 'container' or 'net', not %r" % (place_at,))
+    st = lib().tap_env_desc_set_place_at(C.byref(desc), PLACE_AT[place_at])
+    if st != TAP_OK:
+        raise TapError(st, "place-at %r on a %dD container: the pack-net placement is 2D only" % (place_at, desc.D))
+    return desc
 
 
 def make_desc(batch_size, container_size, blocks_num, reward_type, heightmap_type, packing_strategy):

@@ -304,6 +304,7 @@ extern "C" int tap_env_step(tap_ctx *ctx, const tap_env_desc *d, void *state, co
                             int blocks_dtype, const uint8_t *active, float *feature_out,
                             void *stream)
 {
+    if (d && tap_place_at_semantics(d)) return tap_fail(ctx, TAP_E_INVALID, "a place-at descriptor is stepped by tap_env_step_at");
     if (d && d->B == 0) return tap_desc_validate(ctx, d); // an empty batch has no buffers to check
     if (!blocks) return tap_fail(ctx, TAP_E_INVALID, "null blocks");
     if (blocks_dtype != TAP_DT_F32 && blocks_dtype != TAP_DT_I32)
@@ -318,6 +319,7 @@ extern "C" int tap_env_step_gather(tap_ctx *ctx, const tap_env_desc *d, void *st
                                    const int64_t *ptr, const uint8_t *active, float *feature_out,
                                    void *stream)
 {
+    if (d && tap_place_at_semantics(d)) return tap_fail(ctx, TAP_E_INVALID, "a place-at descriptor is stepped by tap_env_step_at_gather");
     if (d && d->B == 0) return tap_desc_validate(ctx, d); // an empty batch has no buffers to check
     if (!static_ || !ptr || !d || static_rows < 1 + d->D || nR < 1)
         return tap_fail(ctx, TAP_E_INVALID, "bad gather arguments");

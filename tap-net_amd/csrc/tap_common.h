@@ -28,6 +28,7 @@ enum TapHitKind {               // (tapenv.h documents the fields of each)
     TAP_HIT_ROLL_STEP,          // k_rolling_step<D, G, CH> / _soft           (rolling.hip: launch_rolling_step)
     TAP_HIT_ROLL_WINDOW,        // k_rolling_window / _wide / _big            (rolling.hip: rolling_window_impl)
     TAP_HIT_ROLL_INIT,          // k_rolling_init / _big                      (rolling.hip: tap_rolling_init)
+    TAP_HIT_PLACE_AT,           // k_place_at<G, NET>                         (place_at.hip: launch_at)
 };
 struct TapVariantHit {
     int32_t key[7];
@@ -201,6 +202,7 @@ inline size_t tap_env_layout(const tap_env_desc *d, void *base, EnvView *v)
     size_t o_vox = lb ? take(B * cells * (size_t)d->H * 2) : 0;
     size_t o_lfs = lb ? take(B * (size_t)d->H * d->L * (size_t)(d->W + 2)) : 0;
     size_t o_lfn = lb ? take(B * (size_t)d->H * d->L) : 0;
+    if (d->flags & (TAP_F_AT_CONTAINER | TAP_F_AT_NET)) (void)take(B * (size_t)d->W * 4);   // place_at.hip: last section
     if (v) {
         v->scratch = scr ? reinterpret_cast<int32_t *>(p + o_scr) : nullptr;
         v->vox = lb ? reinterpret_cast<int16_t *>(p + o_vox) : nullptr;
@@ -215,6 +217,20 @@ inline size_t tap_env_layout(const tap_env_desc *d, void *base, EnvView *v)
         v->occ = (d->strategy == TAP_MACS && d->D == 3) ? reinterpret_cast<unsigned long long *>(p + o_occ) : nullptr;
     }
     return off;
+}
+
+// place-at semantics of a descriptor (place_at.hip): 0 none, TAP_AT_CONTAINER | TAP_AT_NET, -1 both bits
+inline int tap_place_at_semantics(const tap_env_desc *d)
+{
+    const int f = d->flags & (TAP_F_AT_CONTAINER | TAP_F_AT_NET);
+    return f == 0 ? 0 : f == TAP_F_AT_CONTAINER ? TAP_AT_CONTAINER : f == TAP_F_AT_NET ? TAP_AT_NET : -1;
+}
+// byte offset of the per-column section of a place-at blob: the blob's last section, after the unflagged layout
+inline size_t tap_env_col_offset(const tap_env_desc *d)
+{
+    tap_env_desc u = *d;
+    u.flags &= ~(TAP_F_AT_CONTAINER | TAP_F_AT_NET);
+    return tap_env_layout(&u, nullptr, nullptr);
 }
 
 // arguments of one lock-step placement launch (env.hip, macs.hip)

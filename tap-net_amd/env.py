@@ -23,7 +23,7 @@ class BatchedContainer(object):
 
     def __init__(self, batch_size, container_size, blocks_num, reward_type, heightmap_type='full',
                  initial_container_size=None, max_height=None, packing_strategy='LB_GREEDY',
-                 device='cuda'):
+                 device='cuda', place_at=None):
         self.device = _lib.resolve_device(device)
         self.batch_size = int(batch_size)
         self.container_size = [int(v) for v in container_size]
@@ -35,6 +35,11 @@ class BatchedContainer(object):
         self.max_height = 2 * self.container_size[0] if max_height is None else max_height  # tools.py:3624-3627
         self.desc = _lib.make_desc(self.batch_size, self.container_size, blocks_num, reward_type,
                                    heightmap_type, packing_strategy)
+        # the pack-net placement (tapenv.h: tap_env_step_at): blocks at caller-chosen columns, stepped by
+        # add_new_blocks_at* only; 'container' = tools.Container.add_new_block_at, 'net' = tools.calc_one_position_net
+        self.place_at = place_at
+        if place_at is not None:
+            _lib.set_place_at(self.desc, place_at)
         # tools.py:3617-3620: the reward string may override the strategy
         if reward_type in ('C+P+S-mul-soft', 'C+P+S-mul-hard'):
             packing_strategy = 'MUL'
@@ -127,6 +132,73 @@ class BatchedContainer(object):
             raise ValueError("out must be a contiguous float32 tensor of shape %s" % (self._feature_shape(),))
         self._call(_lib.lib().tap_env_step_gather, _lib.ptr(self._state), _lib.ptr(static),
                    static.shape[1], static.shape[2], _lib.ptr(ptr), _lib.ptr(act), _lib.ptr(feat))
+        return feat
+
+    def _pnet_args(self, pnet_out, pnet_form):
+        if pnet_out is None:
+            return None, 0
+        if self.place_at is None:
+            raise ValueError("pnet_out is written by the place-at step only")
+        d = self.desc
+        if tuple(pnet_out.shape) != (self.batch_size, 1, d.W) or pnet_out.dtype != torch.float32 \
+                or not pnet_out.is_contiguous() or pnet_out.device != self.device:
+            raise ValueError("pnet_out must be a contiguous float32 tensor of shape (%d, 1, %d) on %s"
+                             % (self.batch_size, d.W, self.device))
+        if pnet_form is None:                    # calc_positions_net feeds the raw map (tools.py:3407), DRL_L its own form
+            pnet_form = 'full' if self.place_at == 'net' else self.heightmap_type
+        if pnet_form not in _lib.PNET_FORMS:
+            raise ValueError("pnet_form must be 'full', 'zero' or 'diff', not %r" % (pnet_form,))
+        return pnet_out, _lib.PNET_FORMS[pnet_form]
+
+    def _as_pos_x(self, pos_x):
+        x = torch.as_tensor(pos_x, device=self.device)
+        if x.numel() != self.batch_size:
+            raise ValueError("pos_x must have %d entries, got %s" % (self.batch_size, tuple(x.shape)))
+        return x.reshape(-1).to(torch.int64).contiguous()
+
+    def add_new_blocks_at(self, blocks, pos_x, active=None, want_feature=True, pnet_out=None, pnet_form=None):
+        """add_new_block_at for all envs (tools.py:3746-3822; with place_at='net' calc_one_position_net's placement,
+        tools.py:3371-3461): ``blocks`` (B, 2) float32/int32, ``pos_x`` (B,) column indices.  Returns the decoder
+        feature as add_new_blocks does.  ``pnet_out`` (B, 1, W) float32, optional: filled with the pack-net's input
+        for the next step, in form ``pnet_form`` ('full' / 'zero' / 'diff' in DRL_L's length-W form, model.py:1173-1196;
+        default 'full' for place_at='net', heightmap_type for 'container').  One launch."""
+        blocks = torch.as_tensor(blocks, device=self.device)
+        if blocks.dim() == 3 and blocks.shape[-1] == 1:
+            blocks = blocks.squeeze(-1)
+        if tuple(blocks.shape) != (self.batch_size, self.block_dim):
+            raise ValueError("blocks must be (%d, %d), got %s" % (self.batch_size, self.block_dim, tuple(blocks.shape)))
+        if blocks.dtype == torch.int32:
+            dt = _lib.TAP_DT_I32
+        else:
+            blocks = blocks.to(torch.float32)
+            dt = _lib.TAP_DT_F32
+        blocks = blocks.contiguous()
+        x = self._as_pos_x(pos_x)
+        po, pf = self._pnet_args(pnet_out, pnet_form)
+        act = self._as_active(active)
+        feat = self._new_feature() if want_feature else None
+        self._call(_lib.lib().tap_env_step_at, _lib.ptr(self._state), _lib.ptr(blocks), dt, _lib.ptr(act),
+                   _lib.ptr(feat), _lib.ptr(x), _lib.ptr(po), pf)
+        return feat
+
+    def add_new_blocks_at_gather(self, static, ptr, pos_x, active=None, want_feature=True, out=None, pnet_out=None,
+                                 pnet_form=None):
+        """Same, with the gather of model.py:1164-1167 fused: block = static[b, 1:3, ptr[b]]."""
+        if static.dtype != torch.float32 or not static.is_contiguous() or static.device != self.device:
+            static = static.to(device=self.device, dtype=torch.float32).contiguous()
+        ptr = ptr.to(device=self.device, dtype=torch.int64).contiguous()
+        if static.dim() != 3 or static.shape[0] != self.batch_size or static.shape[1] < 1 + self.block_dim:
+            raise ValueError("static must be (%d, >= %d, nR), got %s" % (self.batch_size, 1 + self.block_dim, tuple(static.shape)))
+        if tuple(ptr.shape) != (self.batch_size,):
+            raise ValueError("ptr must be (%d,), got %s" % (self.batch_size, tuple(ptr.shape)))
+        x = self._as_pos_x(pos_x)
+        po, pf = self._pnet_args(pnet_out, pnet_form)
+        act = self._as_active(active)
+        feat = out if out is not None else (self._new_feature() if want_feature else None)
+        if feat is not None and (tuple(feat.shape) != self._feature_shape() or feat.dtype != torch.float32 or not feat.is_contiguous()):
+            raise ValueError("out must be a contiguous float32 tensor of shape %s" % (self._feature_shape(),))
+        self._call(_lib.lib().tap_env_step_at_gather, _lib.ptr(self._state), _lib.ptr(static), static.shape[1],
+                   static.shape[2], _lib.ptr(ptr), _lib.ptr(act), _lib.ptr(feat), _lib.ptr(x), _lib.ptr(po), pf)
         return feat
 
     def get_heightmaps(self):
@@ -287,6 +359,9 @@ class _Pool(object):
         self.members = 0
         self.refs = []                  # weak references to the member Containers (a collected one leaves the pool)
         self.env = None                 # built when the first member is used: the pool is sealed then
+        self.place_at = None            # 'container' once a member called add_new_block_at (Container.add_new_block_at)
+        self.stepped = False            # an add_new_block round has run: the pool can no longer switch to place-at
+        self.hm_cache = None            # place-at pools: every member's height-map, read once per round (DRL_L, model.py:1176-1178)
 
     def join(self, owner):
         import weakref
@@ -303,9 +378,10 @@ class _Pool(object):
             _open_pool = None
         (cs, n, reward, hm_type, init_cs, max_h, strategy, device) = self.args
         B = self.members
-        self.env = BatchedContainer(B, cs, n, reward, hm_type, init_cs, max_h, strategy, device)
+        self.env = BatchedContainer(B, cs, n, reward, hm_type, init_cs, max_h, strategy, device, place_at=self.place_at)
         D = self.env.block_dim
         self.blocks = np.zeros((B, D), np.float32)
+        self.pos = [0] * B                                       # place-at columns of this round (ints or 0-d tensors)
         self.active = np.zeros(B, np.uint8)
         self.called = np.zeros(B, bool)
         self.ever = np.zeros(B, bool)                            # called in any round so far
@@ -321,8 +397,34 @@ class _Pool(object):
         elif hm_type != 'diff':
             self._fshape = self._fshape[1:]                      # (W, L)
 
-    def request(self, i, block):
-        """member i's call of this round: block = None for get_heightmap (report only)"""
+    def use_place_at(self):
+        """the first add_new_block_at of a member: from now on the pool steps with tap_env_step_at (CONTAINER semantics).
+        A pool whose env was built unflagged (a height-map read before the first step) is rebuilt; one that has run
+        add_new_block rounds cannot switch."""
+        if self.place_at == 'container':
+            return
+        if self.env is not None:
+            self.flush()
+        if self.stepped:
+            raise NotImplementedError("add_new_block_at on a lock-step pool whose Containers were stepped with "
+                                      "add_new_block: one Container uses one of the two placements, not both")
+        self.place_at = 'container'
+        if self.env is not None:
+            (cs, n, reward, hm_type, init_cs, max_h, strategy, device) = self.args
+            self.env = BatchedContainer(self.members, cs, n, reward, hm_type, init_cs, max_h, strategy, device,
+                                        place_at=self.place_at)
+            self.hm_cache = None
+
+    def heightmap(self, i):
+        """member i's height-map; a place-at pool reads every member's once per round"""
+        self.seal()
+        self.flush()
+        if self.hm_cache is None:
+            self.hm_cache = self.env.heightmap.cpu().numpy().astype(np.int64)
+        return self.hm_cache[i].copy()
+
+    def request(self, i, block, pos_x=None):
+        """member i's call of this round: block = None for get_heightmap (report only); pos_x: add_new_block_at's column"""
         self.seal()
         if self.called[i]:
             # a second call within a round: the caller believes the round is over.  Members that were never called
@@ -344,16 +446,18 @@ class _Pool(object):
                     "members have been dropped and the next rounds are complete; THIS call was recorded as the first of "
                     "the next round -- do not re-issue it, its result row is the exception's `.row` (filled when that "
                     "round completes)." % (int(phantom.sum()), self.members))
-                err.row = self._record(i, block)
+                err.row = self._record(i, block, pos_x)
                 raise err
-        return self._record(i, block)
+        return self._record(i, block, pos_x)
 
-    def _record(self, i, block):
+    def _record(self, i, block, pos_x=None):
         if self.out is None:
             self.out = np.full((self.members,) + self._fshape, _UNFILLED, np.int64)
         if block is not None:
             self.blocks[i] = block
             self.active[i] = 1
+            if self.place_at is not None:
+                self.pos[i] = pos_x
         self.called[i] = True
         self.ever[i] = True
         self.live[i] = True
@@ -376,9 +480,25 @@ class _Pool(object):
         self.n_called = 0
         self.out = None
         self.ratios = None
-        feat = env.add_new_blocks(blocks, active=active)
+        self.hm_cache = None
+        if self.place_at is not None:
+            pos, self.pos = self.pos, [0] * self.members
+            feat = env.add_new_blocks_at(blocks, self._columns(pos), active=active)
+        else:
+            self.stepped = self.stepped or bool(active.any())
+            feat = env.add_new_blocks(blocks, active=active)
         out[...] = feat.detach().cpu().numpy().reshape(out.shape)
         env.check()
+
+    def _columns(self, pos):
+        """the round's columns as one (B,) int64 device tensor: DRL_L hands each member a 0-d element of its argmax
+        tensor (model.py:1200, 1211), stacked here in one op -- no host read per member"""
+        dev = self.env.device
+        if all(isinstance(v, torch.Tensor) for v in pos):
+            return torch.stack([v.reshape(()).to(device=dev, dtype=torch.int64) for v in pos])
+        if not any(isinstance(v, torch.Tensor) for v in pos):
+            return torch.as_tensor(np.asarray(pos, dtype=np.int64), device=dev)
+        return torch.stack([torch.as_tensor(v, device=dev).reshape(()).to(torch.int64) for v in pos])
 
     def ratio(self, i):
         self.seal()
@@ -399,6 +519,9 @@ class Container(object):
                  device='cuda'):
         global _open_pool
         self._pool = self._b = None
+        self._mode = None                   # 'block' after add_new_block, 'at' after add_new_block_at (one or the other)
+        self._args = (container_size, blocks_num, reward_type, heightmap_type, initial_container_size, max_height,
+                      packing_strategy, device)
         if _lockstep:
             key = (tuple(int(v) for v in container_size), int(blocks_num), reward_type, heightmap_type,
                    None if initial_container_size is None else tuple(initial_container_size), max_height, packing_strategy,
@@ -448,15 +571,49 @@ class Container(object):
         return a.reshape(a.shape[1:]) if self.heightmap_type == 'diff' else a.reshape(a.shape[2:])
 
     def add_new_block(self, block, is_rotate=False):
+        if self._mode == 'at' or (self._pool is not None and self._pool.place_at is not None):
+            raise NotImplementedError("add_new_block on a Container stepped with add_new_block_at: this package runs "
+                                      "one of the two placements per Container (and per lock-step pool), not both")
         n = len(self.blocks)
         if n >= self.blocks_num:
             raise IndexError("list assignment index out of range")   # tools.py:3677
+        self._mode = 'block'
         self.rotate_state[n] = is_rotate
         self.blocks.append(np.asarray(block))
         if self._pool is not None:
             return self._pool.request(self._i, np.asarray(block, dtype=np.float32).reshape(-1))
         blk = torch.as_tensor(np.asarray(block, dtype=np.float32).reshape(1, -1))
         feat = self._b.add_new_blocks(blk)
+        self._b.check()
+        return self._shape(feat)
+
+    def add_new_block_at(self, block, pos_x, is_rotate=False):
+        """tools.Container.add_new_block_at (tools.py:3746-3822), what DRL_L's decoding loop calls (model.py:1211): the
+        2D block at column ``pos_x`` (clamped to W - w), stability and empty_size by the reference's rules (tapenv.h:
+        TAP_AT_CONTAINER).  Returns the heightmap_type feature like add_new_block.  The first call switches a fresh
+        Container to the place-at step; mixing it with add_new_block raises NotImplementedError.  Pooled
+        (lockstep_scope): one launch per round for the whole pool, ``pos_x`` may be a 0-d device tensor (no host read)."""
+        if self._mode == 'block':
+            raise NotImplementedError("add_new_block_at on a Container stepped with add_new_block: this package runs "
+                                      "one of the two placements per Container, not both")
+        if self.block_dim != 2:
+            raise NotImplementedError("add_new_block_at is 2D only (tools.py:3762 unpacks two block sides)")
+        n = len(self.blocks)
+        if n >= self.blocks_num:
+            raise IndexError("list assignment index out of range")   # tools.py:3758
+        if self._mode is None:
+            if self._pool is not None:
+                self._pool.use_place_at()
+            else:
+                (cs, bn, rt, ht, ics, mh, ps, dev) = self._args
+                self._b = BatchedContainer(1, cs, bn, rt, ht, ics, mh, ps, dev, place_at='container')
+            self._mode = 'at'
+        self.rotate_state[n] = is_rotate
+        self.blocks.append(np.asarray(block))
+        blk = np.asarray(block, dtype=np.float32).reshape(-1)
+        if self._pool is not None:
+            return self._pool.request(self._i, blk, pos_x)
+        feat = self._b.add_new_blocks_at(torch.as_tensor(blk.reshape(1, -1)), torch.as_tensor(pos_x).reshape(1))
         self._b.check()
         return self._shape(feat)
 
@@ -493,12 +650,16 @@ class Container(object):
             raise NotImplementedError("clear_container on one member of a lock-step pool: build new Containers per "
                                       "episode (as model.py:294 does), or switch pooling off for this use")
         self._env.reset()
+        if self._pool is not None:
+            self._pool.hm_cache = None
         self.blocks = []
         self.rotate_state = [False] * self.blocks_num
         self.bounding_box = np.zeros(self.block_dim)
 
     @property
     def heightmap(self):
+        if self._pool is not None and self._pool.place_at is not None:
+            return self._pool.heightmap(self._i)
         return self._env.heightmap[self._i].cpu().numpy().astype(np.int64)
 
     @property

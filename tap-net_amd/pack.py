@@ -699,9 +699,18 @@ def _reward_mul(static, tour_indices, reward_type, input_type, allow_rot, contai
 
 
 def reward(static, tour_indices, reward_type, input_type, allow_rot, container_width, container_height,
-           packing_strategy='LB_GREEDY'):
+           packing_strategy='LB_GREEDY', pack_net=None):
     """pack.reward (pack.py:378-473): pack every env's blocks in tour order from an empty
-    container and return ``-scores`` (un-normalised C+P+S, tools.py:2442-2449), one launch."""
+    container and return ``-scores`` (un-normalised C+P+S, tools.py:2442-2449), one launch.
+    ``pack_net`` (a tools.DQN): the SL / RL reward types are then scored as the reference scores them,
+    tools.calc_positions_net's (C+P+S)/3 (pack.py:431-433; episode_scores_net); without it they keep the LB_GREEDY
+    scoring above."""
+    if pack_net is not None and reward_type in _L_PNET_TYPES and packing_strategy not in ('MACS', 'MUL'):
+        if input_type in ('mul', 'mul-with'):
+            raise NotImplementedError("the pack-net reward of the two-container input types is not implemented")
+        ratio, _ = episode_scores_net(static, tour_indices, reward_type, [container_width, container_height], pack_net,
+                                      input_type, allow_rot)
+        return -ratio.to(torch.float32)
     if packing_strategy in ('MACS', 'MUL'):
         # pack.py:431 names tools.calc_positions_mus, which does not exist in the reference
         raise AttributeError("module 'tools' has no attribute 'calc_positions_mus'")
@@ -753,6 +762,7 @@ _MCS_RATIO_TYPES = ('comp', 'soft', 'hard', 'pyrm', 'pyrm-soft', 'pyrm-hard', 'm
                     'C+P-mul-soft', 'C+P-mul-hard', 'C+P-mcs-soft', 'C+P-mcs-hard',
                     'C+P+S-mul-soft', 'C+P+S-mul-hard', 'C+P+S-mcs-soft', 'C+P+S-mcs-hard')
 _NET_REWARD_TYPES = ('C+P+S-SL-soft', 'C+P+S-RL-soft', 'C+P+S-G-soft', 'C+P+S-LG-soft')             # pack.py:728-730
+_L_PNET_TYPES = ('C+P+S-SL-soft', 'C+P+S-RL-soft')                  # the learned local pack-net (tools.py:3544-3553)
 RENDER_FILES = ('ratio', 'valid_size', 'box_size', 'empty_size', 'stable_num', 'packing_height', 'time', 'ids')
 
 
@@ -851,7 +861,60 @@ def episode_scores(static, tour_indices, reward_type, input_type, allow_rot, con
     return ratio, scores
 
 
-def render(static, tour_indices, save_path, dynamic, valid_time, **kwargs):
+def episode_scores_net(static, tour_indices, reward_type, container_size, net, input_type='bot', allow_rot=True,
+                       check=True, with_env=False):
+    """tools.calc_positions_net (tools.py:3506-3598) for every sample of a batch, SL / RL types: blocks in tour order
+    into an empty 2D container, each at the column ``net`` (a tools.DQN) picks from the raw height-map
+    (tools.calc_one_position_net, tools.py:3371-3461).  n place-at launches (tapenv.h: TAP_AT_NET) with the net
+    between them; each launch also writes the net's next input, so nothing else runs in between.
+    -> (ratio (B,) float64 = (C+P+S)/3, scores (B, 5) int64 = valid_size, box_size, empty_size, stable_num, max height)
+    [, the BatchedContainer with ``with_env``].  ``check``: raise like env.check() when a container overflowed."""
+    from .env import BatchedContainer
+    if reward_type not in _L_PNET_TYPES:
+        raise NotImplementedError("the %s pack-net (calc_positions_LG_net) is outside this package" % reward_type)
+    block_dim = _block_dim(static, input_type)
+    if block_dim != 2:
+        raise NotImplementedError("the pack-net placement is 2D only (tools.py:3395 unpacks two block sides)")
+    R = _rotate_types(block_dim, allow_rot)
+    st = _f32c(static)
+    B, rows, nR = st.shape
+    n = nR // R
+    dev = st.device
+    tour = tour_indices.to(device=dev, dtype=torch.int64)
+    if tour.shape[1] < n:
+        raise ValueError("tour shorter than blocks_num")
+    tour = tour[:, :n]
+    cs = [int(v) for v in container_size]
+    W = cs[0]
+    env = BatchedContainer(B, cs, n, reward_type, 'full', device=dev, place_at='net')
+    blocks = torch.gather(st[:, 1:3, :], 2, tour.unsqueeze(1).expand(-1, 2, -1)).to(torch.int32)  # astype(int), :3393
+    blocks_f = blocks.to(torch.float32).transpose(1, 2).contiguous()                                 # (B, n, 2), :3408
+    blocks = blocks.transpose(1, 2).contiguous()
+    pnet = torch.zeros(B, 1, W, dtype=torch.float32, device=dev)           # the empty container's height-map
+    with torch.no_grad():
+        for t in range(n):
+            x = net(pnet, blocks_f[:, t:t + 1, :]).max(1)[1]                                       # :3411
+            env.add_new_blocks_at(blocks[:, t], x, want_feature=False, pnet_out=pnet, pnet_form='full')
+    if check:
+        env.check()
+    cnt = env.counters.to(torch.int64)
+    max_h = env.heightmap.max(dim=1).values.to(torch.int64)
+    box = max_h * W                                                                                   # :3579-3580
+    valid, empty, nst = cnt[:, 0], cnt[:, 1], cnt[:, 2]
+    if n == 0:
+        ratio = torch.zeros(B, dtype=torch.float64, device=dev)
+    else:
+        C = valid.double() / box.double()
+        P = valid.double() / (empty + valid).double()
+        S = nst.double() / float(n)
+        ratio = ((C + P) + S) / 3                                                                     # :3588-3589
+    if not check:
+        ratio = torch.where(env.errors != 0, torch.full_like(ratio, float('nan')), ratio)
+    scores = torch.stack((valid, box, empty, nst, max_h), 1)                                          # :3597
+    return (ratio, scores, env) if with_env else (ratio, scores)
+
+
+def render(static, tour_indices, save_path, dynamic, valid_time, pack_net=None, **kwargs):
     """pack.render (pack.py:670-977), the ``render_fn`` of a test run (trainer.py:493, called by validate,
     trainer.py:132): re-pack every sample in tour order with the whole-episode function of the packing strategy
     (pack.py:726-734, 792) and write the eight metric files next to ``save_path`` (pack.py:967-977; the drawing
@@ -877,10 +940,17 @@ def render(static, tour_indices, save_path, dynamic, valid_time, **kwargs):
         container_size_ab = [container_width, container_height]
     strategy = kwargs['packing_strategy']
     reward_type = kwargs['reward_type']
-    if strategy not in ('MACS', 'MUL') and reward_type in _NET_REWARD_TYPES:
+    net_path = pack_net is not None and strategy not in ('MACS', 'MUL') and reward_type in _L_PNET_TYPES
+    if net_path and (mul or block_dim != 2):
+        raise NotImplementedError("the pack-net render is implemented for the 2D single-container input types")
+    if not net_path and strategy not in ('MACS', 'MUL') and reward_type in _NET_REWARD_TYPES:
         raise NotImplementedError("tools.calc_positions_net (the pack-net back-ends) is outside this package")
     args = (static, tour_indices, reward_type, input_type, kwargs['allow_rot'])
-    if mul:
+    if net_path:                                                                    # pack.py:728-730, 792
+        ratio, scores = episode_scores_net(static, tour_indices, reward_type, container_size, pack_net, input_type,
+                                           kwargs['allow_rot'])
+        scores = scores.double()
+    elif mul:
         ra, sa = episode_scores(*args, container_size_ab, strategy, target=0)
         rb, sb = episode_scores(*args, container_size_ab, strategy, target=1)
         ratio = (ra + rb) / 2                                                       # pack.py:771-776

@@ -115,7 +115,7 @@ def _flagged_reward(reward, check, *envs):
 def run_episode(static, dynamic, policy, container_width, container_height,
                 reward_type='C+P+S-lb-soft', heightmap_type='diff', packing_strategy='LB_GREEDY',
                 input_type='bot', allow_rot=True, env=None, record=False, steps=None, fused=True, bits=None,
-                container_length=None, stepper=None, check='nan'):
+                container_length=None, stepper=None, check='nan', pack_policy=None):
     """One episode for a batch (model.py:254-515 minus the network).
 
     ``policy(step=, static=, dynamic=, current_mask=, mask=, decoder_static=, decoder_dynamic=)``
@@ -131,7 +131,14 @@ def run_episode(static, dynamic, policy, container_width, container_height,
     allocated per episode; the returned tensors are then views of its buffers, valid until its next ``begin``);
     None builds one for this call.  ``check``: what ``reward`` holds for containers that raised an error bit
     (_flagged_reward: 'nan' -- NaN, no host sync --, 'raise', or False for the raw ratio).
+
+    ``pack_policy(pnet_input, block)``: the learned local pack-net's loop instead (DRL_L.forward, model.py:1016-1250):
+    the block goes to a column the pack policy picks -- see _run_episode_pack.
     """
+    if pack_policy is not None:
+        return _run_episode_pack(static, dynamic, policy, pack_policy, container_width, container_height, reward_type,
+                                 heightmap_type, packing_strategy, input_type, allow_rot, env, record, steps,
+                                 bits=False if bits is None else bits, check=check)
     if input_type in ('mul', 'mul-with'):
         return _run_episode_mul(static, dynamic, policy, container_width, container_height, reward_type,
                                 heightmap_type, packing_strategy, input_type, allow_rot, record, steps, check)
@@ -189,6 +196,70 @@ def run_episode(static, dynamic, policy, container_width, container_height,
            'dynamic': masks.dynamic, 'mask': masks.mask}
     if record:
         out.update(features=feats, current_masks=curs, masks=msks)
+    return out
+
+
+def _run_episode_pack(static, dynamic, policy, pack_policy, container_width, container_height, reward_type,
+                      heightmap_type, packing_strategy, input_type, allow_rot, env, record, steps, bits=False, check='nan'):
+    """DRL_L's decoding loop (model.py:1016-1250) minus its two networks.  Per step: the precedence update
+    (tap_mask_step, model.py:1118-1128), ``policy`` -> ptr, ``pack_policy(pnet_input, block)`` -> the column, then one
+    place-at launch with the gather fused (tap_env_step_at_gather, Container.add_new_block_at's rules,
+    model.py:1205-1212) that also writes the decoder feature and the pack policy's next input.
+    ``pnet_input`` (B, 1, W) f32 is the height-map in DRL_L's heightmap_type form (model.py:1180-1196; 'diff' with its
+    trailing 0), ``block`` = decoder_static transposed, (B, 1, 2).  pack_policy returns columns (B,) int64, or
+    probabilities (B, W), which are argmaxed (model.py:1200-1202) and give ``pack_logp``, the log of the chosen
+    column's probability.  Nothing is read back to the host inside the loop, so the episode can be captured in a
+    hipGraph.  Returns run_episode's dict plus ``place_x`` (B, steps) int64 [and ``pack_logp`` (B, steps)]."""
+    if input_type in ('mul', 'mul-with'):
+        raise NotImplementedError("the pack-net loop of the two-container input types is not implemented")
+    D = int(static.shape[1]) - 1
+    if D != 2:
+        raise NotImplementedError("the pack-net placement is 2D only (tools.py:3762 unpacks two block sides)")
+    n = int(dynamic.shape[-1]) // (math.factorial(D) if allow_rot else 1)
+    B = int(static.shape[0])
+    nsteps = n if steps is None else steps
+    dev = _lib.resolve_device(static.device)
+    if env is None:
+        env = BatchedContainer(B, [container_width, container_height], n, reward_type, heightmap_type,
+                               packing_strategy=packing_strategy, device=dev, place_at='container')
+    elif env.place_at != 'container':
+        raise ValueError("env must be a BatchedContainer built with place_at='container'")
+    else:
+        env.reset()
+    masks = MaskStepper(static.to(dev), dynamic.to(dev), input_type, allow_rot, bits)
+    static_part = masks.static[:, 1:, :]
+    W = env.desc.W
+    # two buffers for the pack policy's input, alternating: the one a policy was handed is never overwritten by the
+    # step that follows it (a recorded episode keeps every step's input)
+    pnet = [torch.zeros(B, 1, W, dtype=torch.float32, device=dev) for _ in range(2)]
+    decoder_static = torch.zeros(B, D, 1, device=dev)
+    decoder_dynamic = torch.zeros(env._feature_shape(), device=dev)
+    tour, xs, logps, feats, curs, msks, pins = [], [], [], [], [], [], []
+    for step in range(nsteps):
+        ptr = policy(step=step, static=masks.static, dynamic=masks.dynamic, current_mask=masks.current_mask,
+                     mask=masks.mask, decoder_static=decoder_static, decoder_dynamic=decoder_dynamic).to(torch.int64)
+        masks.step(ptr)                                                                     # model.py:1118-1128
+        decoder_static = torch.gather(static_part, 2, ptr.view(-1, 1, 1).expand(-1, D, 1))  # model.py:1164-1167
+        pin, pout = pnet[step % 2], pnet[(step + 1) % 2]
+        out = pack_policy(pin, decoder_static.transpose(2, 1))
+        if out.dim() == 2:                                                                  # probabilities, model.py:1200-1202
+            best = out.max(1)
+            x = best[1]
+            logps.append(best[0].log().unsqueeze(1))
+        else:
+            x = out.reshape(B).to(torch.int64)
+        decoder_dynamic = env.add_new_blocks_at_gather(masks.static, ptr, x, pnet_out=pout, pnet_form=heightmap_type)
+        tour.append(ptr.unsqueeze(1))
+        xs.append(x.unsqueeze(1))
+        if record:
+            feats.append(decoder_dynamic); curs.append(masks.current_mask); msks.append(masks.mask); pins.append(pin.clone())
+    ratio = env.calc_ratios()                                                               # model.py:1226-1234
+    out = {'tour_idx': torch.cat(tour, dim=1), 'place_x': torch.cat(xs, dim=1), 'reward': _flagged_reward(-ratio, check, env),
+           'env': env, 'dynamic': masks.dynamic, 'mask': masks.mask}
+    if logps:
+        out['pack_logp'] = torch.cat(logps, dim=1)
+    if record:
+        out.update(features=feats, current_masks=curs, masks=msks, pnet_inputs=pins)
     return out
 
 
