@@ -115,7 +115,8 @@ const char *tap_last_error(const tap_ctx *ctx);
  *      k_rolling_window_big<D, MW>                (20, D, 0, 2, 0, MW, wt)       MW mask words 4, 16, 64
  *   21 k_rolling_init<D>                          (21, D, 0, 0, 0, 0, 0)
  *      k_rolling_init_big<D, MW>                  (21, D, 0, 1, 0, MW, 0)
- *   22 k_place_at<G, NET>                         (22, 2, G, SEM, GATHER, 0, 0)  SEM a TAP_AT_*, GATHER 1 = _gather
+ *   22 k_place_at<G, NET, ENG>                    (22, 2, G, SEM, GATHER, ENG, 0)  SEM a TAP_AT_*, GATHER 1 = _gather,
+ *                                                 ENG 1 = tap_env_step_engine
  * wt is the launch's RollArgs::wt (the window's fp32 stores; the init kernels store none), 0 for the episode kernels. */
 int tap_variant_hits(tap_ctx *ctx, int32_t *out, int cap);
 int tap_variant_hits_reset(tap_ctx *ctx);
@@ -189,6 +190,29 @@ int tap_env_step_at(tap_ctx *ctx, const tap_env_desc *d, void *state, const void
 int tap_env_step_at_gather(tap_ctx *ctx, const tap_env_desc *d, void *state, const float *static_, int static_rows,
                            int nR, const int64_t *ptr, const uint8_t *active, float *feature_out, const int64_t *pos_x,
                            float *pnet_out, int pnet_form, void *stream);
+
+/* The global pack-net's environment (pack_net/LG_RL.py: PackEngine.step, LG_RL.py:440-496; reward types C+P+S-G-soft
+ * / C+P+S-LG-soft, the reference's DRL_RNN) at inner step `step` of a PackRNN forward, for all B envs of a TAP_AT_NET
+ * descriptor whose tape holds at least T steps (n_max >= T).  Block b is blocks[b, :, step] of a (B, 2, T) f32 array,
+ * truncated (block.int()); it goes to column pos_x[b] (B,) int64 with TAP_AT_NET's rules (clamp to W - w, z =
+ * max(heightmap[x:x+w]), stability of the support row, empty_size = sum(heightmap) - valid_size).
+ *   step % max_blocks == 0  the step starts from the empty container and reads nothing from the blob (the forward's
+ *                           clear, LG_RL.py:610-614, and the engine's wrap); max_blocks = 0: never wraps, only step 0
+ *   tape                    (x, z) and stability are recorded at index `step` ((0, 0), unstable, for a refused block);
+ *                           the counters' 4th field is the forward's tape length, step + 1 (tap_env_export shows that
+ *                           many rows); the error word restarts at step 0
+ *   reward_out              (B,) f32 or NULL: (C + P + S) / 3 in fp64, stored as f32 -- C = valid / (max(hm) * W), P =
+ *                           valid / (valid + empty), S = stable blocks / steps since the last clear (PackEngine counts
+ *                           every step), C and P 0 when their denominator is 0 (LG_RL.py:460-475, 670)
+ *   (step + 1) % max_blocks == 0  after the reward and the tape were taken, the engine clears (LG_RL.py:482-491): the
+ *                           blob and feature_out hold the empty container
+ *   feature_out             (B, W') f32 or NULL: the net's next input in the descriptor's heightmap_type form (the
+ *                           layout tap_env_step writes; W' = W - 1 for diff)
+ * A column < 0 or a block wider than W: error bit 4, not placed; z + h > H: error bit 1 (the reference clips its numpy
+ * slices), placed.  TAP_E_INVALID for another descriptor, step outside [0, T) or beyond n_max, max_blocks < 0.  One
+ * launch (k_place_at, lane per column). */
+int tap_env_step_engine(tap_ctx *ctx, const tap_env_desc *d, void *state, const float *blocks, int T, int step,
+                        int max_blocks, const int64_t *pos_x, float *feature_out, float *reward_out, void *stream);
 
 /* tools.Container.get_heightmap (tools.py:3824-3856): the feature of the current state */
 int tap_env_feature(tap_ctx *ctx, const tap_env_desc *d, const void *state, float *feature_out,

@@ -81,6 +81,7 @@ _PROTOS = {
     "tap_env_step_gather": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "tap_env_step_at": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "tap_env_step_at_gather": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "tap_env_step_engine": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "tap_env_feature": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp]),
     "tap_env_ratio": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp, _vp, _vp]),
     "tap_env_export": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp, _vp, _vp, _vp]),

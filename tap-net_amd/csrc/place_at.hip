@@ -15,6 +15,17 @@
 // Mapping: one lane per column, G = 8/16/32/64 lanes per container (tap_group_size), so several W = 5 containers share
 // a wavefront; z, the support mask and the counter sums are group reductions (tap_place.h).  One launch per step also
 // writes the decoder feature (the layout tap_env_step writes) and, optionally, the pack-net's input for the NEXT step.
+//
+// Engine mode (ENG, TAP_AT_NET only; tap_env_step_engine): the global pack-net's own environment, pack_net/LG_RL.py's
+// PackEngine.step (LG_RL.py:440-496) at inner step `step` of a PackRNN forward.  Its placement, stability and
+// empty_size are TAP_AT_NET's (on a height-map state LG_RL.is_stable_2d reads no -1 cell, so it agrees with
+// tools.is_stable_2d).  What differs: the block is column `step` of blocks (B, 2, T) f32, read in place; a step with
+// step % max_blocks == 0 starts from the empty container without reading the blob (the forward's clear, LG_RL.py:610-614,
+// and the engine's wrap); the tape is written at index `step` and the 4th counter holds its length (step + 1, which
+// tap_env_export reads as the steps taken); the reward (C+P+S)/3 is computed in fp64 and stored as
+// f32 (LG_RL.py:460-475, 670); after the step that makes time == max_blocks the engine clears (LG_RL.py:482-491), so
+// the blob and the next input are left empty -- the reward and the tape keep the values from before the clear.
+// max_blocks = 0: never wraps, only step 0 starts empty (LG_RL.calc_positions' replay, LG_RL.py:714-727).
 #include "tap_common.h"
 #include "tap_place.h"
 
@@ -35,11 +46,15 @@ struct AtArgs {
     int flen;
     float *pnet_out;       // (B, 1, W) or null
     int pnet_form;         // TAP_FEAT_*: full / zero / diff in DRL_L's form (length W, trailing 0)
+    // engine mode (ENG): blocks is (B, 2, T) f32, column `step`; wrap period max_blocks (0 = never)
+    int T, step, max_blocks;
+    float *reward_out;     // (B,) f32 or null
 };
 
-template <int G, bool NET>
+template <int G, bool NET, bool ENG>
 __global__ void __launch_bounds__(TAP_BLOCK) k_place_at(AtArgs a)
 {
+    static_assert(NET || !ENG, "the engine mode has TAP_AT_NET's rules");
     __shared__ int s_hm[TAP_BLOCK];
     const int tid = threadIdx.x, c = tid % G, lane = tid & 63, gl0 = lane - c;
     const int env = blockIdx.x * (TAP_BLOCK / G) + tid / G;
@@ -51,9 +66,12 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_place_at(AtArgs a)
     const long xraw = (long)a.pos_x[envc];
     long praw = 0;
     if (a.static_) praw = (long)a.ptr[envc];
-    const int hm_l = a.v.hm[(size_t)envc * W + cc];
+    // engine mode: `start` = the container is empty before this step (nothing read), `wrap` = it is cleared after it
+    const bool start = ENG && (a.max_blocks > 0 ? a.step % a.max_blocks == 0 : a.step == 0);
+    const bool wrap = ENG && a.max_blocks > 0 && (a.step + 1) % a.max_blocks == 0;
+    const int hm_l = start ? 0 : a.v.hm[(size_t)envc * W + cc];
     const int col_l = NET ? 0 : a.col[(size_t)envc * W + cc];
-    const int4 cnt = reinterpret_cast<const int4 *>(a.v.cnt)[envc];
+    const int4 cnt = start ? make_int4(0, 0, 0, 0) : reinterpret_cast<const int4 *>(a.v.cnt)[envc];
     unsigned char act_l = 1;
     if (a.active) act_l = a.active[envc];
     int bw, bh;
@@ -64,6 +82,10 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_place_at(AtArgs a)
         const float fh = a.static_[((size_t)envc * a.static_rows + 2) * a.nR + p];
         bw = badp ? 0 : (int)fw;
         bh = badp ? 0 : (int)fh;
+    } else if (ENG) { // blocks[b, :, step], block.int() (LG_RL.py:450)
+        const float *bp = (const float *)a.blocks + (size_t)envc * 2 * a.T + a.step;
+        bw = (int)bp[0];
+        bh = (int)bp[a.T];
     } else if (a.blocks_dtype == TAP_DT_F32) { // block.astype('int'), tools.py:3760
         bw = (int)((const float *)a.blocks)[(size_t)envc * 2];
         bh = (int)((const float *)a.blocks)[(size_t)envc * 2 + 1];
@@ -99,15 +121,17 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_place_at(AtArgs a)
     }
     const int hsum = NET ? group_sum<G>(incol ? hm : 0) : 0;
     const int demp = NET ? 0 : group_sum<G>(dcol);
-    s_hm[tid] = hm;
+    const int hmax = ENG && a.reward_out ? group_max<G>(incol ? hm : 0) : 0;
+    const int hm_w = wrap ? 0 : hm;                                        // what the blob and the next input see
+    s_hm[tid] = hm_w;
     tap_wave_lds_sync();
     const int *s = s_hm + (tid - c);
     if (ev) {
         if (incol) {
-            a.v.hm[(size_t)env * W + c] = hm;
+            a.v.hm[(size_t)env * W + c] = hm_w;
             if (!NET && do_step && inb) a.col[(size_t)env * W + c] = col;
         }
-        if (a.feature_out) tap_write_feature<2, G>(a.d.feature, W, 1, s, c, hm, a.feature_out + (size_t)env * a.flen);
+        if (a.feature_out) tap_write_feature<2, G>(a.d.feature, W, 1, s, c, hm_w, a.feature_out + (size_t)env * a.flen);
         if (a.pnet_out) {                                                  // model.py:1173-1196 / tools.py:3407
             float *o = a.pnet_out + (size_t)env * W;
             if (a.pnet_form == TAP_FEAT_ZERO) {
@@ -120,16 +144,33 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_place_at(AtArgs a)
             }
         }
         if (c == 0) {
-            if (do_step) {
-                const int valid = cnt.x + bw * bh;
-                const int empty = NET ? hsum - valid : cnt.y + demp;
-                reinterpret_cast<int4 *>(a.v.cnt)[env] = make_int4(valid, empty, cnt.z + stab, cnt.w + 1);
-                int32_t *q = a.v.pos + (size_t)cnt.w * 2 * B + env;
-                q[0] = x;
+            const int4 now = do_step ? make_int4(cnt.x + bw * bh, 0, cnt.z + stab, cnt.w + 1) : cnt;
+            const int valid = now.x;
+            const int empty = !do_step ? cnt.y : NET ? hsum - valid : cnt.y + demp;
+            // engine: the 4th counter is the forward's tape length (step + 1; tap_env_export shows that many rows), kept
+            // across a wrap; the blocks since the last clear follow from the step (PackEngine counts every step)
+            if (ENG)
+                reinterpret_cast<int4 *>(a.v.cnt)[env] = wrap ? make_int4(0, 0, 0, a.step + 1)
+                                                              : make_int4(valid, empty, now.z, a.step + 1);
+            else if (do_step)
+                reinterpret_cast<int4 *>(a.v.cnt)[env] = make_int4(valid, empty, now.z, now.w);
+            if (do_step || ENG) {
+                const int t = ENG ? a.step : cnt.w;                            // the engine's tape: by step index
+                int32_t *q = a.v.pos + (size_t)t * 2 * B + env;
+                q[0] = x;                                                      // (0, 0), unstable, for a refused step
                 q[B] = z;
-                a.v.stable[(size_t)cnt.w * B + env] = (uint8_t)stab;
+                a.v.stable[(size_t)t * B + env] = (uint8_t)(do_step ? stab : 0);
             }
-            if (err) a.v.err[env] |= err;
+            if (ENG && a.reward_out) {                                         // LG_RL.py:460-475, rw.astype('float32')
+                const int since = (a.max_blocks > 0 ? a.step % a.max_blocks : a.step) + 1;
+                const double box = (double)hmax * W, ve = (double)valid + (double)empty;
+                const double C = box == 0 ? 0.0 : (double)valid / box;
+                const double P = ve == 0 ? 0.0 : (double)valid / ve;
+                const double S = (double)now.z / (double)since;
+                a.reward_out[env] = (float)(((C + P) + S) / 3);
+            }
+            if (ENG && a.step == 0) a.v.err[env] = err;                        // errors of this forward only
+            else if (err) a.v.err[env] |= err;
         }
     } else {
         // out-of-range groups take part in the group-wide reductions of the writers, so cross-lane ops stay convergent
@@ -138,21 +179,22 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_place_at(AtArgs a)
     }
 }
 
-template <int G, bool NET> int launch_at(tap_ctx *ctx, const AtArgs &a, hipStream_t st)
+template <int G, bool NET, bool ENG> int launch_at(tap_ctx *ctx, const AtArgs &a, hipStream_t st)
 {
     const int epb = TAP_BLOCK / G, grid = (a.d.B + epb - 1) / epb;
-    hipLaunchKernelGGL((k_place_at<G, NET>), dim3(grid), dim3(TAP_BLOCK), 0, st, a);
+    hipLaunchKernelGGL((k_place_at<G, NET, ENG>), dim3(grid), dim3(TAP_BLOCK), 0, st, a);
     TAP_LAUNCH_CHECK(ctx, "k_place_at");
-    tap_variant_hit(ctx, TAP_HIT_PLACE_AT, 2, G, TapVariant{NET ? TAP_AT_NET : TAP_AT_CONTAINER, a.static_ ? 1 : 0, 0}, 0);
+    tap_variant_hit(ctx, TAP_HIT_PLACE_AT, 2, G,
+                    TapVariant{NET ? TAP_AT_NET : TAP_AT_CONTAINER, a.static_ ? 1 : 0, ENG ? 1 : 0}, 0);
     return TAP_OK;
 }
 
-template <bool NET> int dispatch_at(tap_ctx *ctx, int G, const AtArgs &a, hipStream_t st)
+template <bool NET, bool ENG = false> int dispatch_at(tap_ctx *ctx, int G, const AtArgs &a, hipStream_t st)
 {
-    if (G == 8) return launch_at<8, NET>(ctx, a, st);
-    if (G == 16) return launch_at<16, NET>(ctx, a, st);
-    if (G == 32) return launch_at<32, NET>(ctx, a, st);
-    return launch_at<64, NET>(ctx, a, st);
+    if (G == 8) return launch_at<8, NET, ENG>(ctx, a, st);
+    if (G == 16) return launch_at<16, NET, ENG>(ctx, a, st);
+    if (G == 32) return launch_at<32, NET, ENG>(ctx, a, st);
+    return launch_at<64, NET, ENG>(ctx, a, st);
 }
 
 int step_at_common(tap_ctx *ctx, const tap_env_desc *d, void *state, AtArgs &a, const int64_t *pos_x, float *pnet_out,
@@ -179,6 +221,7 @@ int step_at_common(tap_ctx *ctx, const tap_env_desc *d, void *state, AtArgs &a, 
     a.pnet_form = pnet_form;
     a.flen = tap_env_feature_len(d);
     const int G = tap_group_size(d);
+    if (a.T > 0) return dispatch_at<true, true>(ctx, G, a, (hipStream_t)stream);   // engine mode (checked TAP_AT_NET)
     return sem == TAP_AT_NET ? dispatch_at<true>(ctx, G, a, (hipStream_t)stream)
                              : dispatch_at<false>(ctx, G, a, (hipStream_t)stream);
 }
@@ -221,4 +264,23 @@ extern "C" int tap_env_step_at_gather(tap_ctx *ctx, const tap_env_desc *d, void 
     a.static_ = static_; a.static_rows = static_rows; a.nR = nR; a.ptr = ptr;
     a.active = active; a.feature_out = feature_out;
     return step_at_common(ctx, d, state, a, pos_x, pnet_out, pnet_form, stream);
+}
+
+extern "C" int tap_env_step_engine(tap_ctx *ctx, const tap_env_desc *d, void *state, const float *blocks, int T,
+                                   int step, int max_blocks, const int64_t *pos_x, float *feature_out,
+                                   float *reward_out, void *stream)
+{
+    if (!d) return tap_fail(ctx, TAP_E_INVALID, "null descriptor");
+    if (tap_place_at_semantics(d) != TAP_AT_NET)
+        return tap_fail(ctx, TAP_E_INVALID, "the engine step needs a TAP_AT_NET descriptor (tap_env_desc_set_place_at)");
+    if (T < 1 || step < 0 || step >= T || max_blocks < 0)
+        return tap_fail(ctx, TAP_E_INVALID, "engine step %d of T = %d columns, max_blocks %d", step, T, max_blocks);
+    if (step >= d->n_max)
+        return tap_fail(ctx, TAP_E_INVALID, "engine step %d beyond the descriptor's tape of %d", step, d->n_max);
+    if (d->B == 0 && d->D == 2) return tap_desc_validate(ctx, d);
+    if (d->B != 0 && !blocks) return tap_fail(ctx, TAP_E_INVALID, "null blocks");
+    AtArgs a = {};
+    a.blocks = blocks; a.blocks_dtype = TAP_DT_F32; a.feature_out = feature_out;
+    a.T = T; a.step = step; a.max_blocks = max_blocks; a.reward_out = reward_out;
+    return step_at_common(ctx, d, state, a, pos_x, nullptr, 0, stream);
 }

@@ -293,6 +293,98 @@ class BatchedContainer(object):
         self._state.copy_(sd['state'])
 
 
+class PackEngines(object):
+    """B of the global pack-net's own environments (pack_net/LG_RL.py: PackEngine, LG_RL.py:414-528) in one state blob,
+    stepped by one launch per inner step for all of them (tapenv.h: tap_env_step_engine).  ``T`` is the longest block
+    sequence a forward hands in (the tape's length); ``max_blocks_num`` the engine's wrap period (PackEngine clears
+    after that many steps, LG_RL.py:482-491; 0 = never, the replay of LG_RL.calc_positions).  Nothing is read back to
+    the host.
+
+    step(i, blocks, x) places blocks[:, :, i] of a (B, 2, T') float32 array (T' <= T) at columns x (B,) int64 and
+    returns the net's next input (B, W', 1) float32 in ``heightmap_type`` form (W' = W - 1 for 'diff'); with
+    ``want_reward`` it also refreshes ``reward`` (B,) float32, the step's (C+P+S)/3.  Step 0 -- and every
+    i % max_blocks_num == 0 -- starts from the empty container, so a forward needs no reset launch."""
+
+    def __init__(self, batch_size, container_width, container_height, T, heightmap_type='diff', max_blocks_num=10,
+                 device='cuda'):
+        if heightmap_type not in ('full', 'zero', 'diff'):
+            raise ValueError("heightmap_type must be 'full', 'zero' or 'diff', not %r" % (heightmap_type,))
+        if int(max_blocks_num) < 0:
+            raise ValueError("max_blocks_num must be >= 0")
+        self.batch_size, self.W, self.H, self.T = int(batch_size), int(container_width), int(container_height), int(T)
+        self.heightmap_type = heightmap_type
+        self.max_blocks_num = int(max_blocks_num)
+        self.env = BatchedContainer(self.batch_size, [self.W, self.H], self.T, 'C+P+S-G-soft', heightmap_type,
+                                    device=device, place_at='net')
+        self.device = self.env.device
+        self.reward = torch.zeros(self.batch_size, dtype=torch.float32, device=self.device)
+        self.last_input = None                   # what the last step returned: the blob's state in heightmap_type form
+
+    def reset(self):
+        """PackEngine.clear for every env (one launch; step 0 of a forward clears by itself)."""
+        self.env.reset()
+        self.last_input = None
+
+    def _blocks(self, blocks):
+        if blocks.dim() != 3 or blocks.shape[0] != self.batch_size or blocks.shape[1] != 2:
+            raise ValueError("blocks must be (%d, 2, T), got %s" % (self.batch_size, tuple(blocks.shape)))
+        if blocks.dtype != torch.float32 or blocks.device != self.device or not blocks.is_contiguous():
+            blocks = blocks.to(device=self.device, dtype=torch.float32).contiguous()
+        return blocks
+
+    def step(self, i, blocks, x, want_reward=True, out=None, want_input=True):
+        """PackEngine.step of every env at inner step ``i`` (LG_RL.py:440-496): see the class docstring.  Returns None
+        with ``want_input=False`` (the replay of LG_RL.calc_positions reads only the counters and the tape)."""
+        blocks = self._blocks(blocks)
+        Tb = int(blocks.shape[2])
+        i = int(i)
+        if not 0 <= i < min(Tb, self.T):
+            raise ValueError("step %d outside the %d blocks handed in / the tape of %d" % (i, Tb, self.T))
+        x = self.env._as_pos_x(x)
+        shape = self.env._feature_shape()
+        if out is not None and (tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous()
+                                or out.device != self.device):
+            raise ValueError("out must be a contiguous float32 tensor of shape %s on %s" % (shape, self.device))
+        feat = out if out is not None else (self.env._new_feature() if want_input else None)
+        self.env._call(_lib.lib().tap_env_step_engine, _lib.ptr(self.env._state), _lib.ptr(blocks), Tb, i,
+                       self.max_blocks_num, _lib.ptr(x), _lib.ptr(feat), _lib.ptr(self.reward if want_reward else None))
+        self.last_input = feat
+        return feat
+
+    @property
+    def positions(self):
+        """(B, T, 2) int32: (x after the clamp, z) of every step of the last forward, by step index"""
+        return self.env.positions
+
+    @property
+    def stable(self):
+        """(B, T) bool"""
+        return self.env.stable
+
+    @property
+    def errors(self):
+        return self.env.errors
+
+    def check(self):
+        self.env.check()
+
+    def get_heightaps(self, heightmap_type):
+        """PackEngine.get_heightap (LG_RL.py:498-515) of every env: (B, W', 1) float32 -- 'full' the height-map, 'zero'
+        minus its minimum, 'diff' hm[c+1] - hm[c] (W - 1 entries)."""
+        if heightmap_type == self.heightmap_type and self.last_input is not None:
+            return self.last_input
+        hm = self.env.heightmap.to(torch.float32)
+        if heightmap_type == 'full':
+            out = hm
+        elif heightmap_type == 'zero':
+            out = hm - hm.min(dim=1, keepdim=True).values
+        elif heightmap_type == 'diff':
+            out = hm[:, 1:] - hm[:, :-1]
+        else:
+            raise ValueError("heightmap_type must be 'full', 'zero' or 'diff', not %r" % (heightmap_type,))
+        return out.unsqueeze(2).contiguous()
+
+
 # ---- lock-step pooling of per-env Containers -------------------------------------------------------------------------
 # model.py:294 builds `batch_size` tools.Container objects and model.py:451-453 calls each of them once per decoding
 # step before it stacks the results (torch.FloatTensor(heightmaps), model.py:454-465); model.py:509-510 does the same

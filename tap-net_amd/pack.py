@@ -702,14 +702,14 @@ def reward(static, tour_indices, reward_type, input_type, allow_rot, container_w
            packing_strategy='LB_GREEDY', pack_net=None):
     """pack.reward (pack.py:378-473): pack every env's blocks in tour order from an empty
     container and return ``-scores`` (un-normalised C+P+S, tools.py:2442-2449), one launch.
-    ``pack_net`` (a tools.DQN): the SL / RL reward types are then scored as the reference scores them,
-    tools.calc_positions_net's (C+P+S)/3 (pack.py:431-433; episode_scores_net); without it they keep the LB_GREEDY
-    scoring above."""
-    if pack_net is not None and reward_type in _L_PNET_TYPES and packing_strategy not in ('MACS', 'MUL'):
+    ``pack_net`` (a tools.DQN for the SL / RL reward types, a tools.PackRNN for G / LG): those types are then scored
+    as the reference scores them, tools.calc_positions_net's (C+P+S)/3 (pack.py:431-433; episode_scores_net /
+    episode_scores_rnn); without it they keep the LB_GREEDY scoring above."""
+    if pack_net is not None and reward_type in _NET_REWARD_TYPES and packing_strategy not in ('MACS', 'MUL'):
         if input_type in ('mul', 'mul-with'):
             raise NotImplementedError("the pack-net reward of the two-container input types is not implemented")
-        ratio, _ = episode_scores_net(static, tour_indices, reward_type, [container_width, container_height], pack_net,
-                                      input_type, allow_rot)
+        ratio, _ = _episode_scores_pack_net(static, tour_indices, reward_type, [container_width, container_height],
+                                            pack_net, input_type, allow_rot)
         return -ratio.to(torch.float32)
     if packing_strategy in ('MACS', 'MUL'):
         # pack.py:431 names tools.calc_positions_mus, which does not exist in the reference
@@ -763,6 +763,17 @@ _MCS_RATIO_TYPES = ('comp', 'soft', 'hard', 'pyrm', 'pyrm-soft', 'pyrm-hard', 'm
                     'C+P+S-mul-soft', 'C+P+S-mul-hard', 'C+P+S-mcs-soft', 'C+P+S-mcs-hard')
 _NET_REWARD_TYPES = ('C+P+S-SL-soft', 'C+P+S-RL-soft', 'C+P+S-G-soft', 'C+P+S-LG-soft')             # pack.py:728-730
 _L_PNET_TYPES = ('C+P+S-SL-soft', 'C+P+S-RL-soft')                  # the learned local pack-net (tools.py:3544-3553)
+_PACK_RNN_TYPES = ('C+P+S-G-soft', 'C+P+S-LG-soft')                  # the global pack-net (tools.py:3528-3532)
+
+
+def _episode_scores_pack_net(static, tour_indices, reward_type, container_size, net, input_type, allow_rot):
+    """calc_positions_net's scoring of a batch with the network the reward type names (pack.py:431-433, 745-747)"""
+    from .tools import PackRNN
+    if reward_type in _PACK_RNN_TYPES:
+        if not isinstance(net, PackRNN):
+            raise TypeError("%s is scored with a tools.PackRNN, not %s" % (reward_type, type(net).__name__))
+        return episode_scores_rnn(static, tour_indices, container_size, net, input_type, allow_rot)
+    return episode_scores_net(static, tour_indices, reward_type, container_size, net, input_type, allow_rot)
 RENDER_FILES = ('ratio', 'valid_size', 'box_size', 'empty_size', 'stable_num', 'packing_height', 'time', 'ids')
 
 
@@ -895,14 +906,22 @@ def episode_scores_net(static, tour_indices, reward_type, container_size, net, i
         for t in range(n):
             x = net(pnet, blocks_f[:, t:t + 1, :]).max(1)[1]                                       # :3411
             env.add_new_blocks_at(blocks[:, t], x, want_feature=False, pnet_out=pnet, pnet_form='full')
+    ratio, scores = _net_scores(env, n, check)
+    return (ratio, scores, env) if with_env else (ratio, scores)
+
+
+def _net_scores(env, n, check):
+    """calc_positions_net's score of n blocks placed with TAP_AT_NET's rules (tools.py:3576-3598; LG_RL.calc_positions
+    scores its replay the same way, LG_RL.py:730-742) -> ratio (B,) float64, scores (B, 5) int64"""
     if check:
         env.check()
+    B, W = env.batch_size, env.desc.W
     cnt = env.counters.to(torch.int64)
     max_h = env.heightmap.max(dim=1).values.to(torch.int64)
     box = max_h * W                                                                                   # :3579-3580
     valid, empty, nst = cnt[:, 0], cnt[:, 1], cnt[:, 2]
     if n == 0:
-        ratio = torch.zeros(B, dtype=torch.float64, device=dev)
+        ratio = torch.zeros(B, dtype=torch.float64, device=env.device)
     else:
         C = valid.double() / box.double()
         P = valid.double() / (empty + valid).double()
@@ -911,7 +930,45 @@ def episode_scores_net(static, tour_indices, reward_type, container_size, net, i
     if not check:
         ratio = torch.where(env.errors != 0, torch.full_like(ratio, float('nan')), ratio)
     scores = torch.stack((valid, box, empty, nst, max_h), 1)                                          # :3597
-    return (ratio, scores, env) if with_env else (ratio, scores)
+    return ratio, scores
+
+
+def episode_scores_rnn(static, tour_indices, container_size, net, input_type='bot', allow_rot=True, check=True,
+                       with_env=False):
+    """tools.calc_positions_LG_net (tools.py:3463-3504) for every sample of a batch, G / LG types: ONE forward of
+    ``net`` (a tools.PackRNN) over the blocks in tour order picks every column -- its engine wraps every
+    net.max_blocks_num blocks --, then LG_RL.calc_positions' replay (LG_RL.py:714-727) places the recorded columns into
+    a fresh container without a wrap: n engine launches with max_blocks = 0 (tapenv.h: tap_env_step_engine).
+    -> (ratio (B,) float64 = (C+P+S)/3 of the replay, scores (B, 5) int64 as episode_scores_net) [, the replay's
+    BatchedContainer with ``with_env``].  The forward's own reward (its -rw) is not the replay's ratio once n exceeds
+    the wrap period."""
+    from .env import PackEngines
+    block_dim = _block_dim(static, input_type)
+    if block_dim != 2:
+        raise NotImplementedError("the global pack-net is 2D only (PackEngine's height-map is a row)")
+    R = _rotate_types(block_dim, allow_rot)
+    st = _f32c(static)
+    B, rows, nR = st.shape
+    n = nR // R
+    dev = st.device
+    tour = tour_indices.to(device=dev, dtype=torch.int64)
+    if tour.shape[1] < n:
+        raise ValueError("tour shorter than blocks_num")
+    tour = tour[:, :n]
+    cs = [int(v) for v in container_size]
+    if int(net.container_width) != cs[0]:
+        raise ValueError("the pack-net places into %d columns, the container has %d" % (net.container_width, cs[0]))
+    blocks = torch.gather(st[:, 1:3, :], 2, tour.unsqueeze(1).expand(-1, 2, -1))
+    blocks = blocks.to(torch.int32).to(torch.float32)                                  # astype('int'), tools.py:3484-3490
+    replay = PackEngines(B, cs[0], cs[1], max(n, 1), 'full', max_blocks_num=0, device=dev)
+    if n:
+        with torch.no_grad():
+            positions, _, _ = net(blocks, n)                                           # LG_RL.py:694
+        xs = positions[:, :, 0].to(torch.int64)
+        for t in range(n):                                                             # LG_RL.py:714-727
+            replay.step(t, blocks, xs[:, t], want_reward=False, want_input=False)
+    ratio, scores = _net_scores(replay.env, n, check)
+    return (ratio, scores, replay.env) if with_env else (ratio, scores)
 
 
 def render(static, tour_indices, save_path, dynamic, valid_time, pack_net=None, **kwargs):
@@ -940,15 +997,15 @@ def render(static, tour_indices, save_path, dynamic, valid_time, pack_net=None, 
         container_size_ab = [container_width, container_height]
     strategy = kwargs['packing_strategy']
     reward_type = kwargs['reward_type']
-    net_path = pack_net is not None and strategy not in ('MACS', 'MUL') and reward_type in _L_PNET_TYPES
+    net_path = pack_net is not None and strategy not in ('MACS', 'MUL') and reward_type in _NET_REWARD_TYPES
     if net_path and (mul or block_dim != 2):
         raise NotImplementedError("the pack-net render is implemented for the 2D single-container input types")
     if not net_path and strategy not in ('MACS', 'MUL') and reward_type in _NET_REWARD_TYPES:
         raise NotImplementedError("tools.calc_positions_net (the pack-net back-ends) is outside this package")
     args = (static, tour_indices, reward_type, input_type, kwargs['allow_rot'])
     if net_path:                                                                    # pack.py:728-730, 792
-        ratio, scores = episode_scores_net(static, tour_indices, reward_type, container_size, pack_net, input_type,
-                                           kwargs['allow_rot'])
+        ratio, scores = _episode_scores_pack_net(static, tour_indices, reward_type, container_size, pack_net,
+                                                 input_type, kwargs['allow_rot'])
         scores = scores.double()
     elif mul:
         ra, sa = episode_scores(*args, container_size_ab, strategy, target=0)

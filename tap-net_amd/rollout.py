@@ -115,7 +115,7 @@ def _flagged_reward(reward, check, *envs):
 def run_episode(static, dynamic, policy, container_width, container_height,
                 reward_type='C+P+S-lb-soft', heightmap_type='diff', packing_strategy='LB_GREEDY',
                 input_type='bot', allow_rot=True, env=None, record=False, steps=None, fused=True, bits=None,
-                container_length=None, stepper=None, check='nan', pack_policy=None):
+                container_length=None, stepper=None, check='nan', pack_policy=None, pack_rnn=None):
     """One episode for a batch (model.py:254-515 minus the network).
 
     ``policy(step=, static=, dynamic=, current_mask=, mask=, decoder_static=, decoder_dynamic=)``
@@ -134,7 +134,15 @@ def run_episode(static, dynamic, policy, container_width, container_height,
 
     ``pack_policy(pnet_input, block)``: the learned local pack-net's loop instead (DRL_L.forward, model.py:1016-1250):
     the block goes to a column the pack policy picks -- see _run_episode_pack.
+
+    ``pack_rnn`` (a tools.PackRNN): the global pack-net's loop instead (DRL_RNN.forward, model.py:749-852) -- see
+    _run_episode_rnn.
     """
+    if pack_rnn is not None:
+        if pack_policy is not None:
+            raise ValueError("pack_policy and pack_rnn select two different loops")
+        return _run_episode_rnn(static, dynamic, policy, pack_rnn, container_width, reward_type, heightmap_type,
+                                input_type, allow_rot, record, steps, bits=False if bits is None else bits, check=check)
     if pack_policy is not None:
         return _run_episode_pack(static, dynamic, policy, pack_policy, container_width, container_height, reward_type,
                                  heightmap_type, packing_strategy, input_type, allow_rot, env, record, steps,
@@ -260,6 +268,64 @@ def _run_episode_pack(static, dynamic, policy, pack_policy, container_width, con
         out['pack_logp'] = torch.cat(logps, dim=1)
     if record:
         out.update(features=feats, current_masks=curs, masks=msks, pnet_inputs=pins)
+    return out
+
+
+def _run_episode_rnn(static, dynamic, policy, net, container_width, reward_type, heightmap_type, input_type, allow_rot,
+                     record, steps, bits=False, check='nan'):
+    """DRL_RNN's decoding loop (model.py:749-852) minus its pointer network.  Per outer step t: ``policy`` -> ptr, the
+    precedence update (tap_mask_step), the gather of decoder_static (model.py:801-803), then ``net`` re-packs the whole
+    prefix of t + 1 chosen blocks from an empty container (model.py:809-811: t + 1 engine launches,
+    (n + 1) n / 2 in an episode), and decoder_dynamic is the engines' height-map in ``heightmap_type`` form after that
+    forward (model.py:814-826; (B, W', 1)).  Nothing is read back to the host inside the loop, so the episode can be
+    captured in a hipGraph.  Returns tour_idx (B, steps), reward = DRL_RNN's ``scores`` (the last forward's -rw, (B,)
+    float32), pack_logp = the last forward's hit_porb_log (B, steps), place_x (B, steps) int64 = the last forward's
+    columns, the engine (net's) [and with ``record`` the per-step decoder_dynamic as ``features``].  An episode
+    captured in a hipGraph writes that engine's state blob on every replay: the net keeps it alive
+    (net.captured_engines) even after a call with another batch size replaced net's current engine."""
+    if input_type in ('mul', 'mul-with'):
+        raise NotImplementedError("the pack-net loop of the two-container input types is not implemented")
+    D = int(static.shape[1]) - 1
+    if D != 2:
+        raise NotImplementedError("the global pack-net is 2D only (PackEngine's height-map is a row)")
+    if int(net.container_width) != int(container_width):
+        raise ValueError("the pack-net places into %d columns, the episode has %d" % (net.container_width, container_width))
+    n = int(dynamic.shape[-1]) // (math.factorial(D) if allow_rot else 1)
+    nsteps = n if steps is None else steps
+    dev = _lib.resolve_device(static.device)
+    masks = MaskStepper(static.to(dev), dynamic.to(dev), input_type, allow_rot, bits)
+    return rnn_loop(policy, masks, net, heightmap_type, nsteps, record, check)
+
+
+def rnn_loop(policy, masks, net, heightmap_type, nsteps, record=False, check='nan'):
+    """The body of _run_episode_rnn on a given precedence stepper ``masks`` (a MaskStepper, or any object with its
+    static / dynamic / current_mask / mask attributes and step(ptr)); the engine is ``net``'s own."""
+    B, D = int(masks.static.shape[0]), int(masks.static.shape[1]) - 1
+    dev = masks.static.device
+    engine = net.reserve(B, nsteps, dev)
+    static_part = masks.static[:, 1:, :]
+    W = int(net.container_width)
+    decoder_static = torch.zeros(B, D, 1, device=dev)
+    decoder_dynamic = torch.zeros(B, W - 1 if heightmap_type == 'diff' else W, 1, device=dev)
+    tour, all_blocks, feats = [], [], []
+    pack_logp = scores = positions = None
+    for step in range(nsteps):
+        ptr = policy(step=step, static=masks.static, dynamic=masks.dynamic, current_mask=masks.current_mask,
+                     mask=masks.mask, decoder_static=decoder_static, decoder_dynamic=decoder_dynamic).to(torch.int64)
+        masks.step(ptr)                                                                     # model.py:784-793
+        decoder_static = torch.gather(static_part, 2, ptr.view(-1, 1, 1).expand(-1, D, 1))  # model.py:801-803
+        all_blocks.append(decoder_static)
+        pack_blocks = torch.cat(all_blocks, dim=-1)                                         # model.py:810
+        positions, pack_logp, scores = net(pack_blocks, step + 1)                           # model.py:811
+        decoder_dynamic = engine.get_heightaps(heightmap_type)                              # model.py:816-826
+        tour.append(ptr.unsqueeze(1))
+        if record:
+            feats.append(decoder_dynamic)
+    out = {'tour_idx': torch.cat(tour, dim=1), 'reward': _flagged_reward(scores.detach(), check, engine),
+           'pack_logp': pack_logp, 'place_x': positions[:, :nsteps, 0].to(torch.int64), 'engine': engine,
+           'dynamic': masks.dynamic, 'mask': masks.mask}
+    if record:
+        out['features'] = feats
     return out
 
 

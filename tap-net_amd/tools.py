@@ -8,7 +8,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from . import _lib
-from .env import BatchedContainer, Container, LockstepError, lockstep_containers, lockstep_scope   # noqa: F401
+from .env import BatchedContainer, Container, LockstepError, PackEngines, lockstep_containers, lockstep_scope   # noqa: F401
 from .pack import reward as _reward            # noqa: F401
 
 
@@ -81,32 +81,208 @@ class DQN(nn.Module):
         return F.softmax(self.head(h), dim=1)
 
 
-# the reference's checkpoint paths, relative to its working directory (tools.py:3544-3553)
+class _EngineRow(object):
+    """net.engines[b] after a PackRNN forward: the reference's per-instance PackEngine, read-only (get_heightap)"""
+
+    def __init__(self, rows, b):
+        self._rows, self._b = rows, b
+
+    def get_heightap(self, heightmap_type):
+        """PackEngine.get_heightap (LG_RL.py:498-515): a float64 array of W (W - 1 for 'diff') entries"""
+        return self._rows.host(heightmap_type)[self._b].copy()
+
+
+class _EngineRows(object):
+    """The list the reference keeps in PackRNN.engines (LG_RL.py:610-614), served from the batched engine: the first
+    get_heightap of a forward reads every instance's map in one transfer, the others index it."""
+
+    def __init__(self, engine):
+        self._engine, self._host = engine, {}
+
+    def host(self, heightmap_type):
+        if heightmap_type not in self._host:
+            t = self._engine.get_heightaps(heightmap_type)
+            self._host[heightmap_type] = t.detach().cpu().numpy().astype(np.float64)[:, :, 0]
+        return self._host[heightmap_type]
+
+    def __len__(self):
+        return self._engine.batch_size
+
+    def __getitem__(self, b):
+        if not -len(self) <= b < len(self):
+            raise IndexError("list index out of range")
+        return _EngineRow(self, b % len(self))
+
+
+class PackRNN(nn.Module):
+    """The global pack-net (pack_net/LG_RL.py: PackRNN, LG_RL.py:562-675): 'G' (reward type C+P+S-G-soft) or 'LG'
+    (C+P+S-LG-soft), what the reference's DRL_RNN (model.py:749-852) and tools.calc_positions_LG_net run.  Stock PyTorch
+    with the reference's constructor, parameter names and shapes, so its checkpoints load with strict=True; forward runs
+    the same torch ops in the same order.  Its environment, the reference's per-instance PackEngine, is an injected
+    batched engine: ``engine`` is a factory engine(B, W, H, T, heightmap_type, max_blocks_num, device) -> an object with
+    PackEngines' surface (step, reward, positions, get_heightaps); the default is env.PackEngines, one HIP launch per
+    inner step for the whole batch and no host read.
+
+    forward(blocks (B, 2, T), blocks_num) -> positions (B, T, 2) int32 (x after the clamp, z; zero beyond blocks_num),
+    hit_porb_log (B, blocks_num), -reward (B,) float32 of the last inner step.  Afterwards ``engines[b].get_heightap``
+    answers like the reference's engines (one batched read per forward)."""
+
+    def __init__(self, block_input_size, block_hidden_size, height_input_size, height_hidden_size, container_width,
+                 container_height, heightmap_type, max_blocks_num=10, pack_net_type='LG', engine=None):
+        super(PackRNN, self).__init__()
+        if pack_net_type == 'LG':
+            decoder_hidden_size = block_hidden_size + block_hidden_size + height_hidden_size    # local + global
+        else:
+            decoder_hidden_size = block_hidden_size + height_hidden_size                        # global
+        self.encoder = nn.GRU(block_hidden_size, block_hidden_size, batch_first=True)
+        self.decoder = nn.GRU(decoder_hidden_size, decoder_hidden_size, batch_first=True)
+        if heightmap_type == 'diff':
+            self.height_map_conv = nn.Conv1d(height_input_size - 1, height_hidden_size, kernel_size=1)
+        else:
+            self.height_map_conv = nn.Conv1d(height_input_size, height_hidden_size, kernel_size=1)
+        self.block_conv = nn.Conv1d(block_input_size, block_hidden_size, kernel_size=1)
+        self.fc = nn.Sequential(
+            nn.Linear(decoder_hidden_size, decoder_hidden_size),
+            nn.ReLU(),
+            nn.Linear(decoder_hidden_size, container_width),
+            nn.Softmax(dim=1)
+        )
+        self.container_width = container_width
+        self.container_height = container_height
+        self.max_blocks_num = max_blocks_num
+        self.dropout = nn.Dropout(p=0.1)
+        self.heightmap_type = heightmap_type
+        self.engines = None
+        self.pack_net_type = pack_net_type
+        self.engine_factory = PackEngines if engine is None else engine
+        self._engine = None
+        self.captured_engines = []
+
+    def reserve(self, batch_size, T, device):
+        """the engine for ``batch_size`` instances of up to ``T`` blocks on ``device`` (built or grown when needed;
+        a caller that knows the longest sequence sizes it once -- DRL_RNN's prefixes grow by one block per step, so a
+        grown tape doubles, up to the descriptor's limit of _TAPE_MAX steps).  Replacing the engine drops the net's
+        reference to the old one; an engine that a forward used under hipGraph capture stays referenced by the net
+        (``captured_engines``), because replaying that graph writes into its state blob."""
+        e, dev = self._engine, torch.device(device)
+        if e is not None and e.batch_size == batch_size and e.T >= T and torch.device(e.device) == dev:
+            return e
+        cap = T if e is None or e.batch_size != batch_size else max(T, min(2 * e.T, _TAPE_MAX))
+        self._engine = self.engine_factory(batch_size, self.container_width, self.container_height, cap,
+                                           self.heightmap_type, self.max_blocks_num, dev)
+        return self._engine
+
+    def forward(self, blocks, blocks_num):
+        """blocks: batch_size x block-dim x blocks-num (LG_RL.py:603-675)"""
+        batch_size = blocks.shape[0]
+        blocks_num = int(blocks_num)
+        engine = self.reserve(batch_size, blocks.shape[-1], blocks.device)   # step 0 clears (LG_RL.py:610-614)
+        if blocks.is_cuda and torch.cuda.is_current_stream_capturing() and \
+                not any(c is engine for c in self.captured_engines):
+            self.captured_engines.append(engine)            # the graph's launches write its blob: keep it alive
+
+        block_vec = self.block_conv(blocks)
+        encode_rnn_out, encoder_last_hh = self.encoder(block_vec.transpose(2, 1), None)
+        encoder_last_hh = self.dropout(encoder_last_hh)
+        encoder_last_hh = encoder_last_hh.squeeze(0).unsqueeze(-1)
+
+        width = self.container_width - (1 if self.heightmap_type == 'diff' else 0)
+        height_map = torch.zeros(batch_size, width, 1, dtype=torch.float32, device=blocks.device)   # :627, :633-639
+        hit_porb_log = []
+        last_hh = None
+        for block_index in range(blocks_num):
+            height_vec = self.height_map_conv(height_map)
+            if self.pack_net_type == 'LG':
+                decoder_vec = torch.cat((encoder_last_hh, block_vec[:, :, block_index:block_index + 1], height_vec), dim=1)
+            else:
+                decoder_vec = torch.cat((encoder_last_hh, height_vec), dim=1)
+            rnn_out, last_hh = self.decoder(decoder_vec.transpose(2, 1), last_hh)
+            hit_map = self.fc(last_hh[0].squeeze(1))
+            best = hit_map.max(1)                       # log(max) and the first argmax (:654, :659) in one op
+            hit_porb_log.append(torch.log(best[0]).unsqueeze(1))
+            height_map = engine.step(block_index, blocks.detach(), best[1], want_reward=block_index == blocks_num - 1)
+
+        positions = engine.positions[:, :blocks.shape[-1]]
+        if blocks_num < positions.shape[1]:
+            positions[:, blocks_num:] = 0
+        self.engines = _EngineRows(engine)
+        hit_porb_log = torch.cat(hit_porb_log, dim=1)
+        return positions, hit_porb_log, -engine.reward
+
+
+# the reference's checkpoint paths, relative to its working directory (tools.py:3544-3553, 3488-3500)
 PACK_NET_CHECKPOINTS = {'C+P+S-SL-soft': './pack_net/SL_rand_diff/checkpoints/199/SL.pt',
-                        'C+P+S-RL-soft': './pack_net/RL_rand_diff/checkpoints/199/actor.pt'}
+                        'C+P+S-RL-soft': './pack_net/RL_rand_diff/checkpoints/199/actor.pt',
+                        'C+P+S-G-soft': './pack_net/G_rand_diff/checkpoints/199/actor.pt',
+                        'C+P+S-G-gt-soft': './pack_net/G_rand_diff/checkpoints/199/actor.pt',
+                        'C+P+S-LG-soft': './pack_net/LG_rand_diff/checkpoints/199/actor.pt',
+                        'C+P+S-LG-gt-soft': './pack_net/LG_rand_diff/checkpoints/199/actor.pt'}
+# the global pack-net's types (tools.calc_positions_LG_net, tools.py:3463-3504)
+PACK_RNN_TYPES = {'C+P+S-G-soft': 'G', 'C+P+S-G-gt-soft': 'G', 'C+P+S-LG-soft': 'LG', 'C+P+S-LG-gt-soft': 'LG'}
+# PackRNN's container height when the caller gives none: the descriptor's limit (only error bit 1 depends on it)
+_PACK_RNN_H = 4000
+# the longest tape a descriptor takes (env.hip: tap_desc_validate, n_max <= 4096)
+_TAPE_MAX = 4096
 
 
-def load_pack_net(reward_type, container_width, device='cuda'):
-    """DQN(W, True) in eval mode with the checkpoint tools.calc_positions_net loads for ``reward_type``."""
+def load_pack_net(reward_type, container_width, device='cuda', container_height=None):
+    """The network tools.calc_positions_net loads for ``reward_type``, in eval mode with the reference's checkpoint:
+    DQN(W, True) for the SL / RL types, PackRNN(2, 128, W, 128, W, H, 'diff', pack_net_type='G' | 'LG') for the G / LG
+    types (tools.py:3488-3500).  The LG checkpoint is not shipped: FileNotFoundError, as the reference's torch.load.
+    ``device=None`` leaves the network on the host.  A host PackRNN fed host blocks then needs a host engine
+    injected (``net.engine_factory``): the default engine, env.PackEngines, has no CPU path and raises TapError."""
     if reward_type not in PACK_NET_CHECKPOINTS:
-        raise NotImplementedError("the %s pack-net (calc_positions_LG_net) is outside this package" % reward_type)
-    net = DQN(int(container_width), True)
+        raise NotImplementedError("%s has no pack-net (tools.calc_positions_net)" % reward_type)
+    W = int(container_width)
+    if reward_type in PACK_RNN_TYPES:
+        H = _PACK_RNN_H if container_height is None else int(container_height)
+        net = PackRNN(2, 128, W, 128, W, H, 'diff', pack_net_type=PACK_RNN_TYPES[reward_type])
+    else:
+        net = DQN(W, True)
     path = PACK_NET_CHECKPOINTS[reward_type]
     if not os.path.exists(path):
-        raise FileNotFoundError("%s: the %s pack-net checkpoint (tools.py:3544-3553 loads it relative to the working "
+        raise FileNotFoundError("%s: the %s pack-net checkpoint (tools.py:3488-3553 loads it relative to the working "
                                 "directory); pass net= instead" % (path, reward_type))
     net.load_state_dict(torch.load(path, map_location='cpu'))
-    return net.to(_lib.resolve_device(device)).eval()
+    return (net if device is None else net.to(_lib.resolve_device(device))).eval()
+
+
+def calc_positions_LG_net(blocks, container_size, reward_type, net=None, device='cuda'):
+    """tools.calc_positions_LG_net (tools.py:3463-3504) for one instance, G / LG types: one PackRNN forward (its engine
+    wraps every max_blocks_num blocks) picks the columns, then LG_RL.calc_positions replays them into a fresh
+    container without a wrap (LG_RL.py:678-744) and scores the replay.
+    -> positions (n, 2), container=None, stable [n] bool, ratio = (C+P+S)/3, scores = [valid, box, empty, stable_num,
+    max_h].  ``net=None`` loads the reference's checkpoint (load_pack_net)."""
+    from .pack import episode_scores_rnn
+    if reward_type not in PACK_RNN_TYPES:
+        raise NotImplementedError("%s is not a global pack-net type (calc_positions_LG_net)" % reward_type)
+    blocks = np.asarray(blocks).astype('int')
+    n, D = blocks.shape
+    if D != 2:
+        raise NotImplementedError("calc_positions_LG_net is 2D (PackEngine's height-map is a row)")
+    dev = _lib.resolve_device(device)
+    if net is None:
+        net = load_pack_net(reward_type, container_size[0], dev, container_size[1])
+    static = torch.zeros(1, 3, n, dtype=torch.float32)
+    static[0, 1:, :] = torch.as_tensor(blocks.T.astype(np.float32))
+    tour = torch.arange(n, dtype=torch.int64).unsqueeze(0)
+    ratio, scores, env = episode_scores_rnn(static.to(dev), tour.to(dev), list(container_size), net, allow_rot=False,
+                                            with_env=True)
+    return (env.positions[0].cpu().numpy().astype(int), None, [bool(v) for v in env.stable[0].tolist()],
+            float(ratio[0].item()), [int(v) for v in scores[0].tolist()])
 
 
 def calc_positions_net(blocks, container_size, reward_type, net=None, device='cuda'):
-    """tools.calc_positions_net (tools.py:3506-3598) for one instance, SL / RL types: the pack-net picks every block's
+    """tools.calc_positions_net (tools.py:3506-3598) for one instance.  G / LG types go to calc_positions_LG_net, as in
+    the reference.  SL / RL types: the pack-net picks every block's
     column from the raw height-map, the placement is tools.calc_one_position_net's (tapenv.h: TAP_AT_NET).
     -> positions (n, 2), container=None, stable [n] bool, ratio = (C+P+S)/3,
     scores = [valid, box, empty, stable_num, max_h].  ``net=None`` loads the reference's checkpoint."""
     from .pack import episode_scores_net
+    if reward_type in PACK_RNN_TYPES:                                                   # tools.py:3528-3532
+        return calc_positions_LG_net(blocks, container_size, reward_type, net=net, device=device)
     if reward_type not in PACK_NET_CHECKPOINTS:
-        raise NotImplementedError("the %s pack-net (calc_positions_LG_net) is outside this package" % reward_type)
+        raise NotImplementedError("%s has no pack-net (tools.calc_positions_net)" % reward_type)
     blocks = np.asarray(blocks).astype('int')
     n, D = blocks.shape
     if D != 2:
