@@ -5,7 +5,7 @@
     at once): per-launch time, inside a hipGraph of whole passes as bench.py times them, of
       empty      every wave returns at entry ("empty kernel of the geometry": grid, workgroup size, LDS, kernarg)
       place      placement waves only
-      mask       stream waves only (update_dynamic + update_mask on the bit shadow)
+      mask       stream waves only (update_dynamic + update_mask on the bit shadow; with the 2D step's mask wave)
       fused      the product step
       fused_inplace   the same with ONE fp32 output buffer for every step instead of two alternating ones
 (2) TIMELINE (-DTAP_PROF build: clock stamps, see tap_masks.h): when, relative to the first wave's entry, the waves
@@ -139,7 +139,10 @@ def run_timeline(shape):
                 nwg = int(used.any(1).sum())
                 env_waves = 1 if S["D"] == 2 else 4             # TransGeom: 8 envs x G lanes / 64 (G = 8 at W = 5, 32 at 5 x 5)
                 place = used & (np.arange(WAVES)[None, :] < env_waves)
-                stream = used & ~place
+                # the 2D step's mask wave (tap_transition.h: trans_mask_wave) sits behind the four stream waves; its stamps:
+                # entry, inputs arrived, last store issued, stores acknowledged
+                maskw = used & (np.arange(WAVES)[None, :] == env_waves + 4) if S["D"] == 2 else np.zeros_like(used)
+                stream = used & ~place & ~maskw
                 def q(m, i):
                     v = rel[:, :, i][m]
                     return dict(min=round(float(v.min()), 2), p50=round(float(np.median(v)), 2), p90=round(float(np.percentile(v, 90)), 2),
@@ -155,6 +158,9 @@ def run_timeline(shape):
                                                      last_store_issued=q(stream, 2), stores_acknowledged=q(stream, 3)),
                                          placement=dict(entry=q(place, 0), state_and_block_loaded=q(place, 1),
                                                         placement_decided=q(place, 2), results_stored=q(place, 3)))
+                if maskw.any():
+                    out["step%d" % t]["mask_wave"] = dict(entry=q(maskw, 0), inputs_arrived=q(maskw, 1), last_store_issued=q(maskw, 2),
+                                                          stores_acknowledged=q(maskw, 3))
     out["how"] = ("us since the first wave's entry ON THE SAME XCD (s_memrealtime, 100 MHz: 0.01 us steps; the counters of the eight "
                   "XCDs are not aligned with each other), over all waves of one eager launch; "
                   "the stamps add an s_waitcnt vmcnt(0) before the first store, so the launch is ~0.3 us slower than the product's")

@@ -484,11 +484,14 @@ __device__ __forceinline__ int tap_mod_small(int v, int n)     // v mod n for v 
 // FULL: every input is there (ptr, static, mask_in) and every slab of every wave is an env (B is a multiple of the envs per
 // workgroup) -- the launcher checks; the wave then carries no code for the absent cases (the initial mask, a stepper's
 // first step, the ragged last workgroup): ~40 of its ~550 instructions
-template <int NS, int NC, bool BUILD = false, bool MERGED = true, int C4S = 0, bool INPLACE = false, bool FULL = false>
+// NOMASK: update_dynamic only -- the workgroup's mask wave (mask_wave_bits, below) runs update_mask for all its envs, so
+// this wave loads neither the old mask nor the shadow in the per-column layout and ends with its shadow stores
+template <int NS, int NC, bool BUILD = false, bool MERGED = true, int C4S = 0, bool INPLACE = false, bool FULL = false, bool NOMASK = false>
 __device__ __forceinline__ void stream_wave_bits_r4(const MaskArgs &a, int senv0, int lane, const bool (&on_)[NS],
                                                  float *lds = nullptr)
 {
     static_assert(!(BUILD && INPLACE), "the first step on a fresh tensor writes all of it");
+    static_assert(!NOMASK || (FULL && !BUILD && C4S != 0), "the mask wave exists beside the FULL step on a compiled-in shape only");
     bool on[NS];
 #pragma unroll
     for (int k = 0; k < NS; ++k) on[k] = FULL ? true : on_[k];
@@ -549,7 +552,7 @@ __device__ __forceinline__ void stream_wave_bits_r4(const MaskArgs &a, int senv0
         for (int c = 0; c < NC; ++c) {
             const unsigned j = (unsigned)min(lane + 64 * c, nR - 1);
             row0[k][c] = strow[has_static ? j : 0u];
-            keep[k][c] = mirow[has_mask ? j : 0u];
+            if constexpr (!NOMASK) keep[k][c] = mirow[has_mask ? j : 0u];
         }
     }
 #ifdef TAP_STREAM_G2          // A/B builds: the shadow words requested only after the small inputs have arrived (round 3's order)
@@ -562,7 +565,7 @@ __device__ __forceinline__ void stream_wave_bits_r4(const MaskArgs &a, int senv0
             const unsigned long long *brow = a.bits_in + (size_t)env * nR;
             // (BJ_X: the compiled-in 10-node windows take a column's word from the lane that holds its quad, after the
             //  clear -- below -- instead of loading the shadow a second time in the per-column layout)
-            if constexpr (!BJ_X) {
+            if constexpr (!BJ_X && !NOMASK) {
 #pragma unroll
                 for (int c = 0; c < NC; ++c) bj[k][c] = brow[(unsigned)min(lane + 64 * c, nR - 1)];
             }
@@ -793,6 +796,7 @@ __device__ __forceinline__ void stream_wave_bits_r4(const MaskArgs &a, int senv0
             }
         }
     }
+    if constexpr (NOMASK) return;                         // update_mask: the workgroup's mask wave
     unsigned nbx[NS];                                     // BJ_X: column `lane`'s new word, from the lane that holds its quad
     if constexpr (BJ_X) {
         const int jj = min(lane, nR - 1);
@@ -947,14 +951,76 @@ __device__ __forceinline__ void stream_wave_bits_r3(const MaskArgs &a, int senv0
 }
 
 #endif
-template <int NS, int NC, bool BUILD = false, bool MERGED = true, int C4S = 0, bool INPLACE = false, bool FULL = false>
+template <int NS, int NC, bool BUILD = false, bool MERGED = true, int C4S = 0, bool INPLACE = false, bool FULL = false, bool NOMASK = false>
 __device__ __forceinline__ void stream_wave_bits(const MaskArgs &a, int senv0, int lane, const bool (&on)[NS], float *lds = nullptr)
 {
 #ifdef TAP_STREAM_R3
+    static_assert(!NOMASK, "the round-3 stream wave always carries update_mask");
     stream_wave_bits_r3<NS, NC, BUILD>(a, senv0, lane, on, lds);
 #else
-    stream_wave_bits_r4<NS, NC, BUILD, MERGED, C4S, INPLACE, FULL>(a, senv0, lane, on, lds);
+    stream_wave_bits_r4<NS, NC, BUILD, MERGED, C4S, INPLACE, FULL, NOMASK>(a, senv0, lane, on, lds);
 #endif
+}
+
+// ---- the mask wave of the fused 2D step: update_mask (pack.py:314-329) for ALL the envs of a workgroup ------------------
+// Beside NOMASK stream waves (FULL steps on the compiled-in 2D window: 30 rows, nR = 20).  A workgroup's EPB envs own
+// EPB * nR consecutive floats of mask_in / mask_out / current_out and as many consecutive shadow words, so lane
+// (env, column quad) = lane / C4S, lane % C4S reads the float4 and the four words number `lane` of those runs: three
+// 16-byte loads and two 16-byte stores per wave where the stream waves issued 16 narrow loads and 16 narrow stores per
+// workgroup, behind their own expansion.  The pick is the placement waves' dependent gather (ptr, then row 0 of static
+// at ptr): the wave has nothing else to wait for, and it reads the launch's inputs only -- no hand-over from another wave.
+// Every load is issued before the first store, lanes store mask_out before current_out, and a lane writes the elements it
+// read: mask_in, mask_out and current_out may be one buffer, as in the stream wave's tail.  Only dyn_* and bits_* are
+// promised 16-byte aligned (mask_bits_ok): the three mask buffers are accessed as float4 DECLARED 4-byte aligned, which
+// the compiler emits as one dwordx4 where the target's unaligned access mode allows it (gfx950 under HSA) and splits
+// where not.  `ptr` is requested first: the wave's memory counter retires in order, so the dependent read of row 0 waits
+// for that one load and leaves with the other three still in flight.
+typedef float tap_f4u __attribute__((ext_vector_type(4), aligned(4)));
+template <int EPB, int C4S>
+__device__ __forceinline__ void mask_wave_bits(const MaskArgs &a, int env0, int lane)
+{
+    static_assert(C4S == 5 && EPB * C4S <= 64, "one lane per (env, column quad) of the 10-node 2D window");
+    constexpr int nR = 4 * C4S, n = 10, rows = 30;
+    TL_STAMP(0);
+    if (lane >= EPB * C4S) return;
+    const int e = lane / C4S, q = lane - e * C4S;
+    const int env = env0 + e;
+    const long praw = (long)a.ptr[env];
+    const tap_f4u keep = *reinterpret_cast<const tap_f4u *>(a.mask_in + (size_t)env0 * nR + lane * 4);
+    const ulonglong2 *wsrc = reinterpret_cast<const ulonglong2 *>(a.bits_in + (size_t)env0 * nR) + lane * 2;
+    const ulonglong2 w0 = wsrc[0], w1 = wsrc[1];
+    const bool valid = praw >= 0 && praw < nR;           // an index outside [0, nR) clears nothing and removes no column
+    const int p = valid ? (int)praw : 0;
+    const float r0v = a.static_[(size_t)env * a.static_rows * nR + p];        // pack.py:339
+    const float r0 = valid ? r0v : -1.f;
+    const int real = (r0 > -1.f && r0 < (float)rows) ? (int)r0 : -1;          // .long() truncates; a row beyond the tensor clears nothing
+    unsigned clr = 0;                                                         // pack.py:370-374 (30 rows: the low word carries every row)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const int r = real + n * i;
+        if (real >= 0 && r < rows) clr |= 1u << r;
+    }
+    const int pm = valid ? (int)((unsigned)p % (unsigned)n) : -1;             // pack.py:314-316; -1 matches no column
+    const unsigned nmask = (1u << n) - 1u;
+    const unsigned word[4] = {(unsigned)w0.x, (unsigned)w0.y, (unsigned)w1.x, (unsigned)w1.y};
+    tap_f4u kp, cur;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int j = q * 4 + c, jm = j >= n ? j - n : j;                     // nR = 2 n
+        const unsigned nb = word[c] & ~clr;
+        const int move = __popc(nb & nmask), small = __popc((nb >> n) & nmask), large = __popc((nb >> (2 * n)) & nmask);
+        kp[c] = (jm == pm) ? 0.f : keep[c];                                   // pack.py:320-321
+        cur[c] = (small * large + move) != 0 ? 0.f : kp[c];                   // :327-329
+    }
+#ifdef TAP_PROF
+    TL_WAIT_VM();                                        // (timeline builds: "inputs have arrived")
+    TL_STAMP(1);
+#endif
+    *reinterpret_cast<tap_f4u *>(a.mask_out + (size_t)env0 * nR + lane * 4) = kp;
+    *reinterpret_cast<tap_f4u *>(a.cur_out + (size_t)env0 * nR + lane * 4) = cur;
+    TL_STAMP(2);
+    TL_WAIT_VM();
+    TL_STAMP(3);
 }
 
 // ---- the bit shadow with TWO words per column: 65 <= rows <= 128 (windows of 22 .. 42 nodes) -------------

@@ -20,7 +20,8 @@ struct TransArgs {
 // ---- a stream wave: out-of-place copy of SPW consecutive slabs with the chosen rows cleared
 //      (pack.py:370-374), then the column sums + both masks (pack.py:318-329)
 // MODE: the bits of tap_stream_variant.h (TAP_MODE_*), chosen by tap_stream_variant()
-template <int SPW, int NC, int MODE_>
+// NOMASK: update_dynamic only; the workgroup has a mask wave (trans_mask_wave below, tap_masks.h: mask_wave_bits)
+template <int SPW, int NC, int MODE_, bool NOMASK = false>
 __device__ __forceinline__ void trans_stream_wave(const MaskArgs &m, int senv0, int lane, float *lds)
 {
     constexpr int MODE = MODE_ & 3;
@@ -34,7 +35,7 @@ __device__ __forceinline__ void trans_stream_wave(const MaskArgs &m, int senv0, 
     for (int k = 0; k < SPW; ++k) on[k] = senv0 + k < m.B;
     TL_STAMP(0);
     if (NC > 0) {
-        if (MODE == 1) stream_wave_bits<SPW, (NC > 0 ? NC : 1), false, MERGED, C4S, INPLACE, FULL>(m, senv0, lane, on, lds);
+        if (MODE == 1) stream_wave_bits<SPW, (NC > 0 ? NC : 1), false, MERGED, C4S, INPLACE, FULL, NOMASK>(m, senv0, lane, on, lds);
         else if (MODE == 2) stream_wave_bits<SPW, (NC > 0 ? NC : 1), true, MERGED, C4S>(m, senv0, lane, on, lds);
         else stream_wave_fast<SPW, (NC > 2 ? 4 : 6), (NC > 0 ? NC : 1)>(m, senv0, lane, on, lds);
         TL_STAMP(2);
@@ -71,4 +72,23 @@ template <int G, int SW> struct TransGeom {
     static constexpr int SPW = EPB / STREAM_WAVES;  // slabs per stream wave
     static constexpr int THREADS = 64 * (ENV_WAVES + STREAM_WAVES);
 };
+
+// The LB_GREEDY step's instantiation for the reference's 2D window in its common form -- on the shadow, run-of-rows
+// expansion (write-through launches), every input given, whole workgroups: MODE = 1 | MERGED | C4_5 | FULL -- with two
+// slabs per stream wave (G = 8, 16, 32) has a THIRD kind of wave: one mask wave per workgroup runs update_mask for all
+// its envs and the stream waves keep update_dynamic.  At the BASELINE batch every wave of the launch is resident at once
+// and the last stream wave to finish ends the launch; update_mask was four narrow loads, ~100 instructions and four
+// narrow stores at that wave's tail, on 20 of its 64 lanes.  The three kinds exchange nothing.
+template <int D, int G, int NC, int SW, int MODE> constexpr bool trans_mask_wave()
+{
+#ifdef TAP_NO_MASK_WAVE                                       // A/B builds: update_mask in the stream waves' tail everywhere
+    return false;
+#else
+    return D == 2 && NC == 1 && TransGeom<G, SW>::SPW == 2 && MODE == (1 | TAP_MODE_MERGED | TAP_MODE_C4_5 | TAP_MODE_FULL);
+#endif
+}
+template <int D, int G, int NC, int SW, int MODE> constexpr int trans_threads()
+{
+    return TransGeom<G, SW>::THREADS + (trans_mask_wave<D, G, NC, SW, MODE>() ? 64 : 0);
+}
 

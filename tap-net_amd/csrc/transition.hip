@@ -14,6 +14,8 @@
 // two kinds never exchange data, so there is no s_barrier: lane groups never span a wave and LDS
 // hand-offs only need compiler ordering.  (A first version that let the same waves stream and then
 // place showed no gain: every workgroup was in the same phase at the same time.)
+// The common 2D step (the reference's window on the shadow, whole workgroups) has a third kind: one mask wave per
+// workgroup runs update_mask for all its envs, off the stream waves' tail (tap_transition.h: trans_mask_wave).
 // This file: the LB_GREEDY kernel and the tap_transition* entry points; the MACS / MUL kernels of the same shape live in
 // transition_macs.hip (tap_transition_macs_launch), so that the two halves compile side by side.
 #include <cstdlib>
@@ -30,10 +32,11 @@
 // (TAP_MASK_HOT_PARAMS, tap_masks.h: the load addresses of the stream waves -- and of the placement waves' gather, which
 //  reads the same `ptr` and `static` -- arrive in SGPRs with the wave)
 template <int D, int G, int NC, int SW, int MODE>
-__global__ void __launch_bounds__((TransGeom<G, SW>::THREADS)) k_transition(TAP_MASK_HOT_PARAMS, TransArgs a)
+__global__ void __launch_bounds__((trans_threads<D, G, NC, SW, MODE>())) k_transition(TAP_MASK_HOT_PARAMS, TransArgs a)
 {
     using Geo = TransGeom<G, SW>;
     constexpr int EPB = Geo::EPB, SPW = Geo::SPW, ENV_WAVES = Geo::ENV_WAVES;
+    constexpr bool MASKW = trans_mask_wave<D, G, NC, SW, MODE>();   // one more wave, behind the stream waves: update_mask
     extern __shared__ float trans_lds[];
     __shared__ int s_old[64 * ENV_WAVES];
     __shared__ int s_new[64 * ENV_WAVES];
@@ -59,8 +62,14 @@ __global__ void __launch_bounds__((TransGeom<G, SW>::THREADS)) k_transition(TAP_
         __builtin_amdgcn_s_setprio(TAP_STREAM_PRIO);
 #endif
         const MaskArgs m = tap_mask_hot(a.m, (MODE & 3) == 1, TAP_MASK_HOT_NAMES);
-        trans_stream_wave<SPW, NC, MODE>(m, env_base + (wave - ENV_WAVES) * SPW, lane,
-                                     trans_lds + (size_t)(wave - ENV_WAVES) * SPW * 3 * h_nR);
+        if constexpr (MASKW) {
+            if (wave == ENV_WAVES + Geo::STREAM_WAVES) {     // at the stream waves' priority (raised ones starve the placement chain)
+                mask_wave_bits<EPB, 5>(m, env_base, lane);
+                return;
+            }
+        }
+        trans_stream_wave<SPW, NC, MODE, MASKW>(m, env_base + (wave - ENV_WAVES) * SPW, lane,
+                                            trans_lds + (size_t)(wave - ENV_WAVES) * SPW * 3 * h_nR);
         return;
     }
 
@@ -136,14 +145,14 @@ int tap_macs_validate(tap_ctx *ctx, const tap_env_desc &d);                     
 template <int D, int G, int SW>
 static int launch_transition_v(tap_ctx *ctx, const TransArgs &a, hipStream_t st)
 {
-    constexpr int EPB = TransGeom<G, SW>::EPB, THREADS = TransGeom<G, SW>::THREADS;
+    constexpr int EPB = TransGeom<G, SW>::EPB;
     const int grid = (a.s.d.B + EPB - 1) / EPB;
     if (grid == 0) return TAP_OK;
     const size_t lds = (size_t)EPB * 3 * a.m.nR * sizeof(float);
     const TapVariant v = tap_stream_variant(TAP_SV_TRANSITION, tap_mask_facts(a.m), TapLaunchFacts{D, G, EPB, a.s.d.B, 0, 0, false});
     return tap_launch_variant<TAP_SV_TRANSITION, D, G>(ctx, "k_transition", v, a.m.wt, [&](auto k) -> int {
         using K = decltype(k);
-        hipLaunchKernelGGL((k_transition<D, G, K::nc, SW, K::mode>), dim3(grid), dim3(THREADS), K::nc ? lds : 0, st,
+        hipLaunchKernelGGL((k_transition<D, G, K::nc, SW, K::mode>), dim3(grid), dim3(trans_threads<D, G, K::nc, SW, K::mode>()), K::nc ? lds : 0, st,
                            TAP_MASK_HOT_ARGS(a.m), a);
         return TAP_OK;
     });
