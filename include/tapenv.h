@@ -104,7 +104,7 @@ const char *tap_last_error(const tap_ctx *ctx);
  * hipGraph counts once, at capture.  tap_variant_hits writes up to `cap` rows of 8 ints (the key, then the count) and
  * returns the number of rows the record holds (TAP_E_INVALID if a key found no slot since the last reset);
  * tap_variant_hits_reset empties it. */
-/* The whole-episode and rolling kernels count on the same record, under kinds 16 .. 22 (tap_common.h: TapHitKind), after
+/* The whole-episode and rolling kernels count on the same record, under kinds 16 .. 24 (tap_common.h: TapHitKind), after
  * the stream-wave kinds 0 .. 6.  Their keys, fields (kind, D, G, nc, mode, extra, wt):
  *   16 k_episode<D, G, SOFT>                      (16, D, G, SOFT, 0, 0, 0)
  *   17 k_episode_macs2<G, WIDE>                   (17, 2, G, WIDE, 0, 0, 0)
@@ -117,6 +117,8 @@ const char *tap_last_error(const tap_ctx *ctx);
  *      k_rolling_init_big<D, MW>                  (21, D, 0, 1, 0, MW, 0)
  *   22 k_place_at<G, NET, ENG>                    (22, 2, G, SEM, GATHER, ENG, 0)  SEM a TAP_AT_*, GATHER 1 = _gather,
  *                                                 ENG 1 = tap_env_step_engine
+ *   23 k_macs2d_wave_episode                      (23, 2, 64, 0, 0, PW, 0)       PW wavefronts (containers) per workgroup
+ *   24 k_macs3d_wave_episode / _tight             (24, 3, 64, 0, TIGHT, PW, 0)   TIGHT 1 = the register-tight build (macs3_big.hip)
  * wt is the launch's RollArgs::wt (the window's fp32 stores; the init kernels store none), 0 for the episode kernels. */
 int tap_variant_hits(tap_ctx *ctx, int32_t *out, int cap);
 int tap_variant_hits_reset(tap_ctx *ctx);
@@ -252,7 +254,8 @@ int tap_env_check(tap_ctx *ctx, const tap_env_desc *d, const void *state, int32_
 /* pack.reward (pack.py:378-473) == tools.calc_positions_lb_greedy (tools.py:2393-2449) per env:
  * the whole episode in one launch.  static_ (B, static_rows, nR) f32, tour (B, n) int64,
  * reward_out (B,) f32 = -(C+P+S) un-normalised; positions_out (B, n, D) i32 and stable_out
- * (B, n) u8 nullable.  d->B is ignored (B given here); no state blob is needed. */
+ * (B, n) u8 nullable.  d->B is ignored (B given here); no state blob is needed.  LB_GREEDY only (pack.py:431 names a
+ * function the reference does not have for MACS / MUL: TAP_E_UNSUPPORTED; tap_episode_scores packs with them). */
 int tap_episode_reward(tap_ctx *ctx, const tap_env_desc *d, int B, int n, const float *static_,
                        int static_rows, int nR, const int64_t *tour, float *reward_out,
                        int32_t *positions_out, uint8_t *stable_out, void *stream);
@@ -260,7 +263,11 @@ int tap_episode_reward(tap_ctx *ctx, const tap_env_desc *d, int B, int n, const 
 /* tools.calc_positions_lb_greedy (tools.py:2393-2449) / tools.calc_positions_mcs (tools.py:3213-3315) per env,
  * as pack.render calls them for its metric files (pack.py:743-792; caller trainer.py:132, 493): the whole
  * episode in one launch with every strategy tap_env_step has except the legacy 'LB' (render never uses it,
- * pack.py:741), containers up to 64 cells.  static_ / tour as tap_episode_reward.
+ * pack.py:741), containers of every size the step entry points take: lane-per-cell groups up to 64 cells, above that
+ * (2D: above 64 columns; 3D: above 64 cells or a side above 8) one wavefront per container with its tile in LDS across
+ * the n placements (LB_GREEDY: big.hip; MACS / MUL: macs_big.hip k_macs2d_wave_episode, macs3_big.hip
+ * k_macs3d_wave_episode).  TAP_E_UNSUPPORTED only where that tile does not fit a workgroup's LDS or under
+ * TAP_NO_WAVE_KERNELS: step those with tap_env_step_gather.  static_ / tour as tap_episode_reward.
  *   target_sel   -1: every tour entry.  0 | 1: the two-container input types ('mul', 'mul-with', pack.py:755-790):
  *                only the entries whose target id -- the LAST row of static_ -- equals it, in tour order.
  *   ratio64_out  (B,) f64: the function's `ratio` (tools.py:2442-2445 C+P+S; tools.py:3279-3308 by reward type,
@@ -285,9 +292,12 @@ int tap_episode_scores(tap_ctx *ctx, const tap_env_desc *d, int B, int n, const 
  * (tools.py:3213-3315).  LB_GREEDY containers of any size (generate.py:908 accepts any --initial_container_width):
  * lane-per-cell groups up to 64 cells, above that one wavefront per container with the height-map in LDS across the n
  * placements (big.hip: k_big_wave_episode; above 4096 cells one workgroup per container, k_big_wg_episode, up to
- * 16384; tap_episode_reward / tap_episode_scores take the same path); MACS / MUL
- * above 64 cells: TAP_E_UNSUPPORTED, step them with tap_env_step_gather.  reward_out (B,) f32 = -(C+P+S), positions_out
- * (B, n, D) i32, stable_out (B, n) u8, score64_out (B,) f64 = C+P+S -- each nullable.
+ * 16384; tap_episode_reward / tap_episode_scores take the same path); MACS / MUL above 64 cells (2D: 64 columns; or a
+ * 3D side above 8) likewise one wavefront per container, its height-map, history and lists in LDS across the n
+ * placements (k_macs2d_wave_episode / k_macs3d_wave_episode; TAP_E_UNSUPPORTED only when that tile does not fit a
+ * workgroup's LDS or under TAP_NO_WAVE_KERNELS: step those with tap_env_step_gather).  reward_out (B,) f32 = -score,
+ * positions_out (B, n, D) i32, stable_out (B, n) u8, score64_out (B,) f64 = C+P+S (MACS / MUL: the function's `ratio` by
+ * reward type, NaN where the container raised an error bit) -- each nullable.
  * A block with a side < 1 is not part of its list (lists of different length in one batch: the
  * two-container reward of pack.py:451-466 packs the blocks of each target id separately); S is
  * taken over the blocks that are, and an empty list scores 0 (pack.py:459-460). */

@@ -23,7 +23,9 @@ TAP_SB_INITIAL_MASK, TAP_SB_CONTINUE = 1, 2
 TAP_FEAT_FULL, TAP_FEAT_ZERO, TAP_FEAT_DIFF = 0, 1, 2
 TAP_AT_CONTAINER, TAP_AT_NET = 1, 2
 TAP_F_AT_CONTAINER, TAP_F_AT_NET = 1 << 5, 1 << 6
+TAP_HIT_EPISODE_MACS2, TAP_HIT_EPISODE_MACS3 = 17, 18          # tap_common.h: TapHitKind
 TAP_HIT_PLACE_AT = 22
+TAP_HIT_EPISODE_MACS2_WAVE, TAP_HIT_EPISODE_MACS3_WAVE = 23, 24
 
 
 _vp_t = C.c_void_p

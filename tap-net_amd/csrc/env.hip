@@ -56,6 +56,8 @@ extern "C" int tap_ctx_create(int device, tap_ctx **out)
     int lds = 0;
     c->lds_limit = (hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, device) == hipSuccess && lds > 0)
                        ? (size_t)lds : (size_t)64 * 1024;
+    int cus = 0;
+    c->cus = (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) ? cus : 0;
     bool ok = hipSetDevice(device) == hipSuccess &&
               hipMalloc(reinterpret_cast<void **>(&c->chk), 2 * TAP_CHK_SLOTS * sizeof(int32_t)) == hipSuccess &&
               hipMalloc(reinterpret_cast<void **>(&c->stab_lut), TAP_LUT_WORDS * sizeof(uint32_t)) == hipSuccess &&

@@ -3,6 +3,8 @@
 //   tools.calc_positions_lb_greedy (tools.py:2393-2449)  -> k_episode<D,G>          (tap_place.h)
 //   tools.calc_positions_mcs       (tools.py:3213-3315)  -> k_episode_macs2<G,WIDE> (tap_macs.h / tap_macs_wide.h)
 //                                                           k_episode_macs3<G>      (tap_macs3.h)
+//                                                           above 64 cells: k_macs2d_wave_episode / k_macs3d_wave_episode
+//                                                           (macs_big.hip / macs3_big.hip), as LB_GREEDY's are in big.hip
 // Callers in the reference: pack.reward (pack.py:378-473), pack.render (pack.py:743-792), generate.generate_blocks
 // (generate.py:908), generate_blocks_with_GT (generate.py:112).  gfx950 only.
 #include "tap_common.h"
@@ -239,6 +241,8 @@ template <int G> static int launch_episode_macs3(tap_ctx *ctx, const EpisodeArgs
 int tap_macs_validate(tap_ctx *ctx, const tap_env_desc &d); // macs.hip
 
 int tap_big_episode(tap_ctx *ctx, const EpisodeArgs &a, hipStream_t st);   // big.hip: LB_GREEDY above 64 cells
+int tap_macs_wave_episode(tap_ctx *ctx, const EpisodeArgs &a, hipStream_t st);    // macs_big.hip: MACS / MUL 2D above 64 columns
+int tap_macs3_wave_episode(tap_ctx *ctx, const EpisodeArgs &a, hipStream_t st);   // macs3_big.hip: MACS / MUL 3D above 64 cells or a side above 8
 
 static int episode_dispatch(tap_ctx *ctx, const tap_env_desc *d, const EpisodeArgs &a, hipStream_t st)
 {
@@ -246,6 +250,8 @@ static int episode_dispatch(tap_ctx *ctx, const tap_env_desc *d, const EpisodeAr
     if (d->strategy == TAP_MACS) {
         int rc = tap_macs_validate(ctx, *d);
         if (rc) return rc;
+        if (tap_is_big_macs(d)) return tap_macs_wave_episode(ctx, a, st);     // one wavefront per container, its tile in LDS
+        if (tap_is_big_macs3(d)) return tap_macs3_wave_episode(ctx, a, st);
         if (d->D == 3) {
             switch (tap_group_size(d)) {
             case 8: return launch_episode_macs3<8>(ctx, a, st);
@@ -267,8 +273,6 @@ static int episode_validate(tap_ctx *ctx, const tap_env_desc *d, const char *wha
     if (rc) return rc;
     if (d->strategy == TAP_LB)
         return tap_fail(ctx, TAP_E_UNSUPPORTED, "%s: the legacy 'LB' strategy has no whole-episode form in use (tools.calc_positions_greedy is commented out at pack.py:741)", what);
-    if (tap_is_big_macs(d) || tap_is_big_macs3(d))
-        return tap_fail(ctx, TAP_E_UNSUPPORTED, "%s: MACS / MUL containers above 64 cells are stepped with tap_env_step_gather", what);
     return TAP_OK;
 }
 

@@ -10,6 +10,7 @@
 #include "tap_macs3_wave.h"
 #include "tap_masks.h"
 #include "tap_transition.h"
+#include "tap_episode.h"
 
 static_assert(M3B_F_HARD == TAP_F_HARD && M3B_F_USE_P == TAP_F_USE_P && M3B_F_USE_S == TAP_F_USE_S &&
               M3B_F_ZERO == TAP_F_MCS_ZERO && M3B_F_TIE == TAP_F_MCS_TIE, "flag bits are passed through");
@@ -83,20 +84,29 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_macs3d_big_step(StepArgs a, int32
 }
 
 // ---- one WAVEFRONT per container (tap_macs3_wave.h): the container's working set in the wave's LDS tile ---------------
-// one MACS 3D step of container `env` by one wavefront (every lane calls; env < B); base = the wave's LDS tile
-__device__ __forceinline__ void macs3d_wave_body(const StepArgs &a, int env, int lane, m3b_u64 *base)
+// the tile at `base` (m3w_tile_u64 units): occ | rows | ems | hm | lev | slots | pxy | bs | be | history pos[3 n_max] | blk[3 n_max]
+__device__ __forceinline__ M3WTile macs3d_wave_tile(m3b_u64 *base, int W, int L, int H, int flags, int n_max, int32_t *&hpos, int32_t *&hblk)
 {
-    const int B = a.d.B, W = a.d.W, L = a.d.L, H = a.d.H, cells = W * L, HW = (H + 63) / 64;
-    const int cap = macs3_big_cap(a.d.n_max);
+    const int cells = W * L, HW = (H + 63) / 64, cap = macs3_big_cap(n_max);
     M3WTile s;
-    s.W = W; s.L = L; s.H = H; s.HW = HW; s.flags = a.d.flags; s.cap = cap; s.n_max = a.d.n_max;
+    s.W = W; s.L = L; s.H = H; s.HW = HW; s.flags = flags; s.cap = cap; s.n_max = n_max; s.step = 0;
     s.occ = base;
     s.rows = s.occ + (size_t)cells * HW;
     s.ems = reinterpret_cast<M3BEms *>(s.rows + 64);
     s.hm = reinterpret_cast<int32_t *>(s.ems + cap);
     s.lev = s.hm + cells; s.slots = s.lev + cells; s.pxy = s.slots + cells; s.bs = s.pxy + cells; s.be = s.bs + 64;
-    int32_t *hpos = s.be + 64, *hblk = hpos + 3 * a.d.n_max;                    // the history so far, one round trip for all of it
+    hpos = s.be + 64; hblk = hpos + 3 * n_max;                                   // the history so far, staged in the tile
     s.pos = hpos; s.blk = hblk; s.hs = 1;
+    return s;
+}
+
+// one MACS 3D step of container `env` by one wavefront (every lane calls; env < B); base = the wave's LDS tile: load the
+// state into the tile, place on the tile (m3w_place), store state / feature
+__device__ __forceinline__ void macs3d_wave_body(const StepArgs &a, int env, int lane, m3b_u64 *base)
+{
+    const int B = a.d.B, W = a.d.W, L = a.d.L, H = a.d.H, cells = W * L, HW = (H + 63) / 64;
+    int32_t *hpos, *hblk;                                                        // one round trip for all of the history
+    M3WTile s = macs3d_wave_tile(base, W, L, H, a.d.flags, a.d.n_max, hpos, hblk);
     int32_t *ghm = a.v.hm + (size_t)env * cells;
     m3b_u64 *gocc = a.v.occ + (size_t)env * cells * HW;
     for (int c = lane; c < cells; c += 64) s.hm[c] = ghm[c];
@@ -169,6 +179,116 @@ __device__ __forceinline__ void macs3d_wave_body(const StepArgs &a, int env, int
             for (int c = lane; c < cells; c += 64) o[c] = (float)(s.hm[c] - mn);
         }
     }
+}
+
+// ---- whole episodes: tools.calc_positions_mcs (tools.py:3213-3315) beyond the lane-per-cell kernel ------------------
+// One wavefront per container as in the step kernel, its tile -- height-map, history, free-list bit-grid, lists --
+// living in LDS across the n placements: nothing but the block list and the per-episode results touches memory, and no
+// state blob exists.  A tour entry's block is fetched by lane t % 64 for 64 steps at a time, as in k_big_wave_episode
+// (big.hip).  cnt[3] counts every entry of the container's list (S's denominator), and the history keeps failed entries
+// too (tools.py:2843-2846), as in k_episode_macs3 (episode.hip).
+__device__ __forceinline__ void macs3d_wave_episode_body(const EpisodeArgs &a, int tile_u64)
+{
+    extern __shared__ unsigned long long m3w_lds[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;   // (a vector value, as in this file's other kernels: TAP_WAVE_INDEX() measured slower / flat in them, tap_common.h)
+    const int env = (int)(blockIdx.x * (blockDim.x >> 6)) + wave;
+    if (env >= a.B) return;                                                       // wave-uniform
+    const int W = a.d.W, L = a.d.L, cells = W * L, HW = (a.d.H + 63) / 64, n = a.n;
+    int32_t *hpos, *hblk;
+    M3WTile s = macs3d_wave_tile(m3w_lds + (size_t)wave * tile_u64, W, L, a.d.H, a.d.flags, n, hpos, hblk);
+    for (int c = lane; c < cells; c += 64) s.hm[c] = 0;
+    for (int k = lane; k < cells * HW; k += 64) s.occ[k] = 0ull;                  // level_free_space of an empty container
+    tap_wave_lds_sync();
+    int cnt[4] = {0, 0, 0, 0};
+    int err = 0;
+    for (int t0 = 0; t0 < n; t0 += 64) {
+        int mine[3] = {1, 1, 1}, merr = 0;
+        bool min_ = false;
+        if (t0 + lane < n) min_ = episode_block<3>(a, env, t0 + lane, true, mine, merr);
+        err |= merr;                                                              // OR-ed over the wave below
+        for (int j = 0; j < 64 && t0 + j < n; ++j) {
+            const int t = t0 + j;
+            const int bx = __shfl(mine[0], j), by = __shfl(mine[1], j), bz = __shfl(mine[2], j);
+            const bool in = __shfl((int)min_, j) != 0;
+            bool do_step = in;
+            if (in && (bx < 1 || by < 1 || bz < 1 || bx > W || by > L || bx > TAP_WIDE_MAX_SIDE || by > TAP_WIDE_MAX_SIDE)) { err |= 4; do_step = false; }   // as k_macs3d_wave_step
+            M3BResult r = {0, 0, 0, 0, 0};
+            if (do_step) {                                                        // wave-uniform
+                const int step = cnt[3];
+                s.step = step;
+                r = m3w_place(s, cnt, err, bx, by, bz, a.lut, lane);
+                cnt[3] += 1;                                                      // tools.py:3713
+                if (lane == 0) {                                                  // tools.py:2843-2846: failures too
+                    hpos[step * 3] = r.x; hpos[step * 3 + 1] = r.y; hpos[step * 3 + 2] = r.z;
+                    hblk[step * 3] = bx | (r.placed << 16); hblk[step * 3 + 1] = by; hblk[step * 3 + 2] = bz;
+                }
+                tap_wave_lds_sync();
+            }
+            if (lane == 0) {
+                if (a.pos_out) {
+                    int32_t *pp = a.pos_out + ((size_t)env * n + t) * 3;
+                    pp[0] = r.x; pp[1] = r.y; pp[2] = r.z;
+                }
+                if (a.stable_out) a.stable_out[(size_t)env * n + t] = (uint8_t)r.stab;
+            }
+        }
+    }
+    int gmax = 0;
+    for (int c = lane; c < cells; c += 64) gmax = max(gmax, s.hm[c]);
+    gmax = group_max<64>(gmax);
+    err = group_or<64>(err);
+    const Counters cn = {cnt[0], cnt[1], cnt[2], cnt[3]};
+    if (lane == 0) episode_finish(a, env, cn, gmax, err);
+}
+
+// Two builds of the same body.  Left alone the compiler takes 169 VGPRs for the loop around the placement (the step
+// kernel: 125), which is the faster code but lets a SIMD hold two waves; held to four waves per SIMD it takes 128 and
+// spills 14.  Measured (profiles/macs_wave_episode.json, ms per episode, loose / tight): 10 x 10, n = 10, B = 128
+// 0.84 / 0.90, B = 4 096 1.79 / 1.20 (stepped: 1.59); 20 x 20, n = 30, B = 128 11.6 / 13.2, B = 4 096 23.6 / 26.6.
+// The launcher takes the tight one only when more than two waves per SIMD would be resident (macs3d_episode_tight).
+__global__ void __launch_bounds__(TAP_BLOCK) k_macs3d_wave_episode(EpisodeArgs a, int tile_u64) { macs3d_wave_episode_body(a, tile_u64); }
+__global__ void __launch_bounds__(TAP_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 8))) k_macs3d_wave_episode_tight(EpisodeArgs a, int tile_u64)
+{
+    macs3d_wave_episode_body(a, tile_u64);
+}
+
+// Would a CU hold more waves than the loose build lets it?  What a CU would hold: the smaller of what the LDS admits
+// (whole workgroups of `waves` tiles) and what the batch puts there.  What the loose build lets it hold: 4 SIMDs x
+// (512 VGPRs / its own register count, in granules of 8), read from the code object once -- 8 waves at today's 169
+// VGPRs -- so the rule follows the compiler.  Without a CU count (the query failed at create) the batch bound is
+// unknown and the tight build, which is never slower than stepping, is taken whenever the LDS admits more.
+static bool macs3d_episode_tight(const tap_ctx *ctx, int B, int waves, size_t tile)
+{
+    static const int loose_waves = [] {
+        hipFuncAttributes fa;
+        if (hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k_macs3d_wave_episode)) != hipSuccess || fa.numRegs < 1) return 8;
+        const int per_simd = 512 / ((fa.numRegs + 7) / 8 * 8);
+        return 4 * (per_simd < 1 ? 1 : per_simd > 8 ? 8 : per_simd);
+    }();
+    const long by_lds = (long)(tap_lds_limit(ctx) / ((size_t)waves * tile)) * waves;
+    const long by_batch = (ctx && ctx->cus > 0) ? ((long)B + ctx->cus - 1) / ctx->cus : by_lds;
+    return (by_lds < by_batch ? by_lds : by_batch) > loose_waves;
+}
+
+// -> TAP_OK when launched; TAP_E_UNSUPPORTED when a container's tile does not fit the LDS or the wave kernels are
+// switched off (the thread-per-container kernel steps those shapes)
+int tap_macs3_wave_episode(tap_ctx *ctx, const EpisodeArgs &a, hipStream_t st)
+{
+    if (a.B == 0) return TAP_OK;
+    if (a.n > TAP_WAVE_EPISODE_MAX_N) return tap_fail(ctx, TAP_E_UNSUPPORTED, "whole MACS / MUL episodes of more than %d blocks: step them with tap_env_step_gather", TAP_WAVE_EPISODE_MAX_N);
+    const size_t tile_u64 = m3w_tile_u64(a.d.W * a.d.L, (a.d.H + 63) / 64, a.n, macs3_big_cap(a.n)), tile = tile_u64 * 8;
+    int waves = TAP_BLOCK / 64;
+    while (waves > 1 && (size_t)waves * tile > tap_lds_limit(ctx)) waves >>= 1;
+    if ((size_t)waves * tile > tap_lds_limit(ctx) || tap_wave_kernels_off())
+        return tap_fail(ctx, TAP_E_UNSUPPORTED, "whole MACS / MUL episodes of %d x %d x %d containers, %d blocks: %s, step them with tap_env_step_gather",
+                        a.d.W, a.d.L, a.d.H, a.n, tap_wave_kernels_off() ? "the wave kernels are switched off" : "the container's tile does not fit a workgroup's LDS");
+    const bool tight = macs3d_episode_tight(ctx, a.B, waves, tile);
+    auto *kernel = tight ? k_macs3d_wave_episode_tight : k_macs3d_wave_episode;
+    TAP_HIP_CHECK(ctx, tap_allow_lds(kernel, (size_t)waves * tile));
+    hipLaunchKernelGGL(kernel, dim3((a.B + waves - 1) / waves), dim3(waves * 64), (size_t)waves * tile, st, a, (int)tile_u64);
+    TAP_LAUNCH_CHECK(ctx, "k_macs3d_wave_episode");
+    tap_variant_hit(ctx, TAP_HIT_EPISODE_MACS3_WAVE, 3, 64, TapVariant{0, tight ? 1 : 0, waves}, 0);   // mode 1: the register-tight build
+    return TAP_OK;
 }
 
 __global__ void __launch_bounds__(TAP_BLOCK) k_macs3d_wave_step(StepArgs a)

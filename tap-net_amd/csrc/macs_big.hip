@@ -6,11 +6,13 @@
 // with the long loops shared by the lanes (the form that runs), and k_macs2d_big_step, one THREAD per container walking
 // its own columns in global memory (the serial statement of the algorithm; the fallback when a container's tile does not
 // fit the LDS).  No mask is involved, so neither the container nor a block has a width limit beyond the state
-// blob's (W <= 4096).  gfx950 only.
+// blob's (W <= 4096).  k_macs2d_wave_episode: a whole episode (tools.calc_positions_mcs) of a container above 64 columns
+// in one launch, the wavefront's tile resident across the placements.  gfx950 only.
 #include "tap_common.h"
 #include "tap_place.h"
 #include "tap_masks.h"
 #include "tap_transition.h"
+#include "tap_episode.h"
 
 // EMS entries one step can produce: the runs of level 0 (at most (W+1)/2), one run per level z > 0 for which some
 // column of the run has hm == z (a run without such a column is the same run as on the level below and is skipped,
@@ -282,46 +284,38 @@ __device__ __forceinline__ long mw_sum(long v)
     return v;
 }
 
-// one MACS 2D step of container `env` by one wavefront (every lane calls; env < B); tile = the wave's LDS tile
-__device__ __forceinline__ void macs2d_wave_body(const StepArgs &a, int cap, int env, int lane, int32_t *tile)
+// A wavefront's LDS tile (pointers into it) and the container's sizes: what one placement works on
+struct Mw2Tile {
+    int W, H, flags, cap;
+    int32_t *hm, *lev, *psum, *slots, *tl, *tr;                                   // tl / tr: the tie-break's per-level tables
+    int2 *ems;
+    int32_t *hpos, *hblk;                                                         // the history so far: (x, z) and (bx, bz) of entry i at [2 i]
+};
+__device__ __forceinline__ Mw2Tile macs2d_wave_tile(int32_t *tile, int W, int H, int flags, int cap, int n_max)
 {
-    const int B = a.d.B, W = a.d.W, H = a.d.H;
-    int32_t *hm = tile;
-    int32_t *lev = hm + W, *psum = lev + W, *slots = psum + W;
-    int32_t *tl = slots + W, *tr = tl + W + 1;                                  // the tie-break's per-level tables
-    int2 *ems = reinterpret_cast<int2 *>(tr + W + 1);
-    int32_t *ghm = a.v.hm + (size_t)env * W;
-    int gmax = 0;
-    for (int k = lane; k < W; k += 64) { const int h = ghm[k]; hm[k] = h; gmax = max(gmax, h); }
-    gmax = mw_max(gmax);
-    const int4 cv = reinterpret_cast<const int4 *>(a.v.cnt)[env];
-    Counters cnt = {cv.x, cv.y, cv.z, cv.w};
-    int bx, bz;
-    if (a.static_) {
-        bool badp;
-        const long p = tap_col((long)a.ptr[env], a.nR, badp);
-        bx = badp ? 0 : (int)a.static_[((size_t)env * a.static_rows + 1) * a.nR + p];
-        bz = badp ? 0 : (int)a.static_[((size_t)env * a.static_rows + 2) * a.nR + p];
-    } else if (a.blocks_dtype == TAP_DT_F32) {
-        bx = (int)((const float *)a.blocks)[(size_t)env * 2];
-        bz = (int)((const float *)a.blocks)[(size_t)env * 2 + 1];
-    } else {
-        bx = ((const int32_t *)a.blocks)[(size_t)env * 2];
-        bz = ((const int32_t *)a.blocks)[(size_t)env * 2 + 1];
-    }
-    const bool act = !a.active || a.active[env] != 0;
-    int err = 0;
-    bool do_step = act;
-    if (act && cnt.count >= a.d.n_max) { err |= 2; do_step = false; }
-    if (act && (bx < 1 || bz < 1)) { err |= 4; do_step = false; }
-    const int step = cnt.count;
-    Placement res = {0, 0, 0, 0, 0};
-    int32_t *hpos = reinterpret_cast<int32_t *>(ems + cap), *hblk = hpos + 2 * a.d.n_max;   // the history so far, one round trip for all of it
-    for (int k = lane; k < 2 * min(step, a.d.n_max); k += 64) { hpos[k] = a.v.pos[(size_t)k * B + env]; hblk[k] = a.v.blk[(size_t)k * B + env]; }
-    tap_wave_lds_sync();
+    Mw2Tile T;
+    T.W = W; T.H = H; T.flags = flags; T.cap = cap;
+    T.hm = tile;
+    T.lev = T.hm + W; T.psum = T.lev + W; T.slots = T.psum + W;
+    T.tl = T.slots + W; T.tr = T.tl + W + 1;
+    T.ems = reinterpret_cast<int2 *>(T.tr + W + 1);
+    T.hpos = reinterpret_cast<int32_t *>(T.ems + cap); T.hblk = T.hpos + 2 * n_max;
+    return T;
+}
 
-    if (do_step) {                                                               // wave-uniform
-        const int flags = a.d.flags;
+// One placement ON THE TILE by one wavefront (every lane calls with the same arguments and gets the same result): the
+// tile holds the height-map and the history of the cnt.count entries so far, visible to the wave; gmax = max(hm).  The
+// step kernels call it between their load and their store, the whole-episode kernel in a loop.  On return the tile's
+// height-map is the new one (visible to the wave), cnt counts this entry; the caller appends the history.
+__device__ __forceinline__ Placement macs2d_wave_place(const Mw2Tile &T, Counters &cnt, int &err, int gmax, int bx, int bz, int lane)
+{
+    const int W = T.W, H = T.H, cap = T.cap, step = cnt.count;
+    int32_t *const hm = T.hm, *const lev = T.lev, *const psum = T.psum, *const slots = T.slots, *const tl = T.tl, *const tr = T.tr;
+    int2 *const ems = T.ems;
+    const int32_t *const hpos = T.hpos, *const hblk = T.hblk;
+    Placement res = {0, 0, 0, 0, 0};
+    {
+        const int flags = T.flags;
         const bool hard = (flags & TAP_F_HARD) != 0;
         const int vol = bx * bz;
         int n_ems = 0;
@@ -564,7 +558,7 @@ __device__ __forceinline__ void macs2d_wave_body(const StepArgs &a, int cap, int
             (void)eval_slot(win, xs, Z, sum, stab);
             res.placed = 1; res.x = xs; res.z = Z; res.stab = stab;
             tap_wave_lds_sync();
-            for (int k = xs + lane; k < xs + bx; k += 64) { hm[k] = Z + bz; ghm[k] = Z + bz; }
+            for (int k = xs + lane; k < xs + bx; k += 64) hm[k] = Z + bz;
             cnt.valid += vol;
             cnt.empty = cnt.empty + bx * Z - sum;
             cnt.nstable += stab;
@@ -573,6 +567,50 @@ __device__ __forceinline__ void macs2d_wave_body(const StepArgs &a, int cap, int
         cnt.count += 1;
         tap_wave_lds_sync();
 #undef MW_PUSH
+    }
+    return res;
+}
+
+// one MACS 2D step of container `env` by one wavefront (every lane calls; env < B); tile = the wave's LDS tile:
+// load the state into the tile, place on the tile (macs2d_wave_place), store state / feature
+__device__ __forceinline__ void macs2d_wave_body(const StepArgs &a, int cap, int env, int lane, int32_t *tile)
+{
+    const int B = a.d.B, W = a.d.W;
+    const Mw2Tile T = macs2d_wave_tile(tile, W, a.d.H, a.d.flags, cap, a.d.n_max);
+    int32_t *hm = T.hm;
+    int32_t *ghm = a.v.hm + (size_t)env * W;
+    int gmax = 0;
+    for (int k = lane; k < W; k += 64) { const int h = ghm[k]; hm[k] = h; gmax = max(gmax, h); }
+    gmax = mw_max(gmax);
+    const int4 cv = reinterpret_cast<const int4 *>(a.v.cnt)[env];
+    Counters cnt = {cv.x, cv.y, cv.z, cv.w};
+    int bx, bz;
+    if (a.static_) {
+        bool badp;
+        const long p = tap_col((long)a.ptr[env], a.nR, badp);
+        bx = badp ? 0 : (int)a.static_[((size_t)env * a.static_rows + 1) * a.nR + p];
+        bz = badp ? 0 : (int)a.static_[((size_t)env * a.static_rows + 2) * a.nR + p];
+    } else if (a.blocks_dtype == TAP_DT_F32) {
+        bx = (int)((const float *)a.blocks)[(size_t)env * 2];
+        bz = (int)((const float *)a.blocks)[(size_t)env * 2 + 1];
+    } else {
+        bx = ((const int32_t *)a.blocks)[(size_t)env * 2];
+        bz = ((const int32_t *)a.blocks)[(size_t)env * 2 + 1];
+    }
+    const bool act = !a.active || a.active[env] != 0;
+    int err = 0;
+    bool do_step = act;
+    if (act && cnt.count >= a.d.n_max) { err |= 2; do_step = false; }
+    if (act && (bx < 1 || bz < 1)) { err |= 4; do_step = false; }
+    const int step = cnt.count;
+    Placement res = {0, 0, 0, 0, 0};
+    for (int k = lane; k < 2 * min(step, a.d.n_max); k += 64) { T.hpos[k] = a.v.pos[(size_t)k * B + env]; T.hblk[k] = a.v.blk[(size_t)k * B + env]; }   // the history so far, one round trip for all of it
+    tap_wave_lds_sync();
+
+    if (do_step) {                                                               // wave-uniform
+        res = macs2d_wave_place(T, cnt, err, gmax, bx, bz, lane);
+        if (res.placed)
+            for (int k = res.x + lane; k < res.x + bx; k += 64) ghm[k] = res.z + bz;
     }
 
     if (a.feature_out) {                                                          // tools.py:3716-3744
@@ -600,6 +638,76 @@ __device__ __forceinline__ void macs2d_wave_body(const StepArgs &a, int cap, int
         }
         if (err) a.v.err[env] |= err;
     }
+}
+
+// ---- whole episodes: tools.calc_positions_mcs (tools.py:3213-3315) for containers above 64 columns ------------------
+// One wavefront per container as in the step kernel, its tile -- height-map, history, lists -- living in LDS across the
+// n placements: nothing but the block list and the per-episode results touches memory, and no state blob exists.  A
+// tour entry's block is fetched by lane t % 64 for 64 steps at a time, as in k_big_wave_episode (big.hip).  cnt.count
+// counts every entry of the container's list (S's denominator), and the history keeps failed entries too
+// (tools.py:2531-2533), as in k_episode_macs2 (episode.hip).
+__global__ void __launch_bounds__(TAP_BLOCK) k_macs2d_wave_episode(EpisodeArgs a, int cap, int tile_ints)
+{
+    extern __shared__ int32_t mw_lds[];
+    const int lane = threadIdx.x & 63, wave = TAP_WAVE_INDEX();
+    const int env = (int)(blockIdx.x * (blockDim.x >> 6)) + wave;
+    if (env >= a.B) return;                                                       // wave-uniform
+    const int W = a.d.W, n = a.n;
+    const Mw2Tile T = macs2d_wave_tile(mw_lds + (size_t)wave * tile_ints, W, a.d.H, a.d.flags, cap, n);
+    for (int k = lane; k < W; k += 64) T.hm[k] = 0;
+    tap_wave_lds_sync();
+    Counters cnt = {0, 0, 0, 0};
+    int err = 0, gmax = 0;
+    for (int t0 = 0; t0 < n; t0 += 64) {
+        int mine[3] = {1, 1, 1}, merr = 0;
+        bool min_ = false;
+        if (t0 + lane < n) min_ = episode_block<2>(a, env, t0 + lane, true, mine, merr);
+        err |= merr;                                                              // OR-ed over the wave below
+        for (int j = 0; j < 64 && t0 + j < n; ++j) {
+            const int t = t0 + j;
+            const int bx = __shfl(mine[0], j), bz = __shfl(mine[1], j);
+            const bool in = __shfl((int)min_, j) != 0;
+            bool do_step = in;
+            if (in && (bx < 1 || bz < 1)) { err |= 4; do_step = false; }
+            Placement pl = {0, 0, 0, 0, 0};
+            if (do_step) {                                                        // wave-uniform
+                const int step = cnt.count;
+                pl = macs2d_wave_place(T, cnt, err, gmax, bx, bz, lane);
+                if (pl.placed) gmax = max(gmax, pl.z + bz);
+                if (lane == 0) {                                                  // failures too, at (0, 0)
+                    T.hpos[step * 2] = pl.x; T.hpos[step * 2 + 1] = pl.z;
+                    T.hblk[step * 2] = bx; T.hblk[step * 2 + 1] = bz;
+                }
+                tap_wave_lds_sync();
+            }
+            if (lane == 0) {
+                if (a.pos_out) { a.pos_out[((size_t)env * n + t) * 2] = pl.x; a.pos_out[((size_t)env * n + t) * 2 + 1] = pl.z; }
+                if (a.stable_out) a.stable_out[(size_t)env * n + t] = (uint8_t)pl.stab;
+            }
+        }
+    }
+    err = group_or<64>(err);
+    if (lane == 0) episode_finish(a, env, cnt, gmax, err);
+}
+
+// -> TAP_OK when launched; TAP_E_UNSUPPORTED when a container's tile does not fit the LDS or the wave kernels are
+// switched off (the thread-per-container kernel steps those shapes)
+int tap_macs_wave_episode(tap_ctx *ctx, const EpisodeArgs &a, hipStream_t st)
+{
+    if (a.B == 0) return TAP_OK;
+    if (a.n > TAP_WAVE_EPISODE_MAX_N) return tap_fail(ctx, TAP_E_UNSUPPORTED, "whole MACS / MUL episodes of more than %d blocks: step them with tap_env_step_gather", TAP_WAVE_EPISODE_MAX_N);
+    const int cap = macs_big_cap(a.d.W, a.n);
+    const size_t tile_ints = macs_wave_tile_ints(a.d.W, cap, a.n), tile = tile_ints * sizeof(int32_t);
+    int waves = TAP_BLOCK / 64;
+    while (waves > 1 && (size_t)waves * tile > tap_lds_limit(ctx)) waves >>= 1;
+    if ((size_t)waves * tile > tap_lds_limit(ctx) || tap_wave_kernels_off())
+        return tap_fail(ctx, TAP_E_UNSUPPORTED, "whole MACS / MUL episodes of %d columns, %d blocks: %s, step them with tap_env_step_gather", a.d.W, a.n,
+                        tap_wave_kernels_off() ? "the wave kernels are switched off" : "the container's tile does not fit a workgroup's LDS");
+    TAP_HIP_CHECK(ctx, tap_allow_lds(k_macs2d_wave_episode, (size_t)waves * tile));
+    hipLaunchKernelGGL(k_macs2d_wave_episode, dim3((a.B + waves - 1) / waves), dim3(waves * 64), (size_t)waves * tile, st, a, cap, (int)tile_ints);
+    TAP_LAUNCH_CHECK(ctx, "k_macs2d_wave_episode");
+    tap_variant_hit(ctx, TAP_HIT_EPISODE_MACS2_WAVE, 2, 64, TapVariant{0, 0, waves}, 0);
+    return TAP_OK;
 }
 
 __global__ void __launch_bounds__(TAP_BLOCK) k_macs2d_wave_step(StepArgs a, int cap)

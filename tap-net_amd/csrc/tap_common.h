@@ -20,6 +20,7 @@ constexpr int TAP_BLOCK = 256; // threads per workgroup (4 wave64)
 // kernels (tap_launch_variant) count under their TapStreamKind, D / G = 0 where the launcher's table ignores them; the
 // whole-episode and rolling kernels under TapHitKind below.  314 stream-wave instantiations with wt = 0 and 1 (628 keys)
 // + 25 episode (wt 0) + 40 fused rolling steps and 16 window kernels with both wt + 8 init kernels: at most 773 keys
+// (+ the two wave-episode kernels of macs_big.hip / macs3_big.hip, keyed by their 1, 2 or 4 waves per workgroup)
 constexpr int TAP_VARIANT_HIT_SLOTS = 1024;
 enum TapHitKind {               // (tapenv.h documents the fields of each)
     TAP_HIT_EPISODE = 16,       // k_episode<D, G, SOFT>                      (episode.hip: launch_episode)
@@ -29,6 +30,8 @@ enum TapHitKind {               // (tapenv.h documents the fields of each)
     TAP_HIT_ROLL_WINDOW,        // k_rolling_window / _wide / _big            (rolling.hip: rolling_window_impl)
     TAP_HIT_ROLL_INIT,          // k_rolling_init / _big                      (rolling.hip: tap_rolling_init)
     TAP_HIT_PLACE_AT,           // k_place_at<G, NET>                         (place_at.hip: launch_at)
+    TAP_HIT_EPISODE_MACS2_WAVE, // k_macs2d_wave_episode                      (macs_big.hip: tap_macs_wave_episode)
+    TAP_HIT_EPISODE_MACS3_WAVE, // k_macs3d_wave_episode / _tight             (macs3_big.hip: tap_macs3_wave_episode)
 };
 struct TapVariantHit {
     int32_t key[7];
@@ -41,6 +44,7 @@ struct tap_ctx {
     int32_t *chk;       // device: TAP_CHK_SLOTS x 2 ints (flagged envs, OR of their error words) for tap_env_check
     unsigned chk_next;  //   next slot
     size_t lds_limit;   // LDS a workgroup may allocate on this device (gfx950: 160 KiB per CU), queried at create
+    int cus;            // compute units of this device (MI355X: 256), queried at create; 0 when the query failed
     char err[512];
     std::mutex hit_lock;
     int nhits;

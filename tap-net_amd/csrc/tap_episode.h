@@ -22,6 +22,11 @@ struct EpisodeArgs {
     int32_t *err_out;      // (B,) the sticky error bits of tap_env_check
 };
 
+// Longest block list of the wave-per-container MACS episode kernels (macs_big.hip, macs3_big.hip), whose tile sizes grow
+// with the list: the history alone (4 or 6 ints per entry) passes a workgroup's 160 KiB of LDS before this many entries,
+// so the bound only keeps the launchers' int arithmetic small
+constexpr int TAP_WAVE_EPISODE_MAX_N = 8192;
+
 // One tour entry: the block's sides and whether it belongs to this container's list.
 // pack.py:441-444 gather by tour, :454-455 rows 1..D, tools.py:2415 / :3249 astype('int'); pack.py:455-457,
 // 755-757: with two containers the list of one is the sub-sequence with its target id.

@@ -783,8 +783,8 @@ def _beyond_lane_kernels(desc):
 
 
 def _stepped_scores(st, tour, container_size, n, reward_type, strategy, target, check=True):
-    """The whole-episode figures for shapes the one-launch kernels do not take (LB_GREEDY and MACS 3D above 64 cells or
-    with a 3D side above 8, MACS 2D above 64 columns): the same
+    """The whole-episode figures where tap_episode_scores answers TAP_E_UNSUPPORTED: containers above 64 cells (or with
+    a 3D side above 8) whose tile does not fit a workgroup's LDS, or all of them under TAP_NO_WAVE_KERNELS.  The same
     episode as n placement launches on a state blob, ``active`` selecting one container's blocks.  ``check`` as in
     episode_scores: raise like the reference (one host sync), or report per container -- NaN ratio where the error
     word is set, like the one-launch path."""
@@ -823,7 +823,8 @@ def _stepped_scores(st, tour, container_size, n, reward_type, strategy, target, 
 def episode_scores(static, tour_indices, reward_type, input_type, allow_rot, container_size, packing_strategy='LB_GREEDY',
                    target=None, check=True):
     """tools.calc_positions_lb_greedy (tools.py:2393-2449) / tools.calc_positions_mcs (tools.py:3213-3315) for
-    every sample of a batch in one launch (MACS / MUL containers above 64 cells: one placement launch per block,
+    every sample of a batch in one launch, containers above 64 cells included (one wavefront per container, its tile
+    in LDS; only when that tile does not fit the LDS, or under TAP_NO_WAVE_KERNELS, one placement launch per block,
     _stepped_scores): blocks in tour order into an empty container.
     -> (ratio (B,) float64, scores (B, 5) int64 = valid_size, box_size, empty_size, stable_num, max height).
     ``target`` 0 | 1: only the blocks whose target id (last row of ``static``, the two-container input types) equals
@@ -846,9 +847,6 @@ def episode_scores(static, tour_indices, reward_type, input_type, allow_rot, con
                                 "scores)" % (reward_type, 'calc_positions_mcs' if mcs else 'calc_positions_lb_greedy'))
     strategy = 'MACS' if mcs else 'LB_GREEDY'
     desc = _lib.make_desc(B, container_size, n, reward_type, 'full', strategy)
-    if mcs and _beyond_lane_kernels(desc):
-        # MACS / MUL beyond the whole-episode kernels' container size (above 64 cells -- 2D: 64 columns -- or a 3D side above 8)
-        return _stepped_scores(st, tour, list(container_size), n, reward_type, strategy, target, check)
     ratio = torch.empty(B, dtype=torch.float64, device=st.device)
     scores = torch.empty(B, 5, dtype=torch.int64, device=st.device)
     err = torch.empty(B, dtype=torch.int32, device=st.device)
