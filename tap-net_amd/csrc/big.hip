@@ -4,13 +4,15 @@
 // container walking its own cells -- a correctness path for unusual shapes, not a fast one; every BASELINE
 // shape takes the lane-per-cell kernels.  Limits: W*L <= 16 384 cells (above 4 096: one workgroup per container, at the
 // end of this file); 3D block footprints up to 16 x 16 (beyond the 8 x 8 support masks: tap_stable_wide.h), larger ones
-// raise error bit 4; 2D blocks of any width.
+// raise error bit 4 (big_rejects); 2D blocks of any width.  What surrounds a placement -- block fetch, admission, commit,
+// feature -- is tap_step_seam.h's; this file holds the placements and the tiles they work on.
 #include "tap_common.h"
 #include "tap_place.h"
 #include "tap_stable_wide.h"
 #include "tap_episode.h"
 #include "tap_masks.h"
 #include "tap_transition.h"
+#include "tap_step_seam.h"
 
 #include <type_traits>
 
@@ -225,65 +227,33 @@ __device__ static Placement big_place(const BigCtx &c, Counters &cnt, int &err, 
     return big_is_wide(c.D, bx, by) ? big_place_t<true>(c, cnt, err, bx, by, bz) : big_place_t<false>(c, cnt, err, bx, by, bz);
 }
 
-__device__ static void big_feature(int feature, int D, int W, int L, const int32_t *hm, float *out)
+// LB_GREEDY's own limit on a block (the step seam's `family_rejects`): a 3D footprint beyond the support masks THAT FITS
+// (one that does not fit finds no position and is filed as a failure); not looked at once the container is full
+__device__ __forceinline__ bool big_rejects(const tap_env_desc &d, int count, int bx, int by)
 {
-    const int cells = W * L;
-    if (feature == TAP_FEAT_DIFF) {                                              // tools.py:3716-3744
-        if (D == 2) { for (int c = 0; c + 1 < W; ++c) out[c] = (float)(hm[c + 1] - hm[c]); }
-        else
-            for (int c = 0; c < cells; ++c) {
-                const int x = c / L, y = c - x * L;
-                out[c] = (float)(x > 0 ? hm[c] - hm[c - L] : 0);
-                out[cells + c] = (float)(y > 0 ? hm[c] - hm[c - 1] : 0);
-            }
-        return;
-    }
-    int mn = 0;
-    if (feature == TAP_FEAT_ZERO) { mn = INT_MAX; for (int c = 0; c < cells; ++c) mn = min(mn, hm[c]); }
-    for (int c = 0; c < cells; ++c) out[c] = (float)(hm[c] - mn);
+    return count < d.n_max && d.D == 3 && (bx > TAP_WIDE_MAX_SIDE || by > TAP_WIDE_MAX_SIDE) && bx <= d.W && by <= d.L;
 }
 
 __global__ void __launch_bounds__(TAP_BLOCK) k_big_step(StepArgs a, int32_t *scratch, int lpw)
 {
     const int env = tap_spread_env(lpw, a.d.B);                                  // containers spread over the waves (tap_common.h)
-    const int B = a.d.B;
     if (env < 0) return;
     const int D = a.d.D, W = a.d.W, L = a.d.L, cells = W * L;
-    int dims[3] = {1, 1, 1};
-    int err = 0;
-    if (a.static_) {                                                             // model.py:404-412
-        bool badp;
-        const long p = tap_col((long)a.ptr[env], a.nR, badp);
-        for (int k = 0; k < D; ++k) dims[k] = badp ? 0 : (int)a.static_[((size_t)env * a.static_rows + 1 + k) * a.nR + p];
-    } else if (a.blocks_dtype == TAP_DT_F32) {
-        for (int k = 0; k < D; ++k) dims[k] = (int)((const float *)a.blocks)[(size_t)env * D + k];
-    } else {
-        for (int k = 0; k < D; ++k) dims[k] = ((const int32_t *)a.blocks)[(size_t)env * D + k];
-    }
-    const bool act = !a.active || a.active[env] != 0;
-    const int4 cv = reinterpret_cast<const int4 *>(a.v.cnt)[env];
-    Counters cnt = {cv.x, cv.y, cv.z, cv.w};
-    const int bx = dims[0], by = D == 3 ? dims[1] : 1, bz = dims[D - 1];
-    bool do_step = act;
-    if (act && cnt.count >= a.d.n_max) { err |= 2; do_step = false; }
-    if (act && (bx < 1 || by < 1 || bz < 1)) { err |= 4; do_step = false; }
-    if (act && do_step && (D == 3 && (bx > TAP_WIDE_MAX_SIDE || by > TAP_WIDE_MAX_SIDE) && bx <= W && by <= L)) {
-        err |= 4; do_step = false;                                               // footprint beyond the support masks
-    }
     int32_t *hm = a.v.hm + (size_t)env * cells;
+    const SeamBlock b = tap_seam_fetch(a, env);
+    bool act;
+    Counters cnt = tap_seam_load(a, env, false, act);
+    int err = 0;
+    const bool do_step = tap_seam_admit(act, cnt.count, a.d.n_max, b.bx, b.by, b.bz, big_rejects(a.d, cnt.count, b.bx, b.by), err);
+    const int step = cnt.count;
+    Placement pl = {0, 0, 0, 0, 0};
     if (do_step) {
         const BigCtx c = {D, W, L, a.d.H, a.d.flags, a.lut, hm, scratch + (size_t)env * cells};
-        const int step = cnt.count;
-        const Placement pl = big_place(c, cnt, err, bx, by, bz);
+        pl = big_place(c, cnt, err, b.bx, b.by, b.bz);
         cnt.count += 1;                                                          // tools.py:3713
-        reinterpret_cast<int4 *>(a.v.cnt)[env] = make_int4(cnt.valid, cnt.empty, cnt.nstable, cnt.count);
-        int32_t *q = a.v.pos + (size_t)step * D * B + env;
-        q[0] = pl.x;
-        if (D == 3) { q[B] = pl.y; q[2 * (size_t)B] = pl.z; } else q[B] = pl.z;
-        a.v.stable[(size_t)step * B + env] = (uint8_t)pl.stab;
     }
-    if (err) a.v.err[env] |= err;
-    if (a.feature_out) big_feature(a.d.feature, D, W, L, hm, a.feature_out + (size_t)env * a.flen);
+    tap_seam_commit(a, env, do_step, false, cnt, step, pl, err, nullptr);
+    if (a.feature_out) tap_seam_feature(a.d.feature, D, W, L, hm, a.feature_out + (size_t)env * a.flen, 0, 1, [](int v) { return v; });
 }
 
 // ---- soft rewards: one WAVEFRONT per container (round 4) ----------------------------------------------------------------
@@ -421,98 +391,40 @@ __device__ __forceinline__ Placement big_wave_place(const tap_env_desc &d, const
     return big_wave_place_t<HARD, false>(d, lut, hm, ghm, lane, gmax, cnt, err, bx, by, bz);
 }
 
-// One lock-step of one container by one wavefront (every lane calls): gather / block, placement, state and results out,
-// feature.  `hm` = the wave's LDS tile.  flags (TAP_T_FRESH: the step starts from an empty container; TAP_T_RATIO: emit
-// calc_ratio, tools.py:3887-3966) as in the fused lane-per-cell step; the gather's by-products (tap_step_aux) are written
-// when the step gathers.
+// One lock-step of one container by one wavefront (every lane calls), on the step seam: load tile, fetch, admit, place,
+// commit, feature.  `hm` = the wave's LDS tile.  flags (TAP_T_FRESH: the step starts from an empty container;
+// TAP_T_RATIO: emit calc_ratio) as in the fused lane-per-cell step.
 template <bool HARD>
 __device__ __forceinline__ void big_wave_step_body(const StepArgs &a, int env, int lane, int32_t *hm, int flags, float *ratio_out)
 {
-    const int B = a.d.B, D = a.d.D, W = a.d.W, L = a.d.L, cells = W * L;
+    const int D = a.d.D, W = a.d.W, L = a.d.L, cells = W * L;
     const bool fresh = (flags & TAP_T_FRESH) != 0;
     int32_t *ghm = a.v.hm + (size_t)env * cells;
     int gmax = 0;
     if (fresh) { for (int c = lane; c < cells; c += 64) { hm[c] = 0; ghm[c] = 0; } }
     else for (int c = lane; c < cells; c += 64) { const int h = ghm[c]; hm[c] = h; gmax = max(gmax, h); }
-    int dims[3] = {1, 1, 1};
-    float fv[3] = {0.f, 0.f, 0.f};
-    long praw = 0;
-    if (a.static_) {                                                             // model.py:404-412
-        bool badp;
-        praw = (long)a.ptr[env];
-        const long p = tap_col(praw, a.nR, badp);
-        for (int k = 0; k < D; ++k) {
-            const float v = a.static_[((size_t)env * a.static_rows + 1 + k) * a.nR + p];
-            dims[k] = badp ? 0 : (int)v;
-            fv[k] = badp ? 0.f : v;
-        }
-    } else if (a.blocks_dtype == TAP_DT_F32) {
-        for (int k = 0; k < D; ++k) dims[k] = (int)((const float *)a.blocks)[(size_t)env * D + k];
-    } else {
-        for (int k = 0; k < D; ++k) dims[k] = ((const int32_t *)a.blocks)[(size_t)env * D + k];
-    }
-    const bool act = !a.active || a.active[env] != 0;
-    const int4 cv = reinterpret_cast<const int4 *>(a.v.cnt)[env];
-    Counters cnt = {cv.x, cv.y, cv.z, cv.w};
-    if (fresh) cnt = Counters{0, 0, 0, 0};
-    const int bx = dims[0], by = D == 3 ? dims[1] : 1, bz = dims[D - 1];
+    const SeamBlock b = tap_seam_fetch(a, env);
+    if (lane == 0) tap_seam_aux(a, env, b);
+    bool act;
+    Counters cnt = tap_seam_load(a, env, fresh, act);
     int err = 0;
-    bool do_step = act;
-    if (act && cnt.count >= a.d.n_max) { err |= 2; do_step = false; }
-    if (act && (bx < 1 || by < 1 || bz < 1)) { err |= 4; do_step = false; }
-    if (act && do_step && (D == 3 && (bx > TAP_WIDE_MAX_SIDE || by > TAP_WIDE_MAX_SIDE) && bx <= W && by <= L)) {
-        err |= 4; do_step = false;                                               // footprint beyond the support masks
-    }
+    const bool do_step = tap_seam_admit(act, cnt.count, a.d.n_max, b.bx, b.by, b.bz, big_rejects(a.d, cnt.count, b.bx, b.by), err);
+    const int step = cnt.count;
+    Placement pl = {0, 0, 0, 0, 0};
     gmax = group_max<64>(gmax);
     tap_wave_lds_sync();
     if (do_step) {                                                               // wave-uniform
-        const int step = cnt.count;
-        const Placement pl = big_wave_place<HARD>(a.d, a.lut, hm, ghm, lane, gmax, cnt, err, bx, by, bz);
-        if (pl.placed) gmax = max(gmax, pl.z + bz);
+        pl = big_wave_place<HARD>(a.d, a.lut, hm, ghm, lane, gmax, cnt, err, b.bx, b.by, b.bz);
+        if (pl.placed) gmax = max(gmax, pl.z + b.bz);
         cnt.count += 1;                                                          // tools.py:3713
-        if (lane == 0) {
-            int32_t *q = a.v.pos + (size_t)step * D * B + env;
-            q[0] = pl.x;
-            if (D == 3) { q[B] = pl.y; q[2 * (size_t)B] = pl.z; } else q[B] = pl.z;
-            a.v.stable[(size_t)step * B + env] = (uint8_t)pl.stab;
-        }
         tap_wave_lds_sync();
     }
     if (lane == 0) {
-        if (do_step || fresh) reinterpret_cast<int4 *>(a.v.cnt)[env] = make_int4(cnt.valid, cnt.empty, cnt.nstable, cnt.count);
-        if (fresh) a.v.err[env] = err;
-        else if (err) a.v.err[env] |= err;
-        if (a.static_) tap_step_aux(a, env, D, fv, praw);
-        if ((flags & TAP_T_RATIO) && ratio_out) {                                // tools.py:3887-3966 on the state just written
-            double Cc = 0.0, P = 0.0, S = 0.0;
-            if (cnt.count != 0) {
-                Cc = (double)cnt.valid / (double)((long long)W * L * gmax);
-                P = (double)cnt.valid / (double)(cnt.empty + cnt.valid);
-                S = (double)cnt.nstable / (double)cnt.count;
-            }
-            ratio_out[env] = (float)tap_ratio_formula(a.d.ratio_mode, Cc, P, S);
-        }
+        tap_seam_commit(a, env, do_step, fresh, cnt, step, pl, err, nullptr);
+        if ((flags & TAP_T_RATIO) && ratio_out) ratio_out[env] = tap_seam_ratio(a.d, cnt, gmax);
     }
-    if (a.feature_out) {                                                         // tools.py:3716-3744, lanes over the cells
-        float *out = a.feature_out + (size_t)env * a.flen;
-        if (a.d.feature == TAP_FEAT_DIFF) {
-            if (D == 2) { for (int c = lane; c + 1 < W; c += 64) out[c] = (float)(hm[c + 1] - hm[c]); }
-            else
-                for (int c = lane; c < cells; c += 64) {
-                    const int x = c / L, y = c - x * L;
-                    out[c] = (float)(x > 0 ? hm[c] - hm[c - L] : 0);
-                    out[cells + c] = (float)(y > 0 ? hm[c] - hm[c - 1] : 0);
-                }
-        } else {
-            int mn = 0;
-            if (a.d.feature == TAP_FEAT_ZERO) {
-                mn = INT_MAX;
-                for (int c = lane; c < cells; c += 64) mn = min(mn, hm[c]);
-                mn = group_min<64>(mn);
-            }
-            for (int c = lane; c < cells; c += 64) out[c] = (float)(hm[c] - mn);
-        }
-    }
+    if (a.feature_out)
+        tap_seam_feature(a.d.feature, D, W, L, hm, a.feature_out + (size_t)env * a.flen, lane, 64, [](int v) { return group_min<64>(v); });
 }
 
 template <bool HARD>
@@ -588,12 +500,7 @@ __global__ void __launch_bounds__(TAP_BLOCK) TAP_BIG_REGS k_big_wave_episode(Epi
             const int b0 = __shfl(mine[0], j), b1 = __shfl(mine[1], j), b2 = __shfl(mine[2], j);
             const bool in = __shfl((int)min_, j) != 0;
             const int bx = b0, by = D == 3 ? b1 : 1, bz = D == 3 ? b2 : b1;
-            bool do_step = in;
-            if (in && cnt.count >= a.d.n_max) { err |= 2; do_step = false; }
-            if (in && (bx < 1 || by < 1 || bz < 1)) { err |= 4; do_step = false; }
-            if (do_step && (D == 3 && (bx > TAP_WIDE_MAX_SIDE || by > TAP_WIDE_MAX_SIDE) && bx <= W && by <= L)) {
-                err |= 4; do_step = false;                                        // footprint beyond the support masks
-            }
+            const bool do_step = tap_seam_admit(in, cnt.count, a.d.n_max, bx, by, bz, big_rejects(a.d, cnt.count, bx, by), err);
             Placement pl = {0, 0, 0, 0, 0};
             if (do_step) {                                                        // wave-uniform
                 pl = big_wave_place<HARD>(a.d, a.lut, hm, nullptr, lane, gmax, cnt, err, bx, by, bz);
@@ -810,7 +717,10 @@ __device__ __forceinline__ Placement big_wg_place(BigWg<NT> &g, const tap_env_de
 }
 
 // tap_env_step / tap_env_step_gather: one lock-step of container blockIdx.x (gather / block, placement, state and
-// results out, feature), as k_big_step
+// results out, feature), as k_big_step.  NOT on the step seam (tap_step_seam.h), on a measurement: with the seam's fetch and
+// admission in front of it the placement was compiled differently and hard rewards on 2D 8 192 x 100 ran 2 .. 3 % slower
+// at every batch size (soft rewards 5 .. 6 % faster, 3D hard 1 % faster; cause not found).  This body is the
+// pre-seam one, instruction for instruction.
 template <int NT, bool HARD>
 __global__ void __launch_bounds__(NT) k_big_wg_step(StepArgs a)
 {
@@ -899,12 +809,7 @@ __global__ void __launch_bounds__(NT) k_big_wg_episode(EpisodeArgs a)
         int dims[3];
         const bool in = D == 2 ? episode_block<2>(a, env, t, true, dims, err) : episode_block<3>(a, env, t, true, dims, err);
         const int bx = dims[0], by = D == 3 ? dims[1] : 1, bz = D == 3 ? dims[2] : dims[1];
-        bool do_step = in;
-        if (in && cnt.count >= a.d.n_max) { err |= 2; do_step = false; }
-        if (in && (bx < 1 || by < 1 || bz < 1)) { err |= 4; do_step = false; }
-        if (do_step && (D == 3 && (bx > TAP_WIDE_MAX_SIDE || by > TAP_WIDE_MAX_SIDE) && bx <= W && by <= L)) {
-            err |= 4; do_step = false;                                            // footprint beyond the support masks
-        }
+        const bool do_step = tap_seam_admit(in, cnt.count, a.d.n_max, bx, by, bz, big_rejects(a.d, cnt.count, bx, by), err);
         Placement pl = {0, 0, 0, 0, 0};
         if (do_step) {                                                            // workgroup-uniform
             pl = big_wg_place<NT, HARD>(g, a.d, a.lut, hm, nullptr, gmax, cnt, err, bx, by, bz);
@@ -981,10 +886,9 @@ int tap_big_episode(tap_ctx *ctx, const EpisodeArgs &a, hipStream_t st)
     if (a.d.W * a.d.L > TAP_BIG_WAVE_CELLS) return big_wg_episode(ctx, a, st);   // one workgroup per container
     const bool hard = (a.d.flags & TAP_F_HARD) != 0;
     const size_t tile = (size_t)a.d.W * a.d.L * sizeof(int32_t) * (hard ? 4 : 1);
-    int waves = TAP_BLOCK / 64;
-    while (waves > 1 && (size_t)waves * tile > tap_lds_limit(ctx)) waves >>= 1;
+    const int waves = tap_wave_kernels_off() ? 0 : tap_waves_per_wg(ctx, tile);
     const size_t lds = (size_t)waves * tile;
-    if (lds > tap_lds_limit(ctx) || tap_wave_kernels_off())
+    if (waves == 0)
         return tap_fail(ctx, TAP_E_UNSUPPORTED, "whole episodes of %d x %d containers%s: the height-map tile does not fit a workgroup's "
                                                 "LDS, step them with tap_env_step_gather", a.d.W, a.d.L, hard ? " with hard rewards" : "");
     const dim3 g((a.B + waves - 1) / waves);
@@ -999,38 +903,15 @@ int tap_big_episode(tap_ctx *ctx, const EpisodeArgs &a, hipStream_t st)
     return TAP_OK;
 }
 
-// get_heightmap's feature of the current maps (tools.py:3716-3744), one wavefront per container, lanes over the cells
-// (it was one thread per container until the end of round 4: 74 .. 340 us per call at 10x10 .. 20x20, more than the
-// MACS 3D placement it follows)
+// get_heightmap's feature of the current maps, one wavefront per container, lanes over the cells (it was one thread per
+// container until the end of round 4: 74 .. 340 us per call at 10x10 .. 20x20, more than the MACS 3D placement it follows)
 __global__ void __launch_bounds__(TAP_BLOCK) k_big_feature(tap_env_desc d, EnvView v, float *out, int flen)
 {
     const int lane = threadIdx.x & 63;
     const int env = (int)(((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
     if (env >= d.B) return;                                                       // wave-uniform
-    const int W = d.W, L = d.L, cells = W * L;
-    const int32_t *hm = v.hm + (size_t)env * cells;
-    float *o = out + (size_t)env * flen;
-    if (d.feature == TAP_FEAT_DIFF) {
-        if (d.D == 2) { for (int c = lane; c + 1 < W; c += 64) o[c] = (float)(hm[c + 1] - hm[c]); }
-        else {
-            int x = lane / L, y = lane - x * L;
-            const int dx = 64 / L, dy = 64 - dx * L;
-            for (int c = lane; c < cells; c += 64) {
-                o[c] = (float)(x > 0 ? hm[c] - hm[c - L] : 0);
-                o[cells + c] = (float)(y > 0 ? hm[c] - hm[c - 1] : 0);
-                x += dx; y += dy;
-                if (y >= L) { y -= L; ++x; }
-            }
-        }
-        return;
-    }
-    int mn = 0;
-    if (d.feature == TAP_FEAT_ZERO) {
-        mn = INT_MAX;
-        for (int c = lane; c < cells; c += 64) mn = min(mn, hm[c]);
-        mn = group_min<64>(mn);
-    }
-    for (int c = lane; c < cells; c += 64) o[c] = (float)(hm[c] - mn);
+    tap_seam_feature(d.feature, d.D, d.W, d.L, v.hm + (size_t)env * d.W * d.L, out + (size_t)env * flen, lane, 64,
+                     [](int v) { return group_min<64>(v); });
 }
 
 int tap_big_step(tap_ctx *ctx, const StepArgs &a, void *state, hipStream_t st)
@@ -1041,10 +922,9 @@ int tap_big_step(tap_ctx *ctx, const StepArgs &a, void *state, hipStream_t st)
     if (a.d.W * a.d.L > TAP_BIG_WAVE_CELLS) return big_wg_step(ctx, a, st);     // one workgroup per container
     const bool hard = (a.d.flags & TAP_F_HARD) != 0;
     const size_t tile = (size_t)a.d.W * a.d.L * sizeof(int32_t) * (hard ? 4 : 1);
-    int waves = TAP_BLOCK / 64;                                                  // per workgroup: as many as the LDS holds tiles for
-    while (waves > 1 && (size_t)waves * tile > tap_lds_limit(ctx)) waves >>= 1;
+    const int waves = tap_wave_kernels_off() ? 0 : tap_waves_per_wg(ctx, tile);
     const size_t lds = (size_t)waves * tile;
-    if (lds <= tap_lds_limit(ctx) && !tap_wave_kernels_off()) {                  // one wavefront per container
+    if (waves > 0) {                                                             // one wavefront per container
         const dim3 g((a.d.B + waves - 1) / waves);
         if (hard) {
             TAP_HIP_CHECK(ctx, tap_allow_lds(k_big_wave_step<true>, lds));

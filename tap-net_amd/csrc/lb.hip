@@ -8,12 +8,13 @@
 // The state is therefore the reference's own: the voxel grid (block ids, -1 under covered holes) and the
 // per-level lists of free x corners with their insertion order (the walk over a list BREAKS at the first entry
 // that does not fit, :1662).  One thread steps one container; everything lives in the container's slice of
-// the state blob.  Quirks kept: Container never stores the returned bounding box (tools.py:3706), so
+// the state blob; fetch, admission, commit and feature are tap_step_seam.h's.  Quirks kept: Container never stores the returned bounding box (tools.py:3706), so
 // "compactness" is valid / ((z + bz) * W * L) of the candidate alone; the spaces on top of earlier blocks are
 // only tested against z + zz < H, so a block can reach above H -- the reference's list update then raises
 // IndexError (:1744): error bit 1.
 #include "tap_common.h"
 #include "tap_place.h"
+#include "tap_step_seam.h"
 
 struct LbView {
     int W, L, H, D, cap;
@@ -81,30 +82,19 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_lb_step(StepArgs a, int16_t *vox,
     const int B = a.d.B;
     if (env < 0) return;
     const int D = a.d.D, W = a.d.W, L = a.d.L, H = a.d.H, cells = W * L;
-    int dims[3] = {1, 1, 1};
+    const SeamBlock b = tap_seam_fetch(a, env);
+    const int bx = b.bx, by = b.by, bz = b.bz;
+    bool act;
+    Counters cnt = tap_seam_load(a, env, false, act);
     int err = 0;
-    if (a.static_) {                                                 // gather of model.py:404-412
-        bool badp;
-        const long p = tap_col((long)a.ptr[env], a.nR, badp);
-        for (int k = 0; k < D; ++k) dims[k] = badp ? 0 : (int)a.static_[((size_t)env * a.static_rows + 1 + k) * a.nR + p];
-    } else if (a.blocks_dtype == TAP_DT_F32) {
-        for (int k = 0; k < D; ++k) dims[k] = (int)((const float *)a.blocks)[(size_t)env * D + k];
-    } else {
-        for (int k = 0; k < D; ++k) dims[k] = ((const int32_t *)a.blocks)[(size_t)env * D + k];
-    }
-    const bool act = !a.active || a.active[env] != 0;
-    const int4 cv = reinterpret_cast<const int4 *>(a.v.cnt)[env];
-    Counters cnt = {cv.x, cv.y, cv.z, cv.w};
-    const int bx = dims[0], by = D == 3 ? dims[1] : 1, bz = dims[D - 1];
-    bool do_step = act;
-    if (act && cnt.count >= a.d.n_max) { err |= 2; do_step = false; }
-    if (act && (bx < 1 || by < 1 || bz < 1)) { err |= 4; do_step = false; }
+    const bool do_step = tap_seam_admit(act, cnt.count, a.d.n_max, bx, by, bz, false, err);   // legacy LB: no limit of its own
+    const int idx = cnt.count;
+    Placement pl = {0, 0, 0, 0, 0};
     int32_t *hm = a.v.hm + (size_t)env * cells;
     if (do_step) {
         const LbView s = {W, L, H, D, cap, vox + (size_t)env * cells * H, lfs + (size_t)env * H * L * cap,
                           lfn + (size_t)env * H * L};
         const PlaceCfg cfg = {W, L, H, a.d.flags, a.lut};
-        const int idx = cnt.count;
         cnt.valid += bx * by * bz;                                   // :1656, :1805
         LbBest best = {0, 0, 0, 0, 0, 0, 0.0};
         // corners from the level lists (:1659-1666, :1808-1820)
@@ -222,34 +212,12 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_lb_step(StepArgs a, int16_t *vox,
             else
                 for (int i = 0; i < bx; ++i) for (int j = 0; j < by; ++j) hm[(px + i) * L + py + j] = pz + bz;   // :1756, :1910
         }
-        const size_t o = (size_t)idx * D * B + env;
-        a.v.pos[o] = px;
-        if (D == 3) a.v.pos[o + B] = py;
-        a.v.pos[o + (size_t)(D - 1) * B] = pz;
-        a.v.blk[o] = bx;
-        if (D == 3) a.v.blk[o + B] = by;
-        a.v.blk[o + (size_t)(D - 1) * B] = bz;
-        a.v.stable[(size_t)idx * B + env] = (uint8_t)pst;
+        pl = Placement{best.found, px, py, pz, pst};
         cnt.count += 1;                                              // tools.py:3713
-        reinterpret_cast<int4 *>(a.v.cnt)[env] = make_int4(cnt.valid, cnt.empty, cnt.nstable, cnt.count);
     }
-    if (err) a.v.err[env] |= err;
-    if (a.feature_out) {                                             // tools.py:3716-3744
-        float *out = a.feature_out + (size_t)env * a.flen;
-        if (a.d.feature == TAP_FEAT_DIFF) {
-            if (D == 2) { for (int c = 0; c + 1 < W; ++c) out[c] = (float)(hm[c + 1] - hm[c]); }
-            else
-                for (int c = 0; c < cells; ++c) {
-                    const int x = c / L, y = c - x * L;
-                    out[c] = (float)(x > 0 ? hm[c] - hm[c - L] : 0);
-                    out[cells + c] = (float)(y > 0 ? hm[c] - hm[c - 1] : 0);
-                }
-        } else {
-            int mn = 0;
-            if (a.d.feature == TAP_FEAT_ZERO) { mn = INT_MAX; for (int c = 0; c < cells; ++c) mn = min(mn, hm[c]); }
-            for (int c = 0; c < cells; ++c) out[c] = (float)(hm[c] - mn);
-        }
-    }
+    const SeamHist hist = {bx, by, bz};                              // the corners of the later steps (:1668, :1822)
+    tap_seam_commit(a, env, do_step, false, cnt, idx, pl, err, &hist);
+    if (a.feature_out) tap_seam_feature(a.d.feature, D, W, L, hm, a.feature_out + (size_t)env * a.flen, 0, 1, [](int v) { return v; });
 }
 
 int tap_lb_step(tap_ctx *ctx, const StepArgs &a, void *state, hipStream_t st)

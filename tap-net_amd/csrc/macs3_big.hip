@@ -3,7 +3,8 @@
 // model.py:279).  ONE WAVEFRONT per container (tap_macs3_wave.h: the serial algorithm of tap_macs3_big.h run wave-uniformly on
 // the container's LDS tile, its long loops shared by the lanes), on the same reduced state as the lane kernel (height-map,
 // placement history, the free-list bit-grid in `occ`); one THREAD per container with the lists in the blob's scratch
-// section when the tile does not fit the LDS.  gfx950 only.
+// section when the tile does not fit the LDS.  Block fetch, admission, commit and feature of the step kernels are
+// tap_step_seam.h's.  gfx950 only.
 #include "tap_common.h"
 #include "tap_place.h"
 #include "tap_macs3_big.h"
@@ -11,6 +12,7 @@
 #include "tap_masks.h"
 #include "tap_transition.h"
 #include "tap_episode.h"
+#include "tap_step_seam.h"
 
 static_assert(M3B_F_HARD == TAP_F_HARD && M3B_F_USE_P == TAP_F_USE_P && M3B_F_USE_S == TAP_F_USE_S &&
               M3B_F_ZERO == TAP_F_MCS_ZERO && M3B_F_TIE == TAP_F_MCS_TIE, "flag bits are passed through");
@@ -20,6 +22,14 @@ static_assert(M3B_F_HARD == TAP_F_HARD && M3B_F_USE_P == TAP_F_USE_P && M3B_F_US
 __host__ __device__ inline int macs3_big_cap(int n_max) { return 128 + 8 * n_max; }
 
 // scratch ints per container: ems[cap] (2 ints each) | lev[cells] | slots[cells] | lvh[n_max + 2] | lvr[n_max + 2]
+// MACS 3D's own limit on a block (the step seam's `family_rejects`).  Sides larger than the container are rejected as
+// invalid input, as in tap_macs3.h (the reference keeps such a block in its history at (0,0,0) and its later slices run
+// out of range, tools.py:2858, 2914); footprints above 16 x 16 are beyond the stability test (tap_stable_wide.h)
+__device__ __forceinline__ bool macs3_rejects(int W, int L, int bx, int by)
+{
+    return bx > W || by > L || bx > TAP_WIDE_MAX_SIDE || by > TAP_WIDE_MAX_SIDE;
+}
+
 size_t tap_macs3_big_scratch_ints(const tap_env_desc *d)
 {
     return (size_t)2 * macs3_big_cap(d->n_max) + (size_t)2 * d->W * d->L + (size_t)2 * (d->n_max + 2);
@@ -30,32 +40,16 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_macs3d_big_step(StepArgs a, int32
     const int env = tap_spread_env(lpw, a.d.B);                                  // containers spread over the waves (tap_common.h)
     const int B = a.d.B, W = a.d.W, L = a.d.L, H = a.d.H, cells = W * L;
     if (env < 0) return;
-    int bx, by, bz;
-    if (a.static_) {                                                             // model.py:404-412
-        bool badp;
-        const long p = tap_col((long)a.ptr[env], a.nR, badp);
-        bx = badp ? 0 : (int)a.static_[((size_t)env * a.static_rows + 1) * a.nR + p];
-        by = badp ? 0 : (int)a.static_[((size_t)env * a.static_rows + 2) * a.nR + p];
-        bz = badp ? 0 : (int)a.static_[((size_t)env * a.static_rows + 3) * a.nR + p];
-    } else if (a.blocks_dtype == TAP_DT_F32) {
-        const float *b = (const float *)a.blocks + (size_t)env * 3;
-        bx = (int)b[0]; by = (int)b[1]; bz = (int)b[2];
-    } else {
-        const int32_t *b = (const int32_t *)a.blocks + (size_t)env * 3;
-        bx = b[0]; by = b[1]; bz = b[2];
-    }
-    const bool act = !a.active || a.active[env] != 0;
-    const int4 cv = reinterpret_cast<const int4 *>(a.v.cnt)[env];
-    int cnt[4] = {cv.x, cv.y, cv.z, cv.w};
+    const SeamBlock b = tap_seam_fetch(a, env);
+    const int bx = b.bx, by = b.by, bz = b.bz;
+    bool act;
+    Counters c = tap_seam_load(a, env, false, act);
     int err = 0;
-    bool do_step = act;
-    if (act && cnt[3] >= a.d.n_max) { err |= 2; do_step = false; }               // tools.py:3677 IndexError
-    // sides larger than the container are rejected as invalid input, as in tap_macs3.h (the reference keeps such a
-    // block in its history at (0,0,0) and its later slices run out of range, tools.py:2858, 2914); footprints above
-    // 8 x 8 are beyond the support mask of the stability test
-    if (act && (bx < 1 || by < 1 || bz < 1 || bx > W || by > L || bx > TAP_WIDE_MAX_SIDE || by > TAP_WIDE_MAX_SIDE)) { err |= 4; do_step = false; }
+    const bool do_step = tap_seam_admit(act, c.count, a.d.n_max, bx, by, bz, macs3_rejects(W, L, bx, by), err);
+    const int step = c.count;
+    Placement pl = {0, 0, 0, 0, 0};
     if (do_step) {
-        const int step = cnt[3], cap = macs3_big_cap(a.d.n_max);
+        const int cap = macs3_big_cap(a.d.n_max);
         int32_t *sc = scratch + (size_t)env * scratch_ints;
         M3BState s;
         s.W = W; s.L = L; s.H = H; s.HW = (H + 63) / 64; s.flags = a.d.flags; s.cap = cap; s.step = step;
@@ -68,19 +62,14 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_macs3d_big_step(StepArgs a, int32
         s.lvh = s.slots + cells;
         s.lvr = s.lvh + a.d.n_max + 2;
         const uint32_t *lut = a.lut;
+        int cnt[4] = {c.valid, c.empty, c.nstable, c.count};                     // (tap_macs3_big.h also compiles for the host)
         const M3BResult r = m3b_place(s, cnt, err, bx, by, bz,
                                       [lut](int fx, int fy, m3b_u64 eq) -> int { return tap_stable3d_any(lut, fx, fy, eq); });
-        cnt[3] += 1;                                                             // tools.py:3713
-        reinterpret_cast<int4 *>(a.v.cnt)[env] = make_int4(cnt[0], cnt[1], cnt[2], cnt[3]);
-        a.v.pos[(size_t)(step * 3) * B + env] = r.x;
-        a.v.pos[(size_t)(step * 3 + 1) * B + env] = r.y;
-        a.v.pos[(size_t)(step * 3 + 2) * B + env] = r.z;
-        a.v.stable[(size_t)step * B + env] = (uint8_t)r.stab;
-        a.v.blk[(size_t)(step * 3) * B + env] = bx | (r.placed << 16);          // history of later steps
-        a.v.blk[(size_t)(step * 3 + 1) * B + env] = by;                          // (tools.py:2843-2846), failures too
-        a.v.blk[(size_t)(step * 3 + 2) * B + env] = bz;
+        c = Counters{cnt[0], cnt[1], cnt[2], cnt[3] + 1};                        // tools.py:3713
+        pl = Placement{r.placed, r.x, r.y, r.z, r.stab};
     }
-    if (err) a.v.err[env] |= err;
+    const SeamHist hist = {bx | (pl.placed << 16), by, bz};                      // failures too (tools.py:2843-2846)
+    tap_seam_commit(a, env, do_step, false, c, step, pl, err, &hist);
 }
 
 // ---- one WAVEFRONT per container (tap_macs3_wave.h): the container's working set in the wave's LDS tile ---------------
@@ -100,84 +89,46 @@ __device__ __forceinline__ M3WTile macs3d_wave_tile(m3b_u64 *base, int W, int L,
     return s;
 }
 
-// one MACS 3D step of container `env` by one wavefront (every lane calls; env < B); base = the wave's LDS tile: load the
-// state into the tile, place on the tile (m3w_place), store state / feature
-__device__ __forceinline__ void macs3d_wave_body(const StepArgs &a, int env, int lane, m3b_u64 *base)
+// one MACS 3D step of container `env` by one wavefront (every lane calls; env < B); base = the wave's LDS tile: load
+// tile, fetch, admit, place on the tile (m3w_place), commit, feature; aux: the fused step, which also writes the gather's
+// by-products
+__device__ __forceinline__ void macs3d_wave_body(const StepArgs &a, int env, int lane, m3b_u64 *base, bool aux)
 {
     const int B = a.d.B, W = a.d.W, L = a.d.L, H = a.d.H, cells = W * L, HW = (H + 63) / 64;
     int32_t *hpos, *hblk;                                                        // one round trip for all of the history
     M3WTile s = macs3d_wave_tile(base, W, L, H, a.d.flags, a.d.n_max, hpos, hblk);
     int32_t *ghm = a.v.hm + (size_t)env * cells;
     m3b_u64 *gocc = a.v.occ + (size_t)env * cells * HW;
-    for (int c = lane; c < cells; c += 64) s.hm[c] = ghm[c];
-    {
-        const int nh = 3 * min(reinterpret_cast<const int4 *>(a.v.cnt)[env].w, a.d.n_max);
-        for (int k = lane; k < nh; k += 64) { hpos[k] = a.v.pos[(size_t)k * B + env]; hblk[k] = a.v.blk[(size_t)k * B + env]; }
-    }
+    bool act;
+    Counters c = tap_seam_load(a, env, false, act);
+    for (int k = lane; k < cells; k += 64) s.hm[k] = ghm[k];
+    for (int k = lane; k < 3 * min(c.count, a.d.n_max); k += 64) { hpos[k] = a.v.pos[(size_t)k * B + env]; hblk[k] = a.v.blk[(size_t)k * B + env]; }
     for (int k = lane; k < cells * HW; k += 64) s.occ[k] = gocc[k];
-    int bx, by, bz;
-    if (a.static_) {                                                             // model.py:404-412
-        bool badp;
-        const long p = tap_col((long)a.ptr[env], a.nR, badp);
-        bx = badp ? 0 : (int)a.static_[((size_t)env * a.static_rows + 1) * a.nR + p];
-        by = badp ? 0 : (int)a.static_[((size_t)env * a.static_rows + 2) * a.nR + p];
-        bz = badp ? 0 : (int)a.static_[((size_t)env * a.static_rows + 3) * a.nR + p];
-    } else if (a.blocks_dtype == TAP_DT_F32) {
-        const float *b = (const float *)a.blocks + (size_t)env * 3;
-        bx = (int)b[0]; by = (int)b[1]; bz = (int)b[2];
-    } else {
-        const int32_t *b = (const int32_t *)a.blocks + (size_t)env * 3;
-        bx = b[0]; by = b[1]; bz = b[2];
-    }
-    const bool act = !a.active || a.active[env] != 0;
-    const int4 cv = reinterpret_cast<const int4 *>(a.v.cnt)[env];
-    int cnt[4] = {cv.x, cv.y, cv.z, cv.w};
+    const SeamBlock b = tap_seam_fetch(a, env);
+    if (aux && lane == 0) tap_seam_aux(a, env, b);
+    const int bx = b.bx, by = b.by, bz = b.bz;
     int err = 0;
-    bool do_step = act;
-    if (act && cnt[3] >= a.d.n_max) { err |= 2; do_step = false; }                   // tools.py:3677 IndexError
-    if (act && (bx < 1 || by < 1 || bz < 1 || bx > W || by > L || bx > TAP_WIDE_MAX_SIDE || by > TAP_WIDE_MAX_SIDE)) { err |= 4; do_step = false; }   // as k_macs3d_big_step
+    const bool do_step = tap_seam_admit(act, c.count, a.d.n_max, bx, by, bz, macs3_rejects(W, L, bx, by), err);
+    const int step = c.count;
+    Placement pl = {0, 0, 0, 0, 0};
     tap_wave_lds_sync();
     if (do_step) {                                                               // wave-uniform
-        const int step = cnt[3];
         s.step = step;
+        int cnt[4] = {c.valid, c.empty, c.nstable, c.count};                     // (tap_macs3_big.h also compiles for the host)
         const M3BResult r = m3w_place(s, cnt, err, bx, by, bz, a.lut, lane);
-        cnt[3] += 1;                                                             // tools.py:3713
+        c = Counters{cnt[0], cnt[1], cnt[2], cnt[3] + 1};                        // tools.py:3713
+        pl = Placement{r.placed, r.x, r.y, r.z, r.stab};
         tap_wave_lds_sync();
-        for (int c = lane; c < cells; c += 64) ghm[c] = s.hm[c];
+        for (int k = lane; k < cells; k += 64) ghm[k] = s.hm[k];
         for (int k = lane; k < cells * HW; k += 64) gocc[k] = s.occ[k];
-        if (lane == 0) {
-            reinterpret_cast<int4 *>(a.v.cnt)[env] = make_int4(cnt[0], cnt[1], cnt[2], cnt[3]);
-            a.v.pos[(size_t)(step * 3) * B + env] = r.x;
-            a.v.pos[(size_t)(step * 3 + 1) * B + env] = r.y;
-            a.v.pos[(size_t)(step * 3 + 2) * B + env] = r.z;
-            a.v.stable[(size_t)step * B + env] = (uint8_t)r.stab;
-            a.v.blk[(size_t)(step * 3) * B + env] = bx | (r.placed << 16);      // history of later steps
-            a.v.blk[(size_t)(step * 3 + 1) * B + env] = by;                      // (tools.py:2843-2846), failures too
-            a.v.blk[(size_t)(step * 3 + 2) * B + env] = bz;
-        }
     }
-    if (lane == 0 && err) a.v.err[env] |= err;
-    if (a.feature_out) {                                                         // get_heightmap's feature of the new map (tools.py:3716-3744), from the tile
+    if (lane == 0) {
+        const SeamHist hist = {bx | (pl.placed << 16), by, bz};                  // failures too (tools.py:2843-2846)
+        tap_seam_commit(a, env, do_step, false, c, step, pl, err, &hist);
+    }
+    if (a.feature_out) {                                                         // of the new map, from the tile
         tap_wave_lds_sync();
-        float *o = a.feature_out + (size_t)env * a.flen;
-        if (a.d.feature == TAP_FEAT_DIFF) {
-            int x = lane / L, y = lane - x * L;
-            const int dx = 64 / L, dy = 64 - dx * L;
-            for (int c = lane; c < cells; c += 64) {
-                o[c] = (float)(x > 0 ? s.hm[c] - s.hm[c - L] : 0);
-                o[cells + c] = (float)(y > 0 ? s.hm[c] - s.hm[c - 1] : 0);
-                x += dx; y += dy;
-                if (y >= L) { y -= L; ++x; }
-            }
-        } else {
-            int mn = 0;
-            if (a.d.feature == TAP_FEAT_ZERO) {
-                mn = INT_MAX;
-                for (int c = lane; c < cells; c += 64) mn = min(mn, s.hm[c]);
-                mn = group_min<64>(mn);
-            }
-            for (int c = lane; c < cells; c += 64) o[c] = (float)(s.hm[c] - mn);
-        }
+        tap_seam_feature(a.d.feature, 3, W, L, s.hm, a.feature_out + (size_t)env * a.flen, lane, 64, [](int v) { return group_min<64>(v); });
     }
 }
 
@@ -210,8 +161,10 @@ __device__ __forceinline__ void macs3d_wave_episode_body(const EpisodeArgs &a, i
             const int t = t0 + j;
             const int bx = __shfl(mine[0], j), by = __shfl(mine[1], j), bz = __shfl(mine[2], j);
             const bool in = __shfl((int)min_, j) != 0;
+            // (not tap_seam_admit: with it the loop around the placement was allocated 163 instead of 169 VGPRs and the 10 x 10
+            // episodes measured 1 % (loose) and 3 % (tight build) slower; the tile holds n entries: never full)
             bool do_step = in;
-            if (in && (bx < 1 || by < 1 || bz < 1 || bx > W || by > L || bx > TAP_WIDE_MAX_SIDE || by > TAP_WIDE_MAX_SIDE)) { err |= 4; do_step = false; }   // as k_macs3d_wave_step
+            if (in && (bx < 1 || by < 1 || bz < 1 || bx > W || by > L || bx > TAP_WIDE_MAX_SIDE || by > TAP_WIDE_MAX_SIDE)) { err |= 4; do_step = false; }   // = macs3_rejects
             M3BResult r = {0, 0, 0, 0, 0};
             if (do_step) {                                                        // wave-uniform
                 const int step = cnt[3];
@@ -242,7 +195,7 @@ __device__ __forceinline__ void macs3d_wave_episode_body(const EpisodeArgs &a, i
 }
 
 // Two builds of the same body.  Left alone the compiler takes 169 VGPRs for the loop around the placement (the step
-// kernel: 125), which is the faster code but lets a SIMD hold two waves; held to four waves per SIMD it takes 128 and
+// kernel: 127), which is the faster code but lets a SIMD hold two waves; held to four waves per SIMD it takes 128 and
 // spills 14.  Measured (profiles/macs_wave_episode.json, ms per episode, loose / tight): 10 x 10, n = 10, B = 128
 // 0.84 / 0.90, B = 4 096 1.79 / 1.20 (stepped: 1.59); 20 x 20, n = 30, B = 128 11.6 / 13.2, B = 4 096 23.6 / 26.6.
 // The launcher takes the tight one only when more than two waves per SIMD would be resident (macs3d_episode_tight).
@@ -277,9 +230,8 @@ int tap_macs3_wave_episode(tap_ctx *ctx, const EpisodeArgs &a, hipStream_t st)
     if (a.B == 0) return TAP_OK;
     if (a.n > TAP_WAVE_EPISODE_MAX_N) return tap_fail(ctx, TAP_E_UNSUPPORTED, "whole MACS / MUL episodes of more than %d blocks: step them with tap_env_step_gather", TAP_WAVE_EPISODE_MAX_N);
     const size_t tile_u64 = m3w_tile_u64(a.d.W * a.d.L, (a.d.H + 63) / 64, a.n, macs3_big_cap(a.n)), tile = tile_u64 * 8;
-    int waves = TAP_BLOCK / 64;
-    while (waves > 1 && (size_t)waves * tile > tap_lds_limit(ctx)) waves >>= 1;
-    if ((size_t)waves * tile > tap_lds_limit(ctx) || tap_wave_kernels_off())
+    const int waves = tap_wave_kernels_off() ? 0 : tap_waves_per_wg(ctx, tile);
+    if (waves == 0)
         return tap_fail(ctx, TAP_E_UNSUPPORTED, "whole MACS / MUL episodes of %d x %d x %d containers, %d blocks: %s, step them with tap_env_step_gather",
                         a.d.W, a.d.L, a.d.H, a.n, tap_wave_kernels_off() ? "the wave kernels are switched off" : "the container's tile does not fit a workgroup's LDS");
     const bool tight = macs3d_episode_tight(ctx, a.B, waves, tile);
@@ -298,7 +250,7 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_macs3d_wave_step(StepArgs a)
     const int env = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
     if (env >= a.d.B) return;                                                     // wave-uniform
     const int cells = a.d.W * a.d.L, HW = (a.d.H + 63) / 64;
-    macs3d_wave_body(a, env, lane, m3w_lds + (size_t)wave_in_wg * m3w_tile_u64(cells, HW, a.d.n_max, macs3_big_cap(a.d.n_max)));
+    macs3d_wave_body(a, env, lane, m3w_lds + (size_t)wave_in_wg * m3w_tile_u64(cells, HW, a.d.n_max, macs3_big_cap(a.d.n_max)), false);
 }
 
 // The decoding step in ONE launch (round 5): a container's wavefront runs update_dynamic + update_mask of its own
@@ -315,15 +267,7 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_macs3d_wave_transition(TransArgs 
     // occupy wave slots at this kernel's register count: with 4 + 2 waves per workgroup a CU held 8 placement waves
     // instead of 16 and the step took 218 against 148 us (MACS 3D 10 x 10, B = 4 096, round 5).
     trans_stream_wave<1, NC, MODE>(a.m, env, lane, reinterpret_cast<float *>(m3w_lds + (size_t)PW * tile_u64) + (size_t)wave * 3 * a.m.nR);
-    if (lane == 0 && a.s.static_ && (a.s.dec_static_out || a.s.tour_out || a.s.picked_out)) {   // the gather's by-products
-        bool badp;
-        const long praw = (long)a.s.ptr[env];
-        const long p = tap_col(praw, a.s.nR, badp);
-        float fv[3] = {0.f, 0.f, 0.f};
-        for (int k = 0; k < a.s.d.D; ++k) fv[k] = badp ? 0.f : a.s.static_[((size_t)env * a.s.static_rows + 1 + k) * a.s.nR + p];
-        tap_step_aux(a.s, env, a.s.d.D, fv, praw);
-    }
-    macs3d_wave_body(a.s, env, lane, m3w_lds + (size_t)wave * tile_u64);
+    macs3d_wave_body(a.s, env, lane, m3w_lds + (size_t)wave * tile_u64, true);
 }
 
 static int macs3d_transition_pw(const tap_ctx *ctx, const tap_env_desc *d, int nR)
@@ -362,9 +306,8 @@ int tap_macs3_big_step(tap_ctx *ctx, const StepArgs &a, hipStream_t st)
     {   // one wavefront per container when its working set fits a wave's share of the LDS
         const int cells = a.d.W * a.d.L, HW = (a.d.H + 63) / 64;
         const size_t tile = m3w_tile_u64(cells, HW, a.d.n_max, macs3_big_cap(a.d.n_max)) * 8;
-        int waves = TAP_BLOCK / 64;
-        while (waves > 1 && (size_t)waves * tile > tap_lds_limit(ctx)) waves >>= 1;
-        if ((size_t)waves * tile <= tap_lds_limit(ctx) && !tap_wave_kernels_off()) {
+        const int waves = tap_wave_kernels_off() ? 0 : tap_waves_per_wg(ctx, tile);
+        if (waves > 0) {
             TAP_HIP_CHECK(ctx, tap_allow_lds(k_macs3d_wave_step, (size_t)waves * tile));
             hipLaunchKernelGGL(k_macs3d_wave_step, dim3((a.d.B + waves - 1) / waves), dim3(waves * 64), (size_t)waves * tile, st, a);
             TAP_LAUNCH_CHECK(ctx, "k_macs3d_wave_step");                            // (writes the feature itself)

@@ -7,12 +7,14 @@
 // its own columns in global memory (the serial statement of the algorithm; the fallback when a container's tile does not
 // fit the LDS).  No mask is involved, so neither the container nor a block has a width limit beyond the state
 // blob's (W <= 4096).  k_macs2d_wave_episode: a whole episode (tools.calc_positions_mcs) of a container above 64 columns
-// in one launch, the wavefront's tile resident across the placements.  gfx950 only.
+// in one launch, the wavefront's tile resident across the placements.  Block fetch, admission, commit and feature of
+// the step kernels are tap_step_seam.h's.  gfx950 only.
 #include "tap_common.h"
 #include "tap_place.h"
 #include "tap_masks.h"
 #include "tap_transition.h"
 #include "tap_episode.h"
+#include "tap_step_seam.h"
 
 // EMS entries one step can produce: the runs of level 0 (at most (W+1)/2), one run per level z > 0 for which some
 // column of the run has hm == z (a run without such a column is the same run as on the level below and is skipped,
@@ -80,26 +82,12 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_macs2d_big_step(StepArgs a, int32
     const int B = a.d.B, W = a.d.W, H = a.d.H;
     if (env < 0) return;
     int32_t *hm = a.v.hm + (size_t)env * W;
-    const int4 cv = reinterpret_cast<const int4 *>(a.v.cnt)[env];
-    Counters cnt = {cv.x, cv.y, cv.z, cv.w};
-    int bx, bz;
-    if (a.static_) {
-        bool badp;
-        const long p = tap_col((long)a.ptr[env], a.nR, badp);
-        bx = badp ? 0 : (int)a.static_[((size_t)env * a.static_rows + 1) * a.nR + p];
-        bz = badp ? 0 : (int)a.static_[((size_t)env * a.static_rows + 2) * a.nR + p];
-    } else if (a.blocks_dtype == TAP_DT_F32) {
-        bx = (int)((const float *)a.blocks)[(size_t)env * 2];
-        bz = (int)((const float *)a.blocks)[(size_t)env * 2 + 1];
-    } else {
-        bx = ((const int32_t *)a.blocks)[(size_t)env * 2];
-        bz = ((const int32_t *)a.blocks)[(size_t)env * 2 + 1];
-    }
-    const bool act = !a.active || a.active[env] != 0;
+    const SeamBlock b = tap_seam_fetch(a, env);
+    const int bx = b.bx, bz = b.bz;
+    bool act;
+    Counters cnt = tap_seam_load(a, env, false, act);
     int err = 0;
-    bool do_step = act;
-    if (act && cnt.count >= a.d.n_max) { err |= 2; do_step = false; }
-    if (act && (bx < 1 || bz < 1)) { err |= 4; do_step = false; }
+    const bool do_step = tap_seam_admit(act, cnt.count, a.d.n_max, bx, 1, bz, false, err);   // MACS 2D: no limit of its own
     const int step = cnt.count;
     Placement res = {0, 0, 0, 0, 0};
 
@@ -242,28 +230,9 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_macs2d_big_step(StepArgs a, int32
 #undef MB_PUSH
     }
 
-    if (a.feature_out) {                                                      // tools.py:3716-3744
-        float *out = a.feature_out + (size_t)env * a.flen;
-        if (a.d.feature == TAP_FEAT_DIFF) {
-            for (int k = 0; k + 1 < W; ++k) out[k] = (float)(hm[k + 1] - hm[k]);
-        } else {
-            int mn = 0;
-            if (a.d.feature == TAP_FEAT_ZERO) {
-                mn = INT_MAX;
-                for (int k = 0; k < W; ++k) mn = min(mn, hm[k]);
-            }
-            for (int k = 0; k < W; ++k) out[k] = (float)(hm[k] - mn);
-        }
-    }
-    if (do_step) {
-        reinterpret_cast<int4 *>(a.v.cnt)[env] = make_int4(cnt.valid, cnt.empty, cnt.nstable, cnt.count);
-        a.v.pos[(size_t)(step * 2) * B + env] = res.x;
-        a.v.pos[(size_t)(step * 2 + 1) * B + env] = res.z;
-        a.v.stable[(size_t)step * B + env] = (uint8_t)res.stab;
-        a.v.blk[(size_t)(step * 2) * B + env] = bx;                           // history the later steps read
-        a.v.blk[(size_t)(step * 2 + 1) * B + env] = bz;                       // (tools.py:2531-2533), failures too
-    }
-    if (err) a.v.err[env] |= err;
+    const SeamHist hist = {bx, 1, bz};                                         // failures too (tools.py:2531-2533)
+    tap_seam_commit(a, env, do_step, false, cnt, step, res, err, &hist);
+    if (a.feature_out) tap_seam_feature(a.d.feature, 2, W, 1, hm, a.feature_out + (size_t)env * a.flen, 0, 1, [](int v) { return v; });
 }
 
 // ---- one WAVEFRONT per container (round 4) ------------------------------------------------------------------------------
@@ -571,9 +540,10 @@ __device__ __forceinline__ Placement macs2d_wave_place(const Mw2Tile &T, Counter
     return res;
 }
 
-// one MACS 2D step of container `env` by one wavefront (every lane calls; env < B); tile = the wave's LDS tile:
-// load the state into the tile, place on the tile (macs2d_wave_place), store state / feature
-__device__ __forceinline__ void macs2d_wave_body(const StepArgs &a, int cap, int env, int lane, int32_t *tile)
+// one MACS 2D step of container `env` by one wavefront (every lane calls; env < B); tile = the wave's LDS tile: load
+// tile, fetch, admit, place on the tile (macs2d_wave_place), feature, commit; aux: the fused step, which also writes the
+// gather's by-products
+__device__ __forceinline__ void macs2d_wave_body(const StepArgs &a, int cap, int env, int lane, int32_t *tile, bool aux)
 {
     const int B = a.d.B, W = a.d.W;
     const Mw2Tile T = macs2d_wave_tile(tile, W, a.d.H, a.d.flags, cap, a.d.n_max);
@@ -582,26 +552,13 @@ __device__ __forceinline__ void macs2d_wave_body(const StepArgs &a, int cap, int
     int gmax = 0;
     for (int k = lane; k < W; k += 64) { const int h = ghm[k]; hm[k] = h; gmax = max(gmax, h); }
     gmax = mw_max(gmax);
-    const int4 cv = reinterpret_cast<const int4 *>(a.v.cnt)[env];
-    Counters cnt = {cv.x, cv.y, cv.z, cv.w};
-    int bx, bz;
-    if (a.static_) {
-        bool badp;
-        const long p = tap_col((long)a.ptr[env], a.nR, badp);
-        bx = badp ? 0 : (int)a.static_[((size_t)env * a.static_rows + 1) * a.nR + p];
-        bz = badp ? 0 : (int)a.static_[((size_t)env * a.static_rows + 2) * a.nR + p];
-    } else if (a.blocks_dtype == TAP_DT_F32) {
-        bx = (int)((const float *)a.blocks)[(size_t)env * 2];
-        bz = (int)((const float *)a.blocks)[(size_t)env * 2 + 1];
-    } else {
-        bx = ((const int32_t *)a.blocks)[(size_t)env * 2];
-        bz = ((const int32_t *)a.blocks)[(size_t)env * 2 + 1];
-    }
-    const bool act = !a.active || a.active[env] != 0;
+    const SeamBlock b = tap_seam_fetch(a, env);
+    if (aux && lane == 0) tap_seam_aux(a, env, b);
+    const int bx = b.bx, bz = b.bz;
+    bool act;
+    Counters cnt = tap_seam_load(a, env, false, act);
     int err = 0;
-    bool do_step = act;
-    if (act && cnt.count >= a.d.n_max) { err |= 2; do_step = false; }
-    if (act && (bx < 1 || bz < 1)) { err |= 4; do_step = false; }
+    const bool do_step = tap_seam_admit(act, cnt.count, a.d.n_max, bx, 1, bz, false, err);   // MACS 2D: no limit of its own
     const int step = cnt.count;
     Placement res = {0, 0, 0, 0, 0};
     for (int k = lane; k < 2 * min(step, a.d.n_max); k += 64) { T.hpos[k] = a.v.pos[(size_t)k * B + env]; T.hblk[k] = a.v.blk[(size_t)k * B + env]; }   // the history so far, one round trip for all of it
@@ -613,30 +570,11 @@ __device__ __forceinline__ void macs2d_wave_body(const StepArgs &a, int cap, int
             for (int k = res.x + lane; k < res.x + bx; k += 64) ghm[k] = res.z + bz;
     }
 
-    if (a.feature_out) {                                                          // tools.py:3716-3744
-        float *out = a.feature_out + (size_t)env * a.flen;
-        if (a.d.feature == TAP_FEAT_DIFF) {
-            for (int k = lane; k + 1 < W; k += 64) out[k] = (float)(hm[k + 1] - hm[k]);
-        } else {
-            int mn = 0;
-            if (a.d.feature == TAP_FEAT_ZERO) {
-                mn = INT_MAX;
-                for (int k = lane; k < W; k += 64) mn = min(mn, hm[k]);
-                mn = mw_min(mn);
-            }
-            for (int k = lane; k < W; k += 64) out[k] = (float)(hm[k] - mn);
-        }
-    }
+    if (a.feature_out)
+        tap_seam_feature(a.d.feature, 2, W, 1, hm, a.feature_out + (size_t)env * a.flen, lane, 64, [](int v) { return mw_min(v); });
     if (lane == 0) {
-        if (do_step) {
-            reinterpret_cast<int4 *>(a.v.cnt)[env] = make_int4(cnt.valid, cnt.empty, cnt.nstable, cnt.count);
-            a.v.pos[(size_t)(step * 2) * B + env] = res.x;
-            a.v.pos[(size_t)(step * 2 + 1) * B + env] = res.z;
-            a.v.stable[(size_t)step * B + env] = (uint8_t)res.stab;
-            a.v.blk[(size_t)(step * 2) * B + env] = bx;                           // history the later steps read
-            a.v.blk[(size_t)(step * 2 + 1) * B + env] = bz;                       // (tools.py:2531-2533), failures too
-        }
-        if (err) a.v.err[env] |= err;
+        const SeamHist hist = {bx, 1, bz};                                        // failures too (tools.py:2531-2533)
+        tap_seam_commit(a, env, do_step, false, cnt, step, res, err, &hist);
     }
 }
 
@@ -667,8 +605,7 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_macs2d_wave_episode(EpisodeArgs a
             const int t = t0 + j;
             const int bx = __shfl(mine[0], j), bz = __shfl(mine[1], j);
             const bool in = __shfl((int)min_, j) != 0;
-            bool do_step = in;
-            if (in && (bx < 1 || bz < 1)) { err |= 4; do_step = false; }
+            const bool do_step = tap_seam_admit(in, cnt.count, n, bx, 1, bz, false, err);   // (the tile holds n entries: never full)
             Placement pl = {0, 0, 0, 0, 0};
             if (do_step) {                                                        // wave-uniform
                 const int step = cnt.count;
@@ -698,9 +635,8 @@ int tap_macs_wave_episode(tap_ctx *ctx, const EpisodeArgs &a, hipStream_t st)
     if (a.n > TAP_WAVE_EPISODE_MAX_N) return tap_fail(ctx, TAP_E_UNSUPPORTED, "whole MACS / MUL episodes of more than %d blocks: step them with tap_env_step_gather", TAP_WAVE_EPISODE_MAX_N);
     const int cap = macs_big_cap(a.d.W, a.n);
     const size_t tile_ints = macs_wave_tile_ints(a.d.W, cap, a.n), tile = tile_ints * sizeof(int32_t);
-    int waves = TAP_BLOCK / 64;
-    while (waves > 1 && (size_t)waves * tile > tap_lds_limit(ctx)) waves >>= 1;
-    if ((size_t)waves * tile > tap_lds_limit(ctx) || tap_wave_kernels_off())
+    const int waves = tap_wave_kernels_off() ? 0 : tap_waves_per_wg(ctx, tile);
+    if (waves == 0)
         return tap_fail(ctx, TAP_E_UNSUPPORTED, "whole MACS / MUL episodes of %d columns, %d blocks: %s, step them with tap_env_step_gather", a.d.W, a.n,
                         tap_wave_kernels_off() ? "the wave kernels are switched off" : "the container's tile does not fit a workgroup's LDS");
     TAP_HIP_CHECK(ctx, tap_allow_lds(k_macs2d_wave_episode, (size_t)waves * tile));
@@ -716,7 +652,7 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_macs2d_wave_step(StepArgs a, int 
     const int lane = threadIdx.x & 63, wave_in_wg = TAP_WAVE_INDEX();
     const int env = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
     if (env >= a.d.B) return;                                                     // wave-uniform
-    macs2d_wave_body(a, cap, env, lane, mw_lds + (size_t)wave_in_wg * macs_wave_tile_ints(a.d.W, cap, a.d.n_max));
+    macs2d_wave_body(a, cap, env, lane, mw_lds + (size_t)wave_in_wg * macs_wave_tile_ints(a.d.W, cap, a.d.n_max), false);
 }
 
 // The decoding step in ONE launch (round 5): a container's wavefront runs update_dynamic + update_mask of its own
@@ -734,15 +670,7 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_macs2d_wave_transition(TransArgs 
     // occupy wave slots at this kernel's register count: with 4 + 2 waves per workgroup a CU held 8 placement waves
     // instead of 16 and the step took 218 against 148 us (MACS 3D 10 x 10, B = 4 096, round 5).
     trans_stream_wave<1, NC, MODE>(a.m, env, lane, reinterpret_cast<float *>(mw_lds + (size_t)PW * tile_ints) + (size_t)wave * 3 * a.m.nR);
-    if (lane == 0 && a.s.static_ && (a.s.dec_static_out || a.s.tour_out || a.s.picked_out)) {   // the gather's by-products
-        bool badp;
-        const long praw = (long)a.s.ptr[env];
-        const long p = tap_col(praw, a.s.nR, badp);
-        float fv[3] = {0.f, 0.f, 0.f};
-        for (int k = 0; k < a.s.d.D; ++k) fv[k] = badp ? 0.f : a.s.static_[((size_t)env * a.s.static_rows + 1 + k) * a.s.nR + p];
-        tap_step_aux(a.s, env, a.s.d.D, fv, praw);
-    }
-    macs2d_wave_body(a.s, cap, env, lane, mw_lds + (size_t)wave * tile_ints);
+    macs2d_wave_body(a.s, cap, env, lane, mw_lds + (size_t)wave * tile_ints, true);
 }
 
 static int macs2d_transition_pw(const tap_ctx *ctx, const tap_env_desc *d, int nR)
@@ -780,9 +708,8 @@ int tap_macs_wave_step(tap_ctx *ctx, const StepArgs &a, hipStream_t st)
     if (a.d.B == 0) return TAP_OK;
     const int cap = macs_big_cap(a.d.W, a.d.n_max);
     const size_t tile = macs_wave_tile_ints(a.d.W, cap, a.d.n_max) * sizeof(int32_t);
-    int waves = TAP_BLOCK / 64;
-    while (waves > 1 && (size_t)waves * tile > tap_lds_limit(ctx)) waves >>= 1;
-    if ((size_t)waves * tile > tap_lds_limit(ctx) || tap_wave_kernels_off()) return TAP_E_UNSUPPORTED;
+    const int waves = tap_wave_kernels_off() ? 0 : tap_waves_per_wg(ctx, tile);
+    if (waves == 0) return TAP_E_UNSUPPORTED;
     TAP_HIP_CHECK(ctx, tap_allow_lds(k_macs2d_wave_step, (size_t)waves * tile));
     hipLaunchKernelGGL(k_macs2d_wave_step, dim3((a.d.B + waves - 1) / waves), dim3(waves * 64), (size_t)waves * tile, st, a, cap);
     TAP_LAUNCH_CHECK(ctx, "k_macs2d_wave_step");
