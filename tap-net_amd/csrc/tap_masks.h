@@ -392,9 +392,14 @@ __device__ __forceinline__ void stream_wave_fast(const MaskArgs &a, int senv0, i
 // (nR/4) keeps four column words and writes the float4 of rows rsub, rsub + 64/(nR/4), ...: a wave
 // store instruction covers whole consecutive rows.  Requirements: nR % 4 == 0, nR <= 64*NC, rows <= 64.
 // First step of an episode (mask_builds_bits): the column words come from the fp32 slab instead of a stored
-// shadow.  Lane (rsub, c4) reads the float4 of rows rsub, rsub + RP, ... (the mapping it writes with, all
-// loads in flight together), packs "element != 0" into four partial words and ORs them into a wave-private
-// LDS tile of nR words (ds_or_b64); after the wave-level hand-off every lane picks up the words it needs.
+// shadow.  Lane (rsub, c4) reads the float4 of rows rsub, rsub + RP, ... U = 4 row groups at a time, packs
+// "element != 0" into four partial words and ORs them into a wave-private LDS tile of nR words (ds_or_b64);
+// after the wave-level hand-off every lane picks up the words it needs.  NOT one round trip: the row-group loop
+// has a run-time trip count, so the compiler waits vmcnt(0) at its header -- the slab is requested only after
+// the caller's small inputs have arrived, and again after every pass (30 rows: one pass at RP = 12, whose
+// fourth load is a clamped duplicate of row 29; two at RP = 4).  The generic shapes, k_mask_step, the MACS
+// steps and the wave-per-container kernels run this; the compiled-in 10-node windows of the fused LB_GREEDY
+// step do not (stream_wave_first_regs, below).
 template <int NS>
 __device__ __forceinline__ void stream_build_bits(const MaskArgs &a, int senv0, int lane, const bool (&on)[NS],
                                                   unsigned long long *tile /* NS * nR words */)
@@ -406,7 +411,7 @@ __device__ __forceinline__ void stream_build_bits(const MaskArgs &a, int senv0, 
     tap_wave_lds_sync_m();
     int bad = 0;
     // rows <= 64 and RP >= 1: at most 64 / RP row groups; the common shapes (30 rows: RP = 12 or 4) need 3 or 8
-    // loads per lane and slab -- all of a wave's loads (both slabs) are issued before the first is used
+    // loads per lane and slab -- the loads of one pass (both slabs) are issued before the first is used
     constexpr int U = 4;
     for (int r0 = rsub; r0 < rows; r0 += U * RP) {
         float4 v[NS][U];
@@ -451,6 +456,218 @@ __device__ __forceinline__ void stream_build_bits(const MaskArgs &a, int senv0, 
     tap_wave_lds_sync_m();
 }
 
+// ---- first step of an episode on a compiled-in 10-node window: the fp32 tensor stored from the loaded registers ---------
+// (C4S = 5 / 15: 30 rows, nR = 20 / 60.)  stream_build_bits above sits IN FRONT of the expansion: its slab loop has a
+// run-time trip count, so the wait-count pass puts vmcnt(0) at the loop header -- the slab is requested only after ptr /
+// row 0 / mask_in have arrived, 3D windows take a third round trip for the loop's second pass -- and the listing has about
+// 700 instructions (packing under exec masks, ds_or_b64, two LDS hand-offs, the ds_read of the tile, the expansion from
+// bits) between the slab's arrival and the first tensor store.  None of it is needed there: the float4s a lane stores are
+// the float4s it can load.  Here the lane loads, in ONE burst with compile-time trip counts and right behind the small
+// inputs, the elements the later-step expansion makes it store -- same lane role and rotation (stream_lane_role), the run of
+// NS * 30 rows for the run-of-rows form and for one-slab waves, slab by slab otherwise, a load under the guard of its store
+// -- and stores `row cleared ? 0 : x != 0 ? 1 : 0` straight from those registers (-0.0 -> +0.0, NaN and every other
+// non-zero -> 1.0: what the expansion from bits writes).  The compiler waits for the small inputs alone (a counted vmcnt),
+// the pick runs while the slab is in flight, one vmcnt(0) stands in front of the first store.  BEHIND the stores, where the
+// tail overlaps their drain: x != 0 packed into the lane's partial column words (30 rows: 32-bit words), OR-ed over the
+// lanes of a column quad in the wave's LDS tile (ds_or_b32), the words & ~clear written by the first_row lanes, both masks
+// from the per-column words as in the shadow form; elements that are neither 0 nor 1 are flagged per lane and counted on
+// the rare path only.  A lane stores only elements it loaded, after all the wave's loads have returned.
+// -DTAP_FIRST_STEP_LDS: stream_build_bits for these windows too (A/B builds).
+template <int NS, bool MERGED, int C4S>
+__device__ __forceinline__ void stream_wave_first_regs(const MaskArgs &a, int senv0, int lane, const bool (&on)[NS], float *lds)
+{
+    static_assert(C4S == 5 || C4S == 15, "the reference's own 10-node windows: 30 rows, nR = 20 / 60");
+    static_assert(NS <= 2, "a stream wave expands one or two slabs");
+    constexpr int nR = 4 * C4S, C4 = C4S, ROWS = 30, N = 10, RP = 64 / C4S, c4_magic = 65536 / C4S + 1;
+    constexpr bool RUN = NS == 1 || MERGED;                // the wave's rows as one run (the later step's unrolled expansion)
+    constexpr int NU = (ROWS + RP - 1) / RP;               // slab by slab: instructions per slab
+    constexpr int NI = RUN ? (NS * ROWS + RP - 1) / RP + 1 : NS * NU;
+    static_assert(NS * nR <= 64 && NS * nR * sizeof(unsigned) <= NS * 3 * nR * sizeof(float), "the tile fits the wave's LDS and one lane zeroes a word");
+    if (!on[0]) return;                                    // on[] is a prefix and wave-uniform
+    const bool lane_on = lane < RP * C4;
+#ifdef TAP_STREAM_UNALIGNED
+    const LaneRole role = stream_lane_role(lane, 0, C4, RP, c4_magic, 0, 0, 0);
+#else
+    const LaneRole role = stream_lane_role(lane, senv0, C4, RP, c4_magic, a.sb_mul, a.sb_add, 0);
+#endif
+    const bool first_row = role.rsub == 0;
+    unsigned *tile = reinterpret_cast<unsigned *>(lds);    // NS * nR words
+    const void *any = static_cast<const void *>(a.dyn_in); // a readable address for the inputs a caller may leave out
+    const bool has_ptr = a.ptr != nullptr, has_static = a.static_ != nullptr, has_mask = a.mask_in != nullptr;
+    const int64_t *ptrp = has_ptr ? a.ptr : static_cast<const int64_t *>(any);
+    const float *stp = has_static ? a.static_ : static_cast<const float *>(any);
+    const float *mip = has_mask ? a.mask_in : static_cast<const float *>(any);
+    long praw[NS];
+    float row0[NS], keep[NS];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        const int env = on[k] ? senv0 + k : senv0;         // an idle slab re-reads the first one's inputs
+        praw[k] = ptrp[has_ptr ? env : 0];
+        const float *strow = stp + (has_static ? (size_t)env * a.static_rows * nR : (size_t)0);
+        const float *mirow = mip + (has_mask ? (size_t)env * nR : (size_t)0);
+        const unsigned j = (unsigned)min(lane, nR - 1);
+        row0[k] = strow[has_static ? j : 0u];
+        keep[k] = mirow[has_mask ? j : 0u];
+    }
+    // instruction i of the lane: which row of which slab, and whether the lane has it
+    const int non = (NS > 1 && on[NS - 1]) ? 2 : 1, total = non * ROWS;
+    // (i is a constant wherever this is called: the comparisons a slot cannot fail fold away, and the lane's float4 of
+    //  slot i sits a compile-time distance `at` from the pointers src0 / dst0 below)
+    struct Slot { bool ok, up; int r, at; };               // r: row of slab `up`; at: float4s from src0 / dst0
+    auto slot = [&](int i) -> Slot {
+        if constexpr (RUN) {
+            const int ri = role.r0 + RP * i;               // role.r0 in [-RP, RP)
+            const bool lo_ok = i >= 1 || ri >= 0, hi_ok = RP * (i + 1) <= ROWS || ri < total;
+            const bool up = NS > 1 && (RP * (i - 1) >= ROWS || (RP * (i + 1) > ROWS && ri >= ROWS));
+            return Slot{lane_on && lo_ok && hi_ok, up, up ? ri - ROWS : ri, RP * (i - 1) * C4};
+        } else {
+            const int k = i / NU, u = i - k * NU, r = role.rsub + RP * u;
+            return Slot{lane_on && (RP * (u + 1) <= ROWS || r < ROWS) && on[k], k != 0, r, (k * ROWS + RP * u) * C4};
+        }
+    };
+    // the float4 `at` is counted from: the lane's element of slot 1 in a run (always a row of the first slab; the late
+    // lanes of a rotated wave have no slot 0), of slot 0 slab by slab
+    const int first4 = (RUN ? role.r0 + RP : role.rsub) * C4 + role.c4;
+    const float4 *src0 = reinterpret_cast<const float4 *>(a.dyn_in + (size_t)senv0 * ROWS * nR) + first4;
+    float4 x[NI];
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        const Slot s = slot(i);
+        if (s.ok) x[i] = src0[s.at];                       // x[i] is read under s.ok only
+    }
+    float *o_dyn = a.dyn_out, *o_cur = a.cur_out, *o_mask = a.mask_out;
+    unsigned long long *o_bits = a.bits_out;
+    const int o_wt = a.wt;
+    const int jm = (int)((unsigned)min(lane, nR - 1) % (unsigned)N);          // this lane's column mod n (pack.py:314-316)
+    unsigned clr[NS];
+    int pm[NS];
+    // the pick, the block id and the rows it clears, exactly as in stream_wave_bits_r4: scalar for two-slab waves
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        const bool valid_v = on[k] && has_ptr && praw[k] >= 0 && praw[k] < nR;  // no ptr: the initial mask (model.py:297-307)
+#ifdef TAP_STREAM_VPICK
+        constexpr bool SPICK = false;
+#else
+        constexpr bool SPICK = NS > 1;
+#endif
+        bool valid;
+        int p, real;
+        if constexpr (!SPICK) {
+            valid = valid_v;
+            p = valid ? (int)praw[k] : 0;
+            const float t = __shfl(row0[k], p & 63);                          // pack.py:339 via shuffle
+            const float r0 = (valid && has_static) ? t : -1.f;                // nR <= 64: one column per lane
+            real = (r0 > -1.f && r0 < (float)ROWS) ? (int)r0 : -1;            // .long() truncates; a row beyond the tensor clears nothing
+        } else {
+            const int ps = __builtin_amdgcn_readfirstlane(valid_v ? (int)praw[k] : -1);
+            valid = ps >= 0;
+            p = valid ? ps : 0;
+            const float t = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(row0[k]), p & 63));
+            const float r0 = (valid && has_static) ? t : -1.f;
+            real = __builtin_amdgcn_readfirstlane((r0 > -1.f && r0 < (float)ROWS) ? (int)r0 : -1);
+        }
+        unsigned m = 0;                                                       // pack.py:370-374 (update_rows = 3, checked by the launchers)
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const int r = real + N * i;
+            if (real >= 0 && r < ROWS) m |= 1u << r;
+        }
+        clr[k] = m;
+        pm[k] = valid ? (int)((unsigned)p % (unsigned)N) : -1;                // pack.py:314-316; -1 matches no column
+    }
+    __builtin_amdgcn_s_waitcnt(0x0F70);                  // vmcnt(0): the slab is here; nothing is stored before
+#ifdef TAP_PROF
+    TL_STAMP(1);
+#endif
+    if (o_dyn) {
+        float4 *dst0 = reinterpret_cast<float4 *>(o_dyn + (size_t)senv0 * ROWS * nR) + first4;
+        auto run = [&](auto wt_c) {
+#pragma unroll
+            for (int i = 0; i < NI; ++i) {
+                const Slot s = slot(i);
+                if (!s.ok) continue;
+                const float one = (((s.up ? clr[NS - 1] : clr[0]) >> s.r) & 1u) ? 0.f : 1.f;
+                const float4 v = make_float4(x[i].x != 0.f ? one : 0.f, x[i].y != 0.f ? one : 0.f,
+                                             x[i].z != 0.f ? one : 0.f, x[i].w != 0.f ? one : 0.f);
+                store_stream(dst0 + s.at, v, decltype(wt_c)::value);
+            }
+        };
+        if (o_wt) run(std::integral_constant<int, 1>{}); else run(std::integral_constant<int, 0>{});
+    }
+    __builtin_amdgcn_sched_barrier(0);                   // everything below stays behind the stores
+    if (lane < NS * nR) tile[lane] = 0u;
+    unsigned pw[NS][4];
+#pragma unroll
+    for (int k = 0; k < NS; ++k)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) pw[k][q] = 0u;
+    bool bad = false;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        const Slot s = slot(i);
+        if (!s.ok) continue;
+        const float e[4] = {x[i].x, x[i].y, x[i].z, x[i].w};
+        const unsigned rowbit = 1u << s.r;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const bool nz = e[q] != 0.f;
+            bad |= nz && e[q] != 1.f;
+            const unsigned bit = nz ? rowbit : 0u;
+            if constexpr (NS > 1) {
+                pw[0][q] |= s.up ? 0u : bit;
+                pw[1][q] |= s.up ? bit : 0u;
+            } else {
+                pw[0][q] |= bit;
+            }
+        }
+    }
+    tap_wave_lds_sync_m();
+    if (lane_on) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) atomicOr(&tile[k * nR + role.c4 * 4 + q], pw[k][q]);
+    }
+    if (a.nonbinary) {
+        const unsigned long long anyb = __ballot(bad);
+        if (anyb) {                                      // rare: not a 0/1 tensor -- count, cleared rows included
+            int cnt = 0;
+#pragma unroll
+            for (int i = 0; i < NI; ++i) {
+                if (!slot(i).ok) continue;
+                cnt += (x[i].x != 0.f && x[i].x != 1.f) + (x[i].y != 0.f && x[i].y != 1.f) +
+                       (x[i].z != 0.f && x[i].z != 1.f) + (x[i].w != 0.f && x[i].w != 1.f);
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+            if (lane == 0) atomicAdd(a.nonbinary, cnt);
+        }
+    }
+    tap_wave_lds_sync_m();
+    if (lane_on && first_row && o_bits) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+            if (!on[k]) continue;
+            const unsigned *t4 = tile + k * nR + role.c4 * 4;
+            const unsigned keepb = ~clr[k];
+            ulonglong2 *dst = reinterpret_cast<ulonglong2 *>(o_bits + (size_t)(senv0 + k) * nR + role.c4 * 4);
+            dst[0] = make_ulonglong2(t4[0] & keepb, t4[1] & keepb);
+            dst[1] = make_ulonglong2(t4[2] & keepb, t4[3] & keepb);
+        }
+    }
+    constexpr unsigned nmask = (1u << N) - 1u;
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        if (!on[k] || lane >= nR) continue;
+        const int env = senv0 + k;
+        const unsigned nb = tile[k * nR + lane] & ~clr[k];
+        const int move = __popc(nb & nmask), small = __popc((nb >> N) & nmask), large = __popc((nb >> (2 * N)) & nmask);
+        const float kp = (jm == pm[k]) ? 0.f : (has_mask ? keep[k] : 1.f);    // pack.py:320-321
+        if (o_mask) o_mask[(size_t)env * nR + lane] = kp;
+        if (o_cur) o_cur[(size_t)env * nR + lane] = (small * large + move) != 0 ? 0.f : kp; // :327-329
+    }
+}
+
 // BUILD: the words come from the wave's LDS tile (first step, mask_builds_bits) instead of a.bits_in; a
 // compile-time switch so that neither form reads through a generic pointer.
 //
@@ -492,6 +709,13 @@ __device__ __forceinline__ void stream_wave_bits_r4(const MaskArgs &a, int senv0
 {
     static_assert(!(BUILD && INPLACE), "the first step on a fresh tensor writes all of it");
     static_assert(!NOMASK || (FULL && !BUILD && C4S != 0), "the mask wave exists beside the FULL step on a compiled-in shape only");
+#ifndef TAP_FIRST_STEP_LDS                                // A/B builds: the first step through stream_build_bits everywhere
+    if constexpr (BUILD && (C4S == 5 || C4S == 15)) {
+        static_assert(NC == 1 && !FULL, "the compiled-in 10-node windows have one column per lane; FULL is a shadow step's");
+        stream_wave_first_regs<NS, MERGED, C4S>(a, senv0, lane, on_, lds);
+        return;
+    }
+#endif
     bool on[NS];
 #pragma unroll
     for (int k = 0; k < NS; ++k) on[k] = FULL ? true : on_[k];
@@ -849,8 +1073,8 @@ __device__ __forceinline__ void stream_wave_bits_r3(const MaskArgs &a, int senv0
     float row0[NS][NC], keep[NS][NC];
     u64 bj[NS][NC];
     ulonglong2 w[NS][2];
-    // every small input is requested up front (in the first-step form: before the slab is read, so the
-    // step still has one memory round trip)
+    // every small input is requested up front (in the first-step form the slab is read AFTER they have arrived:
+    // stream_build_bits' loop header waits for vmcnt(0) -- two round trips, see there)
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
         const int env = senv0 + k;
