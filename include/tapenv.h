@@ -104,7 +104,7 @@ const char *tap_last_error(const tap_ctx *ctx);
  * hipGraph counts once, at capture.  tap_variant_hits writes up to `cap` rows of 8 ints (the key, then the count) and
  * returns the number of rows the record holds (TAP_E_INVALID if a key found no slot since the last reset);
  * tap_variant_hits_reset empties it. */
-/* The whole-episode and rolling kernels count on the same record, under kinds 16 .. 24 (tap_common.h: TapHitKind), after
+/* The whole-episode and rolling kernels count on the same record, under kinds 16 .. 25 (tap_common.h: TapHitKind; 25: trial.hip), after
  * the stream-wave kinds 0 .. 6.  Their keys, fields (kind, D, G, nc, mode, extra, wt):
  *   16 k_episode<D, G, SOFT>                      (16, D, G, SOFT, 0, 0, 0)
  *   17 k_episode_macs2<G, WIDE>                   (17, 2, G, WIDE, 0, 0, 0)
@@ -119,6 +119,7 @@ const char *tap_last_error(const tap_ctx *ctx);
  *                                                 ENG 1 = tap_env_step_engine
  *   23 k_macs2d_wave_episode                      (23, 2, 64, 0, 0, PW, 0)       PW wavefronts (containers) per workgroup
  *   24 k_macs3d_wave_episode / _tight             (24, 3, 64, 0, TIGHT, PW, 0)   TIGHT 1 = the register-tight build (macs3_big.hip)
+ *   25 k_trial_scores<D, G, HARD>                 (25, D, G, HARD, MASK, FRESH, 0) MASK 1 = a mask was given, FRESH 1 = TAP_T_FRESH
  * wt is the launch's RollArgs::wt (the window's fp32 stores; the init kernels store none), 0 for the episode kernels. */
 int tap_variant_hits(tap_ctx *ctx, int32_t *out, int cap);
 int tap_variant_hits_reset(tap_ctx *ctx);
@@ -529,6 +530,32 @@ int tap_transition_first(tap_ctx *ctx, const tap_env_desc *d, void *state, int n
                          const int64_t *ptr, const float *mask_in, unsigned long long *bits_out,
                          float *dyn_out, float *current_out, float *mask_out, float *feature_out,
                          float *ratio_out, int32_t *nonbinary_out, int flags, void *stream);
+
+/* ---- trial placements: every selectable block scored without committing one ------------------- */
+
+/* What would calc_ratio be if container b took column c next?  For all B containers and every selectable column in
+ * one launch -- what the reference's greedy baseline generate_order_graph(..., find_order_type='best')
+ * (generate.py:1242-1292: best_to_pack) gets from one deep copy of the target Container per selectable node.
+ *   static_ / static_rows / nR   as tap_env_step_gather: the candidate of column c is static_[b, 1:1+D, c]
+ *   mask        (B, nR) f32 or NULL = every column: the selectable columns (update_mask's current_mask)
+ *   flags       TAP_T_FRESH: treat the blob as freshly reset (the fused stepper clears the container inside its first
+ *               step, not before it); no other bit
+ *   scores_out  (B, nR) f64 or NULL: for a column with mask != 0 the fp64 calc_ratio (tap_env_ratio's ratio64_out)
+ *               container b would hold after tap_env_step_gather with ptr[b] = c; -1.0 when that step would raise
+ *               an error bit (height overflow, count >= n_max, a side < 1 -- every real ratio is >= 0); -inf for a
+ *               column with mask == 0
+ *   best_out    (B,) int64 or NULL: the first column holding the row's maximum, compared in fp64 (the reference
+ *               takes the first node with the strictly largest ratio, and a third of its steps have an exact fp64
+ *               tie) = argmax(scores_out[b]); 0 where no column is selectable.  A NaN score (a block that fits
+ *               nowhere in an empty container: 0 / 0) is never the best.
+ * Read-only: no byte of the state blob changes, the sticky error words included.  No allocation, no host read, no
+ * stream synchronisation: the call can be captured in a hipGraph.  One launch, one wavefront per container, its 64 / G
+ * lane groups trying one column each per pass (k_trial_scores<D, G, HARD>; launch record key (25, D, G, HARD, MASK,
+ * FRESH, 0)).  TAP_E_INVALID for a place-at descriptor; TAP_E_UNSUPPORTED outside the lane-per-cell LB_GREEDY kernels
+ * (MACS / MUL, the legacy 'LB', more than 64 cells, a 3D side above 8): step those on a copy of the blob. */
+int tap_env_trial_scores(tap_ctx *ctx, const tap_env_desc *d, const void *state, const float *static_,
+                         int static_rows, int nR, const float *mask, int flags, double *scores_out,
+                         int64_t *best_out, void *stream);
 
 /* ---- the step object of a decoding loop ----------------------------------------------------- */
 /* DRL.forward's loop (model.py:342-496) runs its policy network between the environment steps, so the loop is

@@ -26,6 +26,7 @@ TAP_F_AT_CONTAINER, TAP_F_AT_NET = 1 << 5, 1 << 6
 TAP_HIT_EPISODE_MACS2, TAP_HIT_EPISODE_MACS3 = 17, 18          # tap_common.h: TapHitKind
 TAP_HIT_PLACE_AT = 22
 TAP_HIT_EPISODE_MACS2_WAVE, TAP_HIT_EPISODE_MACS3_WAVE = 23, 24
+TAP_HIT_TRIAL = 25                                             # trial.hip: k_trial_scores
 
 
 _vp_t = C.c_void_p
@@ -84,6 +85,7 @@ _PROTOS = {
     "tap_env_step_at": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "tap_env_step_at_gather": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "tap_env_step_engine": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "tap_env_trial_scores": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "tap_env_feature": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp]),
     "tap_env_ratio": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp, _vp, _vp]),
     "tap_env_export": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -134,6 +134,81 @@ class BatchedContainer(object):
                    static.shape[1], static.shape[2], _lib.ptr(ptr), _lib.ptr(act), _lib.ptr(feat))
         return feat
 
+    def trial_scores(self, static, mask=None, fresh=False, out=None, best_out=None, stepped=False):
+        """What would calc_ratio be if env b took column c next -- for every selectable column, nothing committed
+        (tapenv.h: tap_env_trial_scores; the reference's best_to_pack, generate.py:1242-1292).  ``static`` (B, >= 1+D,
+        nR) float32; ``mask`` (B, nR) float32 or None = every column (the stepper's ``current_mask``); ``fresh``: score
+        against a freshly reset container whatever the blob holds.  -> (scores (B, nR) float64, best (B,) int64):
+        the fp64 calc_ratio after the step for a selectable column, -1.0 where that step would raise an error bit, -inf
+        for an unselectable one; ``best`` the first column with the row's maximum (0 where none is selectable).  The
+        state blob is only read.  ``out`` / ``best_out``: buffers to fill -- with both given nothing is allocated and the
+        call is one launch (capturable in a hipGraph).  The one-launch kernel takes the lane-per-cell LB_GREEDY shapes;
+        for every other strategy and size the step entry points take (TAP_E_UNSUPPORTED), or with ``stepped=True``,
+        the same answer comes from nR committed steps on a scratch copy of the blob (_trial_scores_stepped)."""
+        if static.dtype != torch.float32 or not static.is_contiguous() or static.device != self.device:
+            static = static.to(device=self.device, dtype=torch.float32).contiguous()
+        if static.dim() != 3 or static.shape[0] != self.batch_size or static.shape[1] < 1 + self.block_dim:
+            raise ValueError("static must be (%d, >= %d, nR), got %s" % (self.batch_size, 1 + self.block_dim, tuple(static.shape)))
+        B, nR = self.batch_size, int(static.shape[2])
+        if mask is not None:
+            if tuple(mask.shape) != (B, nR):
+                raise ValueError("mask must be (%d, %d), got %s" % (B, nR, tuple(mask.shape)))
+            if mask.dtype != torch.float32 or not mask.is_contiguous() or mask.device != self.device:
+                mask = mask.to(device=self.device, dtype=torch.float32).contiguous()
+        for t, shape, dt, what in ((out, (B, nR), torch.float64, "out"), (best_out, (B,), torch.int64, "best_out")):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device):
+                raise ValueError("%s must be a contiguous %s tensor of shape %s on %s" % (what, dt, shape, self.device))
+        scores = out if out is not None else torch.empty(B, nR, dtype=torch.float64, device=self.device)
+        best = best_out if best_out is not None else torch.empty(B, dtype=torch.int64, device=self.device)
+        if self.place_at is not None and stepped:
+            raise _lib.TapError(_lib.TAP_E_INVALID, "trial scores on a place-at container: its blocks go to caller-chosen columns")
+        if not stepped:
+            try:
+                self._call(_lib.lib().tap_env_trial_scores, _lib.ptr(self._state), _lib.ptr(static), static.shape[1], nR,
+                           _lib.ptr(mask), _lib.TAP_T_FRESH if fresh else 0, _lib.ptr(scores), _lib.ptr(best))
+                return scores, best
+            except _lib.TapError as e:
+                if e.status != _lib.TAP_E_UNSUPPORTED:
+                    raise
+        return self._trial_scores_stepped(static, mask, fresh, scores, best)
+
+    def _trial_scores_stepped(self, static, mask, fresh, scores, best):
+        """trial_scores from the kernels every strategy and size has: per column, a scratch blob takes a copy of the
+        state (a reset under ``fresh``), one committed tap_env_step_gather with that column for every env, then
+        tap_env_ratio in fp64 and the error words; the same -inf / -1.0 / first-maximum rules on top."""
+        B, nR = self.batch_size, int(static.shape[2])
+        if getattr(self, "_trial_state", None) is None:
+            self._trial_state = torch.empty_like(self._state)
+        scratch, L = self._trial_state, _lib.lib()
+        # the blob's error words: its third section, after the height-maps and the counters (each 256-byte aligned)
+        al = lambda v: (v + 255) & ~255  # noqa: E731
+        off = al(B * self.desc.W * self.desc.L * 4) + al(B * 16)
+        scratch_err = scratch[off:off + 4 * B].view(torch.int32)
+        ptr = torch.empty(B, dtype=torch.int64, device=self.device)
+        r64 = torch.empty(B, dtype=torch.float64, device=self.device)
+        err = torch.empty(B, dtype=torch.int32, device=self.device)
+        for c in range(nR):
+            if fresh:
+                self._call(L.tap_env_reset, _lib.ptr(scratch))
+            else:
+                scratch.copy_(self._state)
+                scratch_err.zero_()                            # the trial's own error bits, not the blob's sticky ones
+            ptr.fill_(c)
+            self._call(L.tap_env_step_gather, _lib.ptr(scratch), _lib.ptr(static), static.shape[1], nR, _lib.ptr(ptr),
+                       None, None)
+            self._call(L.tap_env_ratio, _lib.ptr(scratch), None, _lib.ptr(r64), None)
+            self._call(L.tap_env_errors, _lib.ptr(scratch), _lib.ptr(err))
+            scores[:, c] = torch.where(err != 0, torch.full_like(r64, -1.0), r64)
+        if mask is not None:
+            scores.masked_fill_(mask == 0, float('-inf'))
+        # the first column holding the maximum; a NaN score (0 / 0: a block that fits nowhere in an empty container)
+        # is never the best
+        key = torch.where(torch.isnan(scores), torch.full_like(scores, float('-inf')), scores)
+        cols = torch.arange(nR, device=self.device).expand(B, nR)
+        at_max = key == key.max(dim=1, keepdim=True).values
+        best.copy_(torch.where(at_max, cols, torch.full_like(cols, nR)).min(dim=1).values)
+        return scores, best
+
     def _pnet_args(self, pnet_out, pnet_form):
         if pnet_out is None:
             return None, 0

@@ -108,6 +108,66 @@ def precedence_tensors(blocks, positions, container_size, arm_size=1):
     return static, dynamic
 
 
+def best_orders(blocks, positions, initial_container_size, target_container_size, reward_type, arm_size=1,
+                allow_bot=True):
+    """generate.generate_order_graph(..., find_order_type='best') (generate.py:1109-1361) for B fully packed initial
+    containers at once: at every step the selectable node -- movement in-degree 0 and (left or right in-degree 0),
+    exactly ``current_mask`` in column order, node id = rot * n + block -- whose block leaves the target container
+    with the largest calc_ratio, the first of them on a tie (best_to_pack, generate.py:1242-1292, compares Python
+    floats: fp64).  ``blocks`` / ``positions`` (B, n, D) int32 (rotation 0), ``allow_bot=False`` drops the side
+    relations (input type 'rot' on the movement rows).  -> (tours (B, n) int64, mean_valid (B,) float64 = the
+    reference's mean_valid_nodes_num).  An episode under rollout.BestRatioPolicy: one trial launch and one step
+    launch per step for the lane-per-cell LB_GREEDY targets."""
+    from .env import BatchedContainer
+    from .rollout import BestRatioPolicy, run_episode
+    blocks = torch.as_tensor(blocks)
+    dev = _lib.resolve_device(blocks.device)
+    blocks = blocks.to(device=dev, dtype=torch.int32).contiguous()
+    positions = torch.as_tensor(positions).to(device=dev, dtype=torch.int32).contiguous()
+    B, n, D = blocks.shape
+    if len(target_container_size) != D or len(initial_container_size) != D:
+        raise ValueError("container sizes must have %d entries" % D)
+    static, dynamic = precedence_tensors(blocks, positions, initial_container_size, arm_size)
+    input_type = 'bot'
+    if not allow_bot:
+        input_type, dynamic = 'rot', dynamic[:, :n, :].contiguous()
+    env = BatchedContainer(B, target_container_size, n, reward_type, 'full',                  # generate.py:1240
+                           initial_container_size=list(initial_container_size), device=dev)
+    best = BestRatioPolicy(env)
+    valid = torch.zeros(B, dtype=torch.float64, device=dev)
+
+    def policy(step, current_mask, **kw):
+        valid.add_(current_mask.sum(1, dtype=torch.float64))                                  # generate.py:1323
+        return best(step=step, current_mask=current_mask, **kw)
+    out = run_episode(static, dynamic, policy, target_container_size[0], target_container_size[-1], reward_type,
+                      'full', input_type=input_type, allow_rot=True, env=env, check=False)
+    return out['tour_idx'].clone(), valid / n
+
+
+def generate_order_graph(blocks, positions, container_size, arm_size, allow_bot, find_order_type, reward_type,
+                         target_container_size=None):
+    """generate.generate_order_graph (generate.py:1109-1361), the reference's parameter list and return triple
+    (solution, search_time, mean_valid_nodes_num) for ONE instance given as numpy arrays / lists; ``solution`` holds
+    node ids rot * n + block.  'best' only (best_orders with a batch of one)."""
+    import time
+    import numpy as np
+    if find_order_type in ('rand', 'max'):
+        raise NotImplementedError("find_order_type %r draws from numpy's global generator (generate.py:1126-1128, 1336, "
+                                  "1341): its orders cannot be reproduced on the device; 'best' is implemented" % (find_order_type,))
+    if find_order_type != 'best':
+        raise ValueError("find_order_type must be 'rand', 'max' or 'best', not %r" % (find_order_type,))
+    if target_container_size is None:
+        raise ValueError("find_order_type 'best' needs target_container_size (generate.py:1239-1240)")
+    dev = _lib.resolve_device('cuda')
+    b = torch.as_tensor(np.asarray(blocks, dtype=np.int32)[None]).to(dev)
+    p = torch.as_tensor(np.asarray(positions, dtype=np.int32)[None]).to(dev)
+    start = time.time()
+    tours, mean_valid = best_orders(b, p, [int(v) for v in container_size], [int(v) for v in target_container_size],
+                                    reward_type, int(arm_size), bool(allow_bot))
+    solution = [int(v) for v in tours[0].tolist()]
+    return solution, time.time() - start, float(mean_valid[0].item())
+
+
 def generate_instances(batch_size, blocks_num, block_dim, initial_container_width=7,
                        initial_container_height=50, arm_size=1, size_range=(1, 5), seed=None,
                        device='cuda', oversample=1.15, return_aux=False):

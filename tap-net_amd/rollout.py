@@ -91,6 +91,37 @@ class UniformKeysPolicy(object):
         return torch.argmax(current_mask * self.v[step], dim=1)
 
 
+class BestRatioPolicy(object):
+    """The greedy best-ratio order (the reference's generate_order_graph(..., find_order_type='best'),
+    generate.py:1242-1292): the selectable column whose placement leaves ``env`` -- the container the episode steps --
+    with the largest calc_ratio, the first of them on a tie, compared in fp64.  One ``env.trial_scores`` call per step
+    on buffers the policy keeps: one launch for the lane-per-cell LB_GREEDY shapes, no host read, so an episode with it
+    can be captured in a hipGraph (the other strategies and sizes go through trial_scores' stepped form).
+    ``fresh_first``: score step 0 against an empty container -- the fused stepper clears the container inside its
+    first step, not before it; pass False when the episode goes on with the container as it is.  After a call
+    ``scores`` (B, nR) float64 holds that step's trial scores."""
+
+    def __init__(self, env, fresh_first=True):
+        self.env = env
+        self.fresh_first = bool(fresh_first)
+        self.scores = None
+        self._best = []                  # one (B,) buffer per step index: a loop may keep every step's picks as views
+
+    def __call__(self, step, static, current_mask, **_):
+        env = self.env
+        if int(static.shape[1]) != 1 + env.block_dim:
+            raise NotImplementedError("BestRatioPolicy scores one target container: the two-container input types "
+                                      "('mul', 'mul-with') are not implemented")
+        nR = int(static.shape[2])
+        if self.scores is None or tuple(self.scores.shape) != (env.batch_size, nR):
+            self.scores = torch.empty(env.batch_size, nR, dtype=torch.float64, device=env.device)
+        while len(self._best) <= step:
+            self._best.append(torch.empty(env.batch_size, dtype=torch.int64, device=env.device))
+        best = self._best[step]
+        env.trial_scores(static, current_mask, fresh=self.fresh_first and step == 0, out=self.scores, best_out=best)
+        return best
+
+
 def _flagged_reward(reward, check, *envs):
     """What an episode reports for containers whose sticky error word is set (a placement above the container's
     height -- the reference's IndexError --, a block the container cannot take, a footprint beyond the big-container
