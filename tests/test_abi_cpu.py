@@ -15,7 +15,7 @@ from tap_net_amd import _lib
 REWARDS = ["C+P+S-lb-soft", "C+P+S-lb-hard", "C+P-lb-soft", "C+P-lb-hard", "C+P+S-mcs-soft",
            "C+P+S-mcs-hard", "C+P+S-mul-soft", "C+P+S-mul-hard", "C+P-mcs-soft", "C+P-mul-hard",
            "mcs-soft", "mcs-hard", "comp", "soft", "hard", "pyrm", "pyrm-soft", "pyrm-hard-SUM",
-           "pyrm-soft-sum", "CPS", "C+P+S-SL-soft"]
+           "pyrm-soft-sum", "CPS", "C+P+S-SL-soft", "pyrm-hard", "pyrm-hard-sum", "pyrm-soft-SUM"]
 
 
 def test_library_exports_every_declared_symbol():
