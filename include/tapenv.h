@@ -104,7 +104,7 @@ const char *tap_last_error(const tap_ctx *ctx);
  * hipGraph counts once, at capture.  tap_variant_hits writes up to `cap` rows of 8 ints (the key, then the count) and
  * returns the number of rows the record holds (TAP_E_INVALID if a key found no slot since the last reset);
  * tap_variant_hits_reset empties it. */
-/* The whole-episode and rolling kernels count on the same record, under kinds 16 .. 25 (tap_common.h: TapHitKind; 25: trial.hip), after
+/* The whole-episode and rolling kernels count on the same record, under kinds 16 .. 26 (tap_common.h: TapHitKind; 25: trial.hip, 26: policy.hip), after
  * the stream-wave kinds 0 .. 6.  Their keys, fields (kind, D, G, nc, mode, extra, wt):
  *   16 k_episode<D, G, SOFT>                      (16, D, G, SOFT, 0, 0, 0)
  *   17 k_episode_macs2<G, WIDE>                   (17, 2, G, WIDE, 0, 0, 0)
@@ -120,6 +120,8 @@ const char *tap_last_error(const tap_ctx *ctx);
  *   23 k_macs2d_wave_episode                      (23, 2, 64, 0, 0, PW, 0)       PW wavefronts (containers) per workgroup
  *   24 k_macs3d_wave_episode / _tight             (24, 3, 64, 0, TIGHT, PW, 0)   TIGHT 1 = the register-tight build (macs3_big.hip)
  *   25 k_trial_scores<D, G, HARD>                 (25, D, G, HARD, MASK, FRESH, 0) MASK 1 = a mask was given, FRESH 1 = TAP_T_FRESH
+ *   26 k_policy_pick<G, GREEDY> / _wide<GREEDY>   (26, 0, G, GREEDY, PROBS, 0, 0) G 0 = the chunked form (nR > 64), PROBS 1 = probs_out given
+ *      k_policy_pick_backward                     (26, 0, 0, 0, 0, 1, 0)
  * wt is the launch's RollArgs::wt (the window's fp32 stores; the init kernels store none), 0 for the episode kernels. */
 int tap_variant_hits(tap_ctx *ctx, int32_t *out, int cap);
 int tap_variant_hits_reset(tap_ctx *ctx);
@@ -556,6 +558,42 @@ int tap_transition_first(tap_ctx *ctx, const tap_env_desc *d, void *state, int n
 int tap_env_trial_scores(tap_ctx *ctx, const tap_env_desc *d, const void *state, const float *static_,
                          int static_rows, int nR, const float *mask, int flags, double *scores_out,
                          int64_t *best_out, void *stream);
+
+/* ---- the decoding head: masked softmax, pick and log-probability in one launch ------------------ */
+
+enum {
+    TAP_P_GREEDY = 1 /* take the most probable selectable column (model.py:370-372) instead of sampling */
+};
+
+/* The line between the pointer network and the step (model.py:359-372: softmax(logits + current_mask.log()), then
+ * Categorical.sample() in a host loop that rejects unselectable picks + log_prob when training, torch.max + log when
+ * not).  Per row b of nR columns:
+ *   logits (B, nR) f32; mask (B, nR) f32: column c is selectable iff mask != 0 (update_mask's current_mask is 0 / 1, so
+ *   logits + log(mask) is the logit there).  Logits on selectable columns must be finite.  Logits on unselectable
+ *   columns never enter an arithmetic result, whatever they hold (NaN, +-inf: the reference's NaN + -inf poisons the row).
+ *   All arithmetic in fp64, the order of summation free: m = max of the selectable logits, w_c = exp(l_c - m), S = sum w_c.
+ *   u (B,) f32 in [0, 1), the caller's pre-drawn uniforms (sampling): t = (double)u * S; ptr = the first selectable column
+ *   whose inclusive prefix sum of w, over the selectable columns in column order, is > t (strictly); the last
+ *   selectable column when none is (t >= S).  An unselectable column is never returned: no rejection loop, no host read.
+ *   flags TAP_P_GREEDY (u NULL): ptr = the first selectable column with l_c == m (the fp32 logits compare exactly).
+ *   logp_out (B,) f32 = (float)((l_ptr - m) - log S); ptr_out (B,) int64.
+ *   probs_out (B, nR) f32 or NULL: (float)(w_c / S), exactly 0 on unselectable columns -- what the backward reads.
+ *   A row with no selectable column: ptr 0, logp NaN, probs all 0.
+ * One launch, no allocation, no host read, no stream synchronisation (capturable in a hipGraph).  nR <= 64: a lane
+ * group of G = 8 / 16 / 32 / 64 lanes per row (k_policy_pick<G, GREEDY>); above: one wavefront per row in 64-column
+ * chunks (k_policy_pick_wide<GREEDY>).  Launch record key (26, 0, G, GREEDY, PROBS, 0, 0), G = 0 for the chunked form.
+ * Checks, in this order, before anything touches the device: B < 0 or nR < 1 -> TAP_E_INVALID; B == 0 -> TAP_OK; a
+ * null logits / mask / ptr_out / logp_out -> TAP_E_INVALID; TAP_P_GREEDY with u, or sampling without u ->
+ * TAP_E_INVALID; unknown flag bits -> TAP_E_INVALID. */
+int tap_policy_pick(tap_ctx *ctx, const float *logits, const float *mask, const float *u, int B, int nR,
+                    int flags, int64_t *ptr_out, float *logp_out, float *probs_out /* or NULL */, void *stream);
+
+/* The backward of logp with respect to the logits (model.py:359-372 under autograd: log_softmax gathered at ptr):
+ * dlogits_out[b, c] = g[b] * ((c == ptr[b]) - probs[b, c]) in fp32, one thread per element; probs / ptr / logp as
+ * tap_policy_pick wrote them, g (B,) f32 the gradient arriving at logp.  Rows whose logp is NaN (no selectable
+ * column) are written as zeros whatever g holds.  The same argument checks (every buffer required). */
+int tap_policy_pick_backward(tap_ctx *ctx, const float *probs, const int64_t *ptr, const float *logp,
+                             const float *g, int B, int nR, float *dlogits_out, void *stream);
 
 /* ---- the step object of a decoding loop ----------------------------------------------------- */
 /* DRL.forward's loop (model.py:342-496) runs its policy network between the environment steps, so the loop is

@@ -12,9 +12,9 @@ from .generate import generate_instances                       # noqa: F401
 from .pack import (EnvTransition, EpisodeStepper, MaskStepper, PACKDataset, episode_scores, initial_mask, render, reward,   # noqa: F401
                    update_dynamic, update_mask)
 from .rolling import RollingDataset, RollingStepper, RollingWindows, run_rolling_episode            # noqa: F401
-from .rollout import (BestRatioPolicy, RandomFeasiblePolicy, TapePolicy, UniformKeysPolicy, UniformPickPolicy,   # noqa: F401
-                      run_episode)
+from .rollout import (BestRatioPolicy, PointerHeadPolicy, RandomFeasiblePolicy, TapePolicy, UniformKeysPolicy,   # noqa: F401
+                      UniformPickPolicy, pointer_pick, run_episode)
 
 __all__ = ["BatchedContainer", "Container", "MaskStepper", "EnvTransition", "EpisodeStepper", "PACKDataset", "initial_mask", "reward", "render", "episode_scores", "RollingDataset",
            "update_dynamic", "update_mask", "run_episode", "TapePolicy", "RandomFeasiblePolicy", "UniformPickPolicy", "UniformKeysPolicy",
-           "BestRatioPolicy", "generate_instances", "RollingWindows", "RollingStepper", "run_rolling_episode", "TapError", "TapOverflowError"]
+           "BestRatioPolicy", "PointerHeadPolicy", "pointer_pick", "generate_instances", "RollingWindows", "RollingStepper", "run_rolling_episode", "TapError", "TapOverflowError"]

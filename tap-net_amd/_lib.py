@@ -27,6 +27,8 @@ TAP_HIT_EPISODE_MACS2, TAP_HIT_EPISODE_MACS3 = 17, 18          # tap_common.h: T
 TAP_HIT_PLACE_AT = 22
 TAP_HIT_EPISODE_MACS2_WAVE, TAP_HIT_EPISODE_MACS3_WAVE = 23, 24
 TAP_HIT_TRIAL = 25                                             # trial.hip: k_trial_scores
+TAP_HIT_POLICY_PICK = 26                                       # policy.hip: k_policy_pick / _wide / _backward
+TAP_P_GREEDY = 1
 
 
 _vp_t = C.c_void_p
@@ -86,6 +88,8 @@ _PROTOS = {
     "tap_env_step_at_gather": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "tap_env_step_engine": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "tap_env_trial_scores": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "tap_policy_pick": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "tap_policy_pick_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "tap_env_feature": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp]),
     "tap_env_ratio": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp, _vp, _vp]),
     "tap_env_export": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp, _vp, _vp, _vp]),

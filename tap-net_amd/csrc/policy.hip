@@ -1,0 +1,245 @@
+// policy.hip -- the decoding head: the line between the pointer network and step(ptr).  The reference does it in
+// model.py:359-372: probs = softmax(logits + current_mask.log()), Categorical(probs).sample() inside a host loop that
+// rejects unselectable picks (training) or torch.max (testing), then log_prob / prob.log().  Here ONE launch turns the
+// network's logits (B, nR) and the stepper's current_mask into ptr, logp and (when wanted) probs, and a second small
+// launch is the backward of logp with respect to the logits.
+//
+// Semantics per row (tapenv.h: tap_policy_pick has the contract): a column is selectable iff mask != 0; logits of
+// unselectable columns never enter an arithmetic result (they are replaced by a select, so NaN and +-inf there change
+// nothing); everything is fp64: m = max of the selectable logits, w_c = exp(l_c - m), S = sum of w.  Sampling takes a
+// PRE-DRAWN uniform u in [0, 1): t = u * S and ptr = the first selectable column whose inclusive prefix sum of w is
+// > t, the last selectable column when none is (t >= S) -- an unselectable column can never be returned, so the
+// reference's rejection loop and its host synchronisation are gone.  Greedy takes the first selectable column whose
+// logit equals m.  logp = (l_ptr - m) - log S.  A row without a selectable column: ptr 0, logp NaN, probs 0.
+//
+// Geometry.  nR <= 64: a LANE GROUP per row, G = 8 / 16 / 32 / 64 the smallest that holds the row, 64 / G rows per
+// wavefront; loads unconditional on clamped addresses, then the select (trial.hip, tap_waves.h); the max by the DPP
+// butterfly of tap_place.h, the fp64 inclusive scan in log2(G) shuffle-up steps, the pick a ballot of (cum > t) and a
+// find-first-set.  nR > 64: ONE WAVEFRONT per row in 64-column chunks: a max pass, then the weight pass -- the same
+// scan with a wave-uniform running prefix carried from chunk to chunk -- twice: once for S, which the threshold
+// t = u * S needs before any column can be compared, and once for the pick (the same instructions in the same order,
+// so both passes see bit-identical prefix sums; the row stays in the cache between them).  No LDS, no barrier, no
+// atomics, plain stores.  A ragged last wave of the group form runs on a clamped row with its stores suppressed (the
+// DPP steps need every lane); in the chunked form the whole wave leaves.
+#include "tap_common.h"
+#include "tap_place.h"
+
+namespace {
+
+constexpr int TAP_HIT_POLICY_PICK = 26; // launch record (tapenv.h: tap_variant_hits), after trial.hip's 25
+
+struct PickArgs {
+    const float *logits; // (B, nR)
+    const float *mask;   // (B, nR)
+    const float *u;      // (B,) or null (greedy)
+    int B, nR;
+    int64_t *ptr;        // (B,)
+    float *logp;         // (B,)
+    float *probs;        // (B, nR) or null
+};
+
+template <int G> __device__ __forceinline__ float group_fmaxf(float v)
+{
+    group_butterfly<G>((int)(threadIdx.x & 63), [&](auto get) { v = fmaxf(v, __int_as_float(get(__float_as_int(v)))); });
+    return v;
+}
+
+// inclusive prefix sum of w over the W lowest-aligned lanes that hold `cell` (fp64: shuffle-up on the two halves)
+template <int W> __device__ __forceinline__ double scan_up(double w, int cell)
+{
+    double cum = w;
+#pragma unroll
+    for (int d = 1; d < W; d <<= 1) {
+        const double up = __shfl_up(cum, d, W);
+        if (cell >= d) cum += up;
+    }
+    return cum;
+}
+
+__device__ __forceinline__ double wave_read(double v, int lane)
+{
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
+}
+
+__device__ __forceinline__ float pick_logp(bool any, float l_ptr, float m, double S)
+{
+    return any ? (float)(((double)l_ptr - (double)m) - log(S)) : __builtin_nanf("");
+}
+
+template <int G, bool GREEDY>
+__global__ void __launch_bounds__(TAP_BLOCK) k_policy_pick(PickArgs a)
+{
+    constexpr int EPB = TAP_BLOCK / G;
+    constexpr u64 GM = G == 64 ? ~0ull : ((1ull << (G & 63)) - 1);
+    const int tid = threadIdx.x, lane = tid & 63, cell = lane % G, gl0 = lane - cell, nR = a.nR;
+    const long long row = (long long)blockIdx.x * EPB + tid / G;
+    const bool live = row < a.B;                                // a ragged last wave: clamped row, no store
+    const size_t env = (size_t)(live ? row : a.B - 1);
+    const bool inr = cell < nR;
+    const size_t at = env * nR + min(cell, nR - 1);
+    const float l_raw = a.logits[at], mv = a.mask[at];
+    float uu = 0.f;
+    if (!GREEDY) uu = a.u[env];
+    const bool sel = inr && mv != 0.f;
+    const float ninf = -__builtin_huge_valf();
+    const float l = sel ? l_raw : ninf;                         // an unselectable logit goes no further
+    const float m = group_fmaxf<G>(l);
+    const u64 selb = (__ballot(sel) >> gl0) & GM;
+    const bool any = selb != 0;
+    const double w = sel ? exp((double)l - (double)m) : 0.0;
+    const double cum = scan_up<G>(w, cell);
+    const double S = __shfl(cum, G - 1, G);
+    u64 q;
+    if (GREEDY) q = __ballot(sel && l == m);
+    else q = __ballot(sel && cum > (double)uu * S);
+    q = (q >> gl0) & GM;
+    const int p = q ? __ffsll((long long)q) - 1 : any ? 63 - __clzll((long long)selb) : 0;
+    const float l_ptr = __shfl(l, gl0 + p);
+    if (live && cell == 0) {
+        a.ptr[env] = p;
+        a.logp[env] = pick_logp(any, l_ptr, m, S);
+    }
+    if (a.probs && live && inr) a.probs[env * nR + cell] = any ? (float)(w / S) : 0.f;
+}
+
+// one 64-column chunk of the weight pass: this lane's weight and the row's inclusive prefix sum up to its column
+struct Chunk {
+    bool inr, sel;
+    float l;
+    double w, cum;
+};
+__device__ __forceinline__ Chunk pick_chunk(const float *lrow, const float *mrow, int base, int lane, int nR, float m, double &run)
+{
+    Chunk c;
+    const int col = base + lane, at = min(col, nR - 1);
+    const float l_raw = lrow[at], mv = mrow[at];
+    c.inr = col < nR;
+    c.sel = c.inr && mv != 0.f;
+    c.l = c.sel ? l_raw : -__builtin_huge_valf();
+    c.w = c.sel ? exp((double)c.l - (double)m) : 0.0;
+    c.cum = run + scan_up<64>(c.w, lane);
+    run = wave_read(c.cum, 63);
+    return c;
+}
+
+template <bool GREEDY>
+__global__ void __launch_bounds__(TAP_BLOCK) k_policy_pick_wide(PickArgs a)
+{
+    const int lane = threadIdx.x & 63, nR = a.nR;
+    const long long row = (long long)blockIdx.x * (TAP_BLOCK / 64) + TAP_WAVE_INDEX();
+    if (row >= a.B) return;                                     // the whole wave leaves: nothing below spans waves
+    const size_t env = (size_t)row;
+    const float *lrow = a.logits + env * nR, *mrow = a.mask + env * nR;
+    const float ninf = -__builtin_huge_valf();
+    float m = ninf;
+    bool mine = false;
+    for (int base = 0; base < nR; base += 64) {                 // the max pass
+        const int col = base + lane, at = min(col, nR - 1);
+        const float l_raw = lrow[at], mv = mrow[at];
+        const bool sel = col < nR && mv != 0.f;
+        m = fmaxf(m, sel ? l_raw : ninf);
+        mine |= sel;
+    }
+    m = group_fmaxf<64>(m);
+    const bool any = __ballot(mine) != 0;
+    double S = 0.0;
+    int p = -1;
+    for (int base = 0; base < nR; base += 64) {                 // the weight pass, for S (and the greedy pick)
+        const Chunk c = pick_chunk(lrow, mrow, base, lane, nR, m, S);
+        if (GREEDY && p < 0) {
+            const u64 q = __ballot(c.sel && c.l == m);
+            if (q) p = base + __ffsll((long long)q) - 1;
+        }
+    }
+    if (!GREEDY || a.probs) {                                   // the weight pass again, for the pick and the probabilities
+        const double t = GREEDY ? 0.0 : (double)a.u[env] * S;
+        double run = 0.0;
+        int last = 0;
+        for (int base = 0; base < nR; base += 64) {
+            const Chunk c = pick_chunk(lrow, mrow, base, lane, nR, m, run);
+            if (!GREEDY) {
+                const u64 q = __ballot(c.sel && c.cum > t), sb = __ballot(c.sel);
+                if (p < 0 && q) p = base + __ffsll((long long)q) - 1;   // the first chunk with a qualifying column decides
+                if (sb) last = base + 63 - __clzll((long long)sb);
+            }
+            if (a.probs) { if (c.inr) a.probs[env * nR + base + lane] = any ? (float)(c.w / S) : 0.f; }
+            else if (p >= 0) break;                             // wave-uniform
+        }
+        if (!GREEDY && p < 0) p = last;                         // t >= S: the last selectable column (0 on an empty row)
+    }
+    if (p < 0) p = 0;
+    const float l_ptr = lrow[p];
+    if (lane == 0) {
+        a.ptr[env] = p;
+        a.logp[env] = pick_logp(any, l_ptr, m, S);
+    }
+}
+
+__global__ void __launch_bounds__(TAP_BLOCK) k_policy_pick_backward(const float *probs, const int64_t *ptr, const float *logp,
+                                                                    const float *g, size_t total, int nR, float *dlogits)
+{
+    const size_t i = (size_t)blockIdx.x * TAP_BLOCK + threadIdx.x;
+    if (i >= total) return;
+    const size_t b = i / (size_t)nR;
+    const int c = (int)(i - b * (size_t)nR);
+    const float hit = ptr[b] == (int64_t)c ? 1.f : 0.f;
+    const float lp = logp[b];
+    dlogits[i] = lp != lp ? 0.f : g[b] * (hit - probs[i]);      // an empty row (logp NaN) has no gradient
+}
+
+template <int G> int launch_pick(tap_ctx *ctx, const PickArgs &a, bool greedy, hipStream_t st)
+{
+    constexpr int EPB = TAP_BLOCK / G;
+    const int grid = (a.B + EPB - 1) / EPB;
+    if (greedy) hipLaunchKernelGGL((k_policy_pick<G, true>), dim3(grid), dim3(TAP_BLOCK), 0, st, a);
+    else hipLaunchKernelGGL((k_policy_pick<G, false>), dim3(grid), dim3(TAP_BLOCK), 0, st, a);
+    TAP_LAUNCH_CHECK(ctx, "k_policy_pick");
+    tap_variant_hit(ctx, TAP_HIT_POLICY_PICK, 0, G, TapVariant{greedy ? 1 : 0, a.probs ? 1 : 0, 0}, 0);
+    return TAP_OK;
+}
+
+int launch_pick_wide(tap_ctx *ctx, const PickArgs &a, bool greedy, hipStream_t st)
+{
+    const int wpb = TAP_BLOCK / 64, grid = a.B / wpb + (a.B % wpb ? 1 : 0);
+    if (greedy) hipLaunchKernelGGL((k_policy_pick_wide<true>), dim3(grid), dim3(TAP_BLOCK), 0, st, a);
+    else hipLaunchKernelGGL((k_policy_pick_wide<false>), dim3(grid), dim3(TAP_BLOCK), 0, st, a);
+    TAP_LAUNCH_CHECK(ctx, "k_policy_pick_wide");
+    tap_variant_hit(ctx, TAP_HIT_POLICY_PICK, 0, 0, TapVariant{greedy ? 1 : 0, a.probs ? 1 : 0, 0}, 0);
+    return TAP_OK;
+}
+
+} // namespace
+
+extern "C" int tap_policy_pick(tap_ctx *ctx, const float *logits, const float *mask, const float *u, int B, int nR,
+                               int flags, int64_t *ptr_out, float *logp_out, float *probs_out, void *stream)
+{
+    if (B < 0 || nR < 1) return tap_fail(ctx, TAP_E_INVALID, "policy pick: B %d, nR %d", B, nR);
+    if (B == 0) return TAP_OK; // an empty batch has no buffers to check
+    if (!logits || !mask || !ptr_out || !logp_out) return tap_fail(ctx, TAP_E_INVALID, "policy pick: null buffer");
+    const bool greedy = (flags & TAP_P_GREEDY) != 0;
+    if (greedy && u) return tap_fail(ctx, TAP_E_INVALID, "policy pick: TAP_P_GREEDY takes no uniforms");
+    if (!greedy && !u) return tap_fail(ctx, TAP_E_INVALID, "policy pick: sampling needs the uniforms u (or TAP_P_GREEDY)");
+    if (flags & ~TAP_P_GREEDY) return tap_fail(ctx, TAP_E_INVALID, "policy pick: bad flags %d", flags);
+    const PickArgs a = {logits, mask, u, B, nR, ptr_out, logp_out, probs_out};
+    hipStream_t st = (hipStream_t)stream;
+    if (nR <= 8) return launch_pick<8>(ctx, a, greedy, st);
+    if (nR <= 16) return launch_pick<16>(ctx, a, greedy, st);
+    if (nR <= 32) return launch_pick<32>(ctx, a, greedy, st);
+    if (nR <= 64) return launch_pick<64>(ctx, a, greedy, st);
+    return launch_pick_wide(ctx, a, greedy, st);
+}
+
+extern "C" int tap_policy_pick_backward(tap_ctx *ctx, const float *probs, const int64_t *ptr, const float *logp,
+                                        const float *g, int B, int nR, float *dlogits_out, void *stream)
+{
+    if (B < 0 || nR < 1) return tap_fail(ctx, TAP_E_INVALID, "policy pick backward: B %d, nR %d", B, nR);
+    if (B == 0) return TAP_OK;
+    if (!probs || !ptr || !logp || !g || !dlogits_out) return tap_fail(ctx, TAP_E_INVALID, "policy pick backward: null buffer");
+    const size_t total = (size_t)B * (size_t)nR, blocks = (total + TAP_BLOCK - 1) / TAP_BLOCK;
+    if (blocks > (size_t)INT_MAX) return tap_fail(ctx, TAP_E_UNSUPPORTED, "policy pick backward: %zu elements in one launch", total);
+    hipLaunchKernelGGL(k_policy_pick_backward, dim3((unsigned)blocks), dim3(TAP_BLOCK), 0, (hipStream_t)stream, probs, ptr, logp,
+                       g, total, nR, dlogits_out);
+    TAP_LAUNCH_CHECK(ctx, "k_policy_pick_backward");
+    tap_variant_hit(ctx, TAP_HIT_POLICY_PICK, 0, 0, TapVariant{0, 0, 1}, 0);
+    return TAP_OK;
+}

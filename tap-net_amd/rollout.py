@@ -122,6 +122,132 @@ class BestRatioPolicy(object):
         return best
 
 
+def _as_f32(t, dev):
+    if t.dtype is not torch.float32 or not t.is_contiguous() or t.device != dev:
+        t = t.to(device=dev, dtype=torch.float32).contiguous()
+    return t
+
+
+def _pick_into(logits, mask, u, ptr, logp, probs):
+    """tap_policy_pick on prepared buffers: one launch on the current stream, nothing allocated"""
+    dev = logits.device
+    c = _lib.ctx(dev)
+    B, nR = int(logits.shape[0]), int(logits.shape[1])
+    _lib.check(_lib.lib().tap_policy_pick(c, _lib.ptr(logits), _lib.ptr(mask), _lib.ptr(u), B, nR,
+                                          _lib.TAP_P_GREEDY if u is None else 0, _lib.ptr(ptr), _lib.ptr(logp),
+                                          _lib.ptr(probs), _lib.stream_of(dev)), c)
+
+
+class _PointerPick(torch.autograd.Function):
+    """pointer_pick under autograd: forward = the head's launch with probs kept, backward = tap_policy_pick_backward.
+    probs is the head's OWN output: the stepper's mask buffers alternate and are overwritten two steps later, so the
+    mask is not what backward keeps."""
+
+    @staticmethod
+    def forward(ctx, logits, mask, u):
+        B, nR = logits.shape
+        ptr = torch.empty(B, dtype=torch.int64, device=logits.device)
+        logp = torch.empty(B, dtype=torch.float32, device=logits.device)
+        probs = torch.empty(B, nR, dtype=torch.float32, device=logits.device)
+        _pick_into(logits, mask, u, ptr, logp, probs)
+        ctx.save_for_backward(probs, ptr, logp)
+        ctx.mark_non_differentiable(ptr, probs)
+        return ptr, logp, probs
+
+    @staticmethod
+    def backward(ctx, _g_ptr, g, _g_probs):
+        probs, ptr, logp = ctx.saved_tensors
+        g = _as_f32(g, probs.device)
+        B, nR = probs.shape
+        out = torch.empty_like(probs)
+        c = _lib.ctx(probs.device)
+        _lib.check(_lib.lib().tap_policy_pick_backward(c, _lib.ptr(probs), _lib.ptr(ptr), _lib.ptr(logp), _lib.ptr(g), int(B),
+                                                       int(nR), _lib.ptr(out), _lib.stream_of(probs.device)), c)
+        return out, None, None
+
+
+def pointer_pick(logits, mask, u=None, want_probs=False):
+    """The decoding head (tapenv.h: tap_policy_pick; model.py:359-372): masked softmax, pick and log-probability in ONE
+    launch.  ``logits`` (B, nR) from the pointer network, ``mask`` (B, nR) the stepper's ``current_mask`` (a column is
+    selectable iff mask != 0; logits on unselectable columns are never used, NaN and +-inf included; logits on
+    selectable columns must be finite), ``u`` (B,) uniforms in [0, 1) to sample with, or None for the greedy pick (the
+    first selectable column holding the row's maximum).  -> (ptr (B,) int64, logp (B,) float32[, probs (B, nR)
+    float32 with ``want_probs``]).  Sampling takes the first selectable column whose inclusive prefix sum of
+    exp(l - max) exceeds u * sum, in fp64: an unselectable column is never returned, so there is no rejection loop and
+    no host read.  A row with no selectable column gives ptr 0, logp NaN, probs 0.
+    Tensors of another dtype, layout or device are converted as ``BatchedContainer.trial_scores`` converts its inputs
+    (half / bf16 logits through ``.float()``, so autograd sees the cast).  With grad enabled and
+    ``logits.requires_grad``, ``logp`` carries its gradient to ``logits`` through one backward launch
+    (g * (onehot(ptr) - probs), zeros on rows whose logp is NaN); ``ptr`` and ``probs`` are not differentiable."""
+    if logits.dim() != 2 or int(logits.shape[1]) < 1:
+        raise ValueError("logits must be (B, nR) with nR >= 1, got %s" % (tuple(logits.shape),))
+    dev = _lib.resolve_device(logits.device)
+    B, nR = int(logits.shape[0]), int(logits.shape[1])
+    if tuple(mask.shape) != (B, nR):
+        raise ValueError("mask must be (%d, %d), got %s" % (B, nR, tuple(mask.shape)))
+    if u is not None and tuple(u.shape) != (B,):
+        raise ValueError("u must be (%d,), got %s" % (B, tuple(u.shape)))
+    if logits.dtype is not torch.float32:
+        logits = logits.float()
+    if not logits.is_contiguous() or logits.device != dev:
+        logits = logits.to(dev).contiguous()
+    mask = _as_f32(mask.detach(), dev)
+    u = None if u is None else _as_f32(u.detach(), dev)
+    if torch.is_grad_enabled() and logits.requires_grad:
+        ptr, logp, probs = _PointerPick.apply(logits, mask, u)
+    else:
+        ptr = torch.empty(B, dtype=torch.int64, device=dev)
+        logp = torch.empty(B, dtype=torch.float32, device=dev)
+        probs = torch.empty(B, nR, dtype=torch.float32, device=dev) if want_probs else None
+        _pick_into(logits, mask, u, ptr, logp, probs)
+    return (ptr, logp, probs) if want_probs else (ptr, logp)
+
+
+class PointerHeadPolicy(object):
+    """A pointer network's decoding head as a policy for ``run_episode`` and the steppers (model.py:356-372):
+    ``scorer(step=, static=, dynamic=, current_mask=, mask=, decoder_static=, decoder_dynamic=)`` returns the logits
+    (B, nR), and ``pointer_pick(logits, current_mask, ...)`` turns them into the step's ptr and log-probability.
+    ``u``: PRE-DRAWN uniforms (steps, B) in [0, 1), step-major so a step's row is contiguous (like TapePolicy's tour):
+    the episode is then deterministic given ``u`` and can be captured in a hipGraph and replayed on refreshed uniforms.
+    ``greedy=True``: the first maximum instead (the reference's test mode).  With neither, ``torch.rand(B,
+    generator=generator)`` is drawn per step, eagerly.  Each step's logp is kept: ``tour_logp()`` -> (B, steps), the
+    reference's tour_logp (model.py:513); ``reset()`` clears the kept values (step 0 of a new episode does too)."""
+
+    def __init__(self, scorer, u=None, greedy=False, generator=None):
+        if greedy and u is not None:
+            raise ValueError("greedy=True takes no uniforms")
+        self.scorer = scorer
+        self.u = u
+        self.greedy = bool(greedy)
+        self.generator = generator
+        self._logp = []
+
+    def reset(self):
+        self._logp = []
+
+    def __call__(self, step, current_mask, **kw):
+        if step == 0:
+            self._logp = []
+        logits = self.scorer(step=step, current_mask=current_mask, **kw)
+        if self.greedy:
+            u = None
+        elif self.u is not None:
+            u = self.u[step]
+        else:
+            u = torch.rand(int(logits.shape[0]), generator=self.generator, device=logits.device)
+        ptr, logp = pointer_pick(logits, current_mask, u)
+        while len(self._logp) <= step:
+            self._logp.append(None)
+        self._logp[step] = logp
+        return ptr
+
+    def tour_logp(self):
+        """(B, steps) float32: the kept log-probabilities of the picks, in step order"""
+        if not self._logp or any(v is None for v in self._logp):
+            raise RuntimeError("PointerHeadPolicy.tour_logp: no complete episode has been kept")
+        return torch.stack(self._logp, dim=1)
+
+
 def _flagged_reward(reward, check, *envs):
     """What an episode reports for containers whose sticky error word is set (a placement above the container's
     height -- the reference's IndexError --, a block the container cannot take, a footprint beyond the big-container
