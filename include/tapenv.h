@@ -104,7 +104,7 @@ const char *tap_last_error(const tap_ctx *ctx);
  * hipGraph counts once, at capture.  tap_variant_hits writes up to `cap` rows of 8 ints (the key, then the count) and
  * returns the number of rows the record holds (TAP_E_INVALID if a key found no slot since the last reset);
  * tap_variant_hits_reset empties it. */
-/* The whole-episode and rolling kernels count on the same record, under kinds 16 .. 26 (tap_common.h: TapHitKind; 25: trial.hip, 26: policy.hip), after
+/* The whole-episode and rolling kernels count on the same record, under kinds 16 .. 27 (tap_common.h: TapHitKind; 25: trial.hip, 26: policy.hip, 27: encode.hip), after
  * the stream-wave kinds 0 .. 6.  Their keys, fields (kind, D, G, nc, mode, extra, wt):
  *   16 k_episode<D, G, SOFT>                      (16, D, G, SOFT, 0, 0, 0)
  *   17 k_episode_macs2<G, WIDE>                   (17, 2, G, WIDE, 0, 0, 0)
@@ -122,6 +122,8 @@ const char *tap_last_error(const tap_ctx *ctx);
  *   25 k_trial_scores<D, G, HARD>                 (25, D, G, HARD, MASK, FRESH, 0) MASK 1 = a mask was given, FRESH 1 = TAP_T_FRESH
  *   26 k_policy_pick<G, GREEDY> / _wide<GREEDY>   (26, 0, G, GREEDY, PROBS, 0, 0) G 0 = the chunked form (nR > 64), PROBS 1 = probs_out given
  *      k_policy_pick_backward                     (26, 0, 0, 0, 0, 1, 0)
+ *   27 k_encode_bits<HPL>                         (27, 0, HPL, PLANES, BIAS, 0, 0) HPL 1 | 2 hidden rows per lane, PLANES 1 | 2 shadow planes, BIAS 1 = a bias was given
+ *      k_encode_bits_bw_partial + _reduce         (27, 0, 0, PLANES, BIAS, 1, 0) BIAS 1 = dbias wanted (one count per call)
  * wt is the launch's RollArgs::wt (the window's fp32 stores; the init kernels store none), 0 for the episode kernels. */
 int tap_variant_hits(tap_ctx *ctx, int32_t *out, int cap);
 int tap_variant_hits_reset(tap_ctx *ctx);
@@ -594,6 +596,46 @@ int tap_policy_pick(tap_ctx *ctx, const float *logits, const float *mask, const 
  * column) are written as zeros whatever g holds.  The same argument checks (every buffer required). */
 int tap_policy_pick_backward(tap_ctx *ctx, const float *probs, const int64_t *ptr, const float *logp,
                              const float *g, int B, int nR, float *dlogits_out, void *stream);
+
+/* ---- the dynamic encoder on the bit shadow: from bits to hidden in one launch ------------------- */
+
+/* The reference's first use of `dynamic` after every step (model.py:380: dynamic_hidden = self.dynamic_encoder(dynamic), an
+ * nn.Conv1d(rows, H, kernel_size=1)) computed from the shadow, so that a loop on a stepper without the fp32 expansion
+ * (tap_stepper_buffers.dyn NULL) never writes or reads that tensor.  A 1x1 convolution of a 0/1 tensor needs no
+ * multiplication:
+ *   bits (B, tap_bits_words(rows, nR)) the shadow in tap_dyn_bits' layout: word c of plane p holds rows 64p .. 64p + 63 of
+ *   column c.  Bits at positions >= rows are IGNORED, whatever they hold.
+ *   weight (H, rows) f32 row-major = Conv1d.weight (H, rows, 1); bias (H,) f32 or NULL = zeros.
+ *   out[b, h, c] (B, H, nR) f32 = the fp32 sum that starts at bias[h] (+0.0f without a bias) and adds, one fp32 addition
+ *   per row in ASCENDING row order (plane 0 before plane 1), W[h, r] for a set row and +0.0f for an unset one -- the same
+ *   value as adding the set rows only, up to the sign of a zero.  No multiplication, no reassociation, no contraction: the
+ *   result is reproducible bit for bit and equals the sequential fp32 sum of a model that follows the same order.
+ * Shapes: every window with a shadow (tap_bits_words(rows, nR) > 0: rows <= 128, nR % 4 == 0, nR <= 256) and
+ * 1 <= H <= 1024; anything else -> TAP_E_UNSUPPORTED.  bits 8-byte aligned (any offset view of a shadow), out 16-byte.
+ * One launch, no allocation, no host read, no stream synchronisation (capturable in a hipGraph).  k_encode_bits<HPL>: a
+ * wavefront per (env, column) with lanes along the hidden rows (HPL = 1 or 2 rows per lane), a scalar loop over the
+ * column's set bits, one LDS read and one addition per set row, the results transposed through an LDS tile and stored as
+ * float4s, consecutive threads consecutive 16-byte pieces (encode.hip).  Launch record key (27, 0, HPL, PLANES, BIAS, 0, 0).
+ * Checks, in tap_policy_pick's order, before anything touches the device: B < 0 or nR / rows / H < 1 -> TAP_E_INVALID;
+ * B == 0 -> TAP_OK; a null bits / weight / out -> TAP_E_INVALID; a shape outside the list above -> TAP_E_UNSUPPORTED; a
+ * misaligned bits / out -> TAP_E_INVALID. */
+int tap_encode_bits(tap_ctx *ctx, const unsigned long long *bits, int B, int nR, int rows, int H,
+                    const float *weight, const float *bias /* or NULL */, float *out, void *stream);
+
+/* The backward of tap_encode_bits with respect to weight and bias (the bits have no gradient):
+ *   dweight[h, r] (H, rows) = sum over b, c of g[b, h, c] * bit[b, r, c];  dbias[h] (H,) or NULL = sum over b, c of g[b, h, c];
+ *   g (B, H, nR) f32, 16-byte aligned, the gradient arriving at out.  fp32 accumulators; the summation order is fixed by
+ *   the shape alone (columns in order inside an env, envs in order inside a slice, slices in order), NO atomics: two
+ *   calls on the same inputs give the same bytes.  Two launches (per-slice partials into `scratch`, then their sum), no
+ *   allocation inside: scratch (floats: 4-byte aligned) holds at least tap_encode_bits_backward_scratch(B, nR, rows, H)
+ *   bytes, a smaller scratch_bytes (or a null scratch) -> TAP_E_INVALID.  The forward's checks in the forward's order
+ *   (bits / g / dweight required, then the shape, then the scratch, then the alignment); B == 0 -> TAP_OK with nothing
+ *   written.
+ * Launch record key (27, 0, 0, PLANES, DBIAS, 1, 0), one count per call. */
+int tap_encode_bits_backward(tap_ctx *ctx, const unsigned long long *bits, const float *g, int B, int nR, int rows, int H,
+                             float *dweight, float *dbias /* or NULL */, void *scratch, size_t scratch_bytes, void *stream);
+/* bytes of scratch the backward needs for this shape (0 for a shape the entry refuses) */
+size_t tap_encode_bits_backward_scratch(int B, int nR, int rows, int H);
 
 /* ---- the step object of a decoding loop ----------------------------------------------------- */
 /* DRL.forward's loop (model.py:342-496) runs its policy network between the environment steps, so the loop is

@@ -28,6 +28,7 @@ TAP_HIT_PLACE_AT = 22
 TAP_HIT_EPISODE_MACS2_WAVE, TAP_HIT_EPISODE_MACS3_WAVE = 23, 24
 TAP_HIT_TRIAL = 25                                             # trial.hip: k_trial_scores
 TAP_HIT_POLICY_PICK = 26                                       # policy.hip: k_policy_pick / _wide / _backward
+TAP_HIT_ENCODE_BITS = 27                                       # encode.hip: k_encode_bits<HPL> / _bw_partial + _bw_reduce
 TAP_P_GREEDY = 1
 
 
@@ -90,6 +91,9 @@ _PROTOS = {
     "tap_env_trial_scores": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "tap_policy_pick": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "tap_policy_pick_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "tap_encode_bits": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "tap_encode_bits_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "tap_encode_bits_backward_scratch": (_sz, [_i, _i, _i, _i]),
     "tap_env_feature": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp]),
     "tap_env_ratio": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp, _vp, _vp]),
     "tap_env_export": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -600,6 +600,8 @@ class EpisodeStepper(object):
         if rc:
             _lib.check(rc, self._ctx)
         self.static, self.dynamic, self.k = static, dynamic, 0
+        # valid before step 0: the phase-1 shadow the begin launch built (step 0 reads it); None when no launch built one
+        self.dynamic_bits = self._bits[1] if initial_mask and not self._copy else None
         self._count_in_step0 = not initial_mask and not self._copy
         self._dec.zero_()
         if self._copy:                                        # begin always makes its launches there: masks and the count exist
@@ -630,6 +632,7 @@ class EpisodeStepper(object):
             self._ones = torch.ones(self.B, self.nR, dtype=torch.float32, device=self._dev)
         self._count_in_step0 = False                      # the caller's shadow: nothing is counted
         self.static, self.dynamic, self.k, self._bits0 = static, dynamic, 0, bits
+        self.dynamic_bits = bits                          # the caller's shadow is what step 0 reads
         self.current_mask, self.mask = current_mask, self._ones
         return self
 

@@ -203,6 +203,105 @@ def pointer_pick(logits, mask, u=None, want_probs=False):
     return (ptr, logp, probs) if want_probs else (ptr, logp)
 
 
+def _encode_into(bits, weight, bias, rows, out):
+    """tap_encode_bits on prepared buffers: one launch on the current stream, nothing allocated"""
+    dev = bits.device
+    c = _lib.ctx(dev)
+    B, H, nR = (int(v) for v in out.shape)
+    _lib.check(_lib.lib().tap_encode_bits(c, _lib.ptr(bits), B, nR, rows, H, _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(out),
+                                          _lib.stream_of(dev)), c)
+
+
+class _EncodeBits(torch.autograd.Function):
+    """encode_dynamic_bits under autograd: forward = the encoder's launch, backward = tap_encode_bits_backward (two
+    launches, the scratch from torch.empty).  What backward keeps is the SHADOW, B * words * 8 bytes, not an fp32
+    tensor -- and a CLONE of it: the stepper's shadow buffers alternate and are overwritten two steps later, long
+    before an episode's backward runs."""
+
+    @staticmethod
+    def forward(ctx, bits, weight, bias, rows, nR):
+        B, H = int(bits.shape[0]), int(weight.shape[0])
+        out = torch.empty(B, H, nR, dtype=torch.float32, device=bits.device)
+        _encode_into(bits, weight, bias, rows, out)
+        ctx.save_for_backward(bits.clone())
+        ctx.shape = (B, nR, rows, H)
+        ctx.has_bias = bias is not None
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        bits, = ctx.saved_tensors
+        B, nR, rows, H = ctx.shape
+        dev = bits.device
+        g = _as_f32(g, dev)
+        L, c = _lib.lib(), _lib.ctx(dev)
+        dweight = torch.empty(H, rows, dtype=torch.float32, device=dev)
+        dbias = torch.empty(H, dtype=torch.float32, device=dev) if ctx.has_bias and ctx.needs_input_grad[2] else None
+        if B == 0:
+            dweight.zero_()
+            if dbias is not None:
+                dbias.zero_()
+            return None, dweight, dbias, None, None
+        need = int(L.tap_encode_bits_backward_scratch(B, nR, rows, H))
+        scratch = torch.empty(max(need, 16) // 4, dtype=torch.float32, device=dev)
+        _lib.check(L.tap_encode_bits_backward(c, _lib.ptr(bits), _lib.ptr(g), B, nR, rows, H, _lib.ptr(dweight), _lib.ptr(dbias),
+                                              _lib.ptr(scratch), need, _lib.stream_of(dev)), c)
+        return None, dweight, dbias, None, None
+
+
+def encode_dynamic_bits(bits, weight, bias=None, rows=None):
+    """The dynamic encoder on the bit shadow (tapenv.h: tap_encode_bits; model.py:380, dynamic_encoder(dynamic)): the 1x1
+    convolution of the 0/1 tensor ``dynamic`` computed from its shadow in ONE launch -> (B, H, nR) float32.
+    ``bits`` int64 in ``pack.dynamic_bits`` layout, (B, nR) -- (B, 2 * nR) or (B, 2, nR) above 64 rows (a stepper's
+    ``dynamic_bits``); ``weight`` (H, rows) or (H, rows, 1) = Conv1d.weight; ``bias`` (H,) or None; ``rows`` defaults to
+    ``weight.shape[1]`` (bits at positions >= rows are ignored).  out[b, h, c] = bias[h] + the W[h, r] of the rows r set
+    in column c, added in ascending row order in fp32: no multiplication, reproducible bit for bit.
+    ``weight`` / ``bias`` of another dtype, layout or device are converted as ``pointer_pick`` converts its logits (through
+    ``.float()``, so autograd sees the cast).  With grad enabled and ``weight`` or ``bias`` requiring grad the call runs
+    through a ``torch.autograd.Function`` whose backward is tap_encode_bits_backward (deterministic: no atomics); it keeps
+    a clone of ``bits`` (B * words * 8 bytes), never an fp32 ``dynamic``.  The bits carry no gradient."""
+    if bits.dtype is not torch.int64:
+        raise TypeError("bits must be the int64 shadow (pack.dynamic_bits), got %s" % (bits.dtype,))
+    if weight.dim() == 3 and int(weight.shape[2]) == 1:
+        weight = weight.squeeze(2)
+    if weight.dim() != 2 or not weight.is_floating_point():
+        raise ValueError("weight must be a floating (H, rows) or (H, rows, 1) tensor, got %s %s" % (weight.dtype, tuple(weight.shape)))
+    H = int(weight.shape[0])
+    rows = int(weight.shape[1]) if rows is None else int(rows)
+    if rows != int(weight.shape[1]):
+        raise ValueError("weight has %d input rows, rows is %d" % (int(weight.shape[1]), rows))
+    if bits.dim() not in (2, 3) or rows < 1:
+        raise ValueError("bits must be (B, words) or (B, planes, nR), got %s" % (tuple(bits.shape),))
+    B = int(bits.shape[0])
+    planes = 2 if rows > 64 else 1
+    words = int(math.prod(bits.shape[1:]))
+    nR = words // planes
+    if words != planes * nR or nR < 1 or (bits.dim() == 3 and tuple(bits.shape[1:]) != (planes, nR)):
+        raise ValueError("bits of shape %s is not the shadow of a window of %d rows (%d plane(s))" % (tuple(bits.shape), rows, planes))
+    if not (1 <= H <= 1024) or _lib.lib().tap_bits_words(rows, nR) != words:
+        raise ValueError("no bit shadow / encoder for rows %d, nR %d, H %d (rows <= 128, nR %% 4 == 0, nR <= 256, H <= 1024)" % (rows, nR, H))
+    if bias is not None and (tuple(bias.shape) != (H,) or not bias.is_floating_point()):
+        raise ValueError("bias must be a floating (%d,) tensor, got %s %s" % (H, bias.dtype, tuple(bias.shape)))
+    dev = _lib.resolve_device(bits.device)
+    if not bits.is_contiguous() or bits.device != dev:
+        bits = bits.to(dev).contiguous()
+
+    def prep(t):
+        if t.dtype is not torch.float32:
+            t = t.float()
+        if not t.is_contiguous() or t.device != dev:
+            t = t.to(dev).contiguous()
+        return t
+    weight = prep(weight)
+    bias = None if bias is None else prep(bias)
+    if torch.is_grad_enabled() and (weight.requires_grad or (bias is not None and bias.requires_grad)):
+        return _EncodeBits.apply(bits, weight, bias, rows, nR)
+    out = torch.empty(B, H, nR, dtype=torch.float32, device=dev)
+    _encode_into(bits, weight.detach(), None if bias is None else bias.detach(), rows, out)
+    return out
+
+
 class PointerHeadPolicy(object):
     """A pointer network's decoding head as a policy for ``run_episode`` and the steppers (model.py:356-372):
     ``scorer(step=, static=, dynamic=, current_mask=, mask=, decoder_static=, decoder_dynamic=)`` returns the logits

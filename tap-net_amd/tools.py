@@ -81,6 +81,29 @@ class DQN(nn.Module):
         return F.softmax(self.head(h), dim=1)
 
 
+class DynamicBitsEncoder(nn.Module):
+    """The reference actor's ``dynamic_encoder`` (model.py:380; an Encoder whose only layer is ``conv``, a
+    Conv1d(rows, hidden_size, kernel_size=1)) with a second input form: its state dict -- ``conv.weight``,
+    ``conv.bias`` -- loads with ``strict=True``.  ``forward(x)``: an int64 tensor is the bit shadow of ``dynamic``
+    (``EpisodeStepper.dynamic_bits``, ``pack.dynamic_bits``) and goes through ``rollout.encode_dynamic_bits`` -- one
+    launch, no fp32 ``dynamic`` anywhere, the shadow kept for the backward --; a floating tensor is the fp32 ``dynamic``
+    (B, rows, nR) and goes through ``F.conv1d``, so the module can replace the reference's encoder before a trainer
+    moves to ``EpisodeStepper(expand_dynamic=False)``."""
+
+    def __init__(self, rows, hidden_size):
+        super(DynamicBitsEncoder, self).__init__()
+        self.rows, self.hidden_size = int(rows), int(hidden_size)
+        self.conv = nn.Conv1d(self.rows, self.hidden_size, kernel_size=1)
+
+    def forward(self, x):
+        if x.dtype is torch.int64:
+            from .rollout import encode_dynamic_bits
+            return encode_dynamic_bits(x, self.conv.weight, self.conv.bias, rows=self.rows)
+        if not x.is_floating_point():
+            raise TypeError("DynamicBitsEncoder takes the int64 shadow or the floating `dynamic`, got %s" % (x.dtype,))
+        return F.conv1d(x, self.conv.weight, self.conv.bias)
+
+
 class _EngineRow(object):
     """net.engines[b] after a PackRNN forward: the reference's per-instance PackEngine, read-only (get_heightap)"""
 
