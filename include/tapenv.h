@@ -104,7 +104,7 @@ const char *tap_last_error(const tap_ctx *ctx);
  * hipGraph counts once, at capture.  tap_variant_hits writes up to `cap` rows of 8 ints (the key, then the count) and
  * returns the number of rows the record holds (TAP_E_INVALID if a key found no slot since the last reset);
  * tap_variant_hits_reset empties it. */
-/* The whole-episode and rolling kernels count on the same record, under kinds 16 .. 27 (tap_common.h: TapHitKind; 25: trial.hip, 26: policy.hip, 27: encode.hip), after
+/* The whole-episode and rolling kernels count on the same record, under kinds 16 .. 28 (tap_common.h: TapHitKind; 25: trial.hip, 26: policy.hip, 27: encode.hip, 28: pointer.hip), after
  * the stream-wave kinds 0 .. 6.  Their keys, fields (kind, D, G, nc, mode, extra, wt):
  *   16 k_episode<D, G, SOFT>                      (16, D, G, SOFT, 0, 0, 0)
  *   17 k_episode_macs2<G, WIDE>                   (17, 2, G, WIDE, 0, 0, 0)
@@ -124,6 +124,8 @@ const char *tap_last_error(const tap_ctx *ctx);
  *      k_policy_pick_backward                     (26, 0, 0, 0, 0, 1, 0)
  *   27 k_encode_bits<HPL>                         (27, 0, HPL, PLANES, BIAS, 0, 0) HPL 1 | 2 hidden rows per lane, PLANES 1 | 2 shadow planes, BIAS 1 = a bias was given
  *      k_encode_bits_bw_partial + _reduce         (27, 0, 0, PLANES, BIAS, 1, 0) BIAS 1 = dbias wanted (one count per call)
+ *   28 k_pointer_scores<HPL>                      (28, 0, HPL, PLANES, CHUNKS, 0, 0) CHUNKS = Hd / (64 HPL) hidden chunks per segment
+ *      k_pointer_scores_bw<HPL> + _bw_reduce      (28, 0, HPL, PLANES, CHUNKS, 1, 0) (one count per call)
  * wt is the launch's RollArgs::wt (the window's fp32 stores; the init kernels store none), 0 for the episode kernels. */
 int tap_variant_hits(tap_ctx *ctx, int32_t *out, int cap);
 int tap_variant_hits_reset(tap_ctx *ctx);
@@ -636,6 +638,58 @@ int tap_encode_bits_backward(tap_ctx *ctx, const unsigned long long *bits, const
                              float *dweight, float *dbias /* or NULL */, void *scratch, size_t scratch_bytes, void *stream);
 /* bytes of scratch the backward needs for this shape (0 for a shape the entry refuses) */
 size_t tap_encode_bits_backward_scratch(int B, int nR, int rows, int H);
+
+/* ---- the pointer network on the bit shadow: glimpse and logits in one launch -------------------- */
+
+/* The line between the dynamic encoder and the decoding head (model.py:356-358: probs, last_hh = self.pointer(static_hidden,
+ * dynamic_hidden, decoder_hidden, last_hh); classes Attention and Pointer, model.py:38-138) after its GRU step, with
+ * everything that does not depend on the step folded out.  He / Hd the encoder / decoder hidden sizes, Wa =
+ * encoder_attn.W[0] (Hd, 2 He + Hd), Wp = W[0] (Hd, 4 He), We / be the dynamic encoder's conv.weight[:, :, 0] / conv.bias.
+ * The caller prepares, in differentiable host code: Ws = [Wa[:, :He]; Wp[:, :He]; Wp[:, 2He:3He]] and Wd = [Wa[:, He:2He];
+ * Wp[:, He:2He]; Wp[:, 3He:4He]] (3 Hd, He); proj = Ws . static_hidden once per EPISODE; M = Wd . We (3 Hd, rows), k = Wd . be
+ * (3 Hd,); q = rnn_out . Wa[:, 2He:]^T (B, Hd) per step.  Per env b and column c, all in fp32:
+ *   U[x, c]   = proj[b, x, c] + (k[x] + the M[x, r] of the rows r set in column c, added to k in ASCENDING row order)
+ *   s[c]      = sum_j va[j] tanh(U[j, c] + q[b, j])
+ *   attn      = softmax_c(s)  over ALL nR columns, unmasked, as the reference's Attention is
+ *   t[j]      = sum_c attn[c] U[2 Hd + j, c]
+ *   logits[c] = sum_j vp[j] tanh(U[Hd + j, c] + t[j])
+ * which equals the reference's arithmetic in exact arithmetic (the context is a convex combination of columns, so W's
+ * action on it is the same combination of W's action on the columns).
+ *   proj (B, 3, nR, Hd) f32, SEGMENT-major and hidden fastest: proj[b, x, c] above is element [b][x / Hd][c][x % Hd] -- a
+ *   wavefront reads 256 contiguous bytes per load.  bits (B, tap_bits_words(rows, nR)) the shadow in tap_dyn_bits' layout;
+ *   bits at positions >= rows are IGNORED.  M (3 Hd, rows) row-major, k (3 Hd,), q (B, Hd), va / vp (Hd,).
+ *   logits_out (B, nR), attn_out (B, nR), t_out (B, Hd): attn and t are what the backward reads.
+ * The order of every sum is fixed by the shape (a lane's hidden rows in order, an xor butterfly over the 64 lanes, the
+ * hidden chunks in order; the columns of a wavefront in order, the four wavefronts in order): two calls give the same
+ * bytes.  No atomics, no contraction.  One launch, no allocation, no host read, no stream synchronisation (capturable in a
+ * hipGraph).  k_pointer_scores<HPL> (pointer.hip): a workgroup per run of consecutive envs, a wavefront per column, lanes
+ * along the hidden rows (HPL = 1 or 2 rows per lane), the phases s / t / logits as outer loops so that each third of proj
+ * is read once and the LDS holds one chunk of one third of M.  Launch record key (28, 0, HPL, PLANES, CHUNKS, 0, 0), CHUNKS
+ * = Hd / (64 HPL).
+ * Shapes: every window with a shadow (rows <= 128, nR % 4 == 0, nR <= 256) and Hd 64, 128 or 256; anything else ->
+ * TAP_E_UNSUPPORTED.  Checks, in tap_policy_pick's order: B < 0 or nR / rows / Hd < 1 -> TAP_E_INVALID; B == 0 -> TAP_OK; a
+ * null buffer -> TAP_E_INVALID; a shape outside the list -> TAP_E_UNSUPPORTED; a misaligned buffer (bits 8 bytes, floats
+ * 4) -> TAP_E_INVALID. */
+int tap_pointer_scores(tap_ctx *ctx, const float *proj, const unsigned long long *bits, int B, int nR, int rows, int Hd,
+                       const float *M, const float *k, const float *q, const float *va, const float *vp,
+                       float *logits_out, float *attn_out, float *t_out, void *stream);
+
+/* The backward of tap_pointer_scores: g (B, nR) the gradient arriving at logits, attn / t as the forward wrote them, the
+ * forward's inputs; U, A = U + q and G = U + t are recomputed.  Writes
+ *   dU_out (B, 3 Hd, nR) f32, columns fastest -- dproj is this tensor (read through the transposed view), and
+ *   tap_encode_bits_backward with g = dU_out and H = 3 Hd gives dM and dk --; dq_out (B, Hd); dva_out, dvp_out (Hd,).
+ * dva / dvp go through one partial per workgroup in `scratch` (at least tap_pointer_scores_backward_scratch(B, nR, rows,
+ * Hd) bytes; a smaller scratch_bytes or a null scratch -> TAP_E_INVALID) and a second launch that adds them in workgroup
+ * order: no atomics, two calls give the same bytes.  The forward's checks in the forward's order (every buffer
+ * required), then the scratch, then the alignment (dU_out leaves as float4s through an LDS tile: 16 bytes); B == 0 ->
+ * TAP_OK with nothing written.
+ * Launch record key (28, 0, HPL, PLANES, CHUNKS, 1, 0), one count per call. */
+int tap_pointer_scores_backward(tap_ctx *ctx, const float *proj, const unsigned long long *bits, int B, int nR, int rows,
+                                int Hd, const float *M, const float *k, const float *q, const float *va, const float *vp,
+                                const float *attn, const float *t, const float *g, float *dU_out, float *dq_out,
+                                float *dva_out, float *dvp_out, void *scratch, size_t scratch_bytes, void *stream);
+/* bytes of scratch the backward needs for this shape (0 for a shape the entry refuses) */
+size_t tap_pointer_scores_backward_scratch(int B, int nR, int rows, int Hd);
 
 /* ---- the step object of a decoding loop ----------------------------------------------------- */
 /* DRL.forward's loop (model.py:342-496) runs its policy network between the environment steps, so the loop is

@@ -29,6 +29,7 @@ TAP_HIT_EPISODE_MACS2_WAVE, TAP_HIT_EPISODE_MACS3_WAVE = 23, 24
 TAP_HIT_TRIAL = 25                                             # trial.hip: k_trial_scores
 TAP_HIT_POLICY_PICK = 26                                       # policy.hip: k_policy_pick / _wide / _backward
 TAP_HIT_ENCODE_BITS = 27                                       # encode.hip: k_encode_bits<HPL> / _bw_partial + _bw_reduce
+TAP_HIT_POINTER = 28                                           # pointer.hip: k_pointer_scores<HPL> / _bw<HPL> + _bw_reduce
 TAP_P_GREEDY = 1
 
 
@@ -94,6 +95,10 @@ _PROTOS = {
     "tap_encode_bits": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "tap_encode_bits_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "tap_encode_bits_backward_scratch": (_sz, [_i, _i, _i, _i]),
+    "tap_pointer_scores": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tap_pointer_scores_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _vp, _sz, _vp]),
+    "tap_pointer_scores_backward_scratch": (_sz, [_i, _i, _i, _i]),
     "tap_env_feature": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp]),
     "tap_env_ratio": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp, _vp, _vp]),
     "tap_env_export": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp, _vp, _vp, _vp]),

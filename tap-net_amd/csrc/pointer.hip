@@ -1,0 +1,528 @@
+// pointer.hip -- the pointer network on the bit shadow: the reference's probs, last_hh = self.pointer(static_hidden,
+// dynamic_hidden, decoder_hidden, last_hh) (model.py:356-358; classes Attention and Pointer, model.py:38-138) after its
+// GRU step, with everything that does not depend on the step folded out of it (tapenv.h: tap_pointer_scores has the
+// contract).  static_hidden is constant during an episode, so W's action on it is ONE projection per episode (`proj`);
+// dynamic_hidden = conv.weight . bits + conv.bias with bits in {0, 1}, so W's action on it is the sum of a few columns
+// of a small folded matrix M (3 Hd, rows) -- the scalar loop over set bits of encode.hip --; the context is a convex
+// combination of columns and folds the same way.  A step then reads proj (3 Hd nR floats per env) and the shadow and
+// writes nR logits per env: no dynamic_hidden, no concatenation, no GEMM.
+//
+// Geometry.  The 3 Hd rows of U = proj + k + M . bits are three independent segments -- 0: the attention's, 1: the
+// pointer's, 2: the context's -- and each is needed in a phase of its own: s and the softmax from segment 0, then
+// t = U2 . attn from segment 2, then the logits from segment 1 and t.  So every element of proj is read ONCE, by the
+// phase that needs it, and proj is laid out segment-major, (B, 3, nR, Hd), hidden fastest: a wavefront takes a column,
+// lanes along the hidden rows (HPL = 1 or 2 rows per lane, row = lane + 64 i), and each of its loads is 256 contiguous
+// bytes; the loads of four of its columns are issued before the first column's bit loop and consumed after it.  The column's shadow word is wave-uniform; a lane's
+// addend per set row is one conflict-free LDS read from an [r][x] copy of the segment's folded weights (row stride
+// odd).  A workgroup (4 wavefronts) takes a run of consecutive envs, and the phases are its OUTER loops: the LDS holds
+// one chunk (64 HPL hidden rows) of one segment of M at a time, filled once per phase and chunk for the whole run, so
+// that M + the per-env vectors stay under 60 KB whatever the shape.  The per-column sums over the hidden rows are a
+// lane's own terms in order, then an xor butterfly, then the chunks in order; the softmax over the columns is one
+// wavefront per env; t adds the four wavefronts' column partials in wavefront order.  Every order is fixed by the
+// shape: two calls give the same bytes.  No atomics.
+//
+// Backward: the same three phases in the order 1, 2, 0 (the gradient reaches the pointer's segment first, then t's,
+// then the attention's), recomputing U, A and G; dU leaves in (B, 3 Hd, nR) -- the layout tap_encode_bits_backward
+// takes as g, which then gives dM and dk -- through an LDS tile [hidden row][column] per env and pass of columns, stored
+// as float4s like k_encode_bits' output; dva / dvp as one partial per workgroup in the caller's scratch, added in
+// workgroup order by a second launch.
+#include <algorithm>
+
+#include "tap_common.h"
+
+namespace {
+
+constexpr int TAP_HIT_POINTER = 28; // launch record (tapenv.h: tap_variant_hits), after encode.hip's 27
+constexpr int PTR_NW = TAP_BLOCK / 64;
+constexpr int PTR_AHEAD = 4;                // columns whose proj loads a wavefront issues ahead
+constexpr size_t PTR_LDS_BUDGET = 60 * 1024;
+
+struct PtrGeom {
+    int planes, hpl, hck, nch; // shadow planes; hidden rows per lane, per chunk; chunks per segment
+    int epb, blocks;           // consecutive envs per workgroup; workgroups
+    int ct;                    // backward: columns per pass of the dU tile, min(nR, 4096 / hck)
+    size_t lds;                // bytes of dynamic LDS
+};
+inline size_t ptr_lds_floats(int nR, int rows, int Hd, int hck, int epb, int ct)
+{
+    // the folded weights of a chunk, s / attn / logits (or dattn / ds), the wavefronts' partials, t (or dt); the backward
+    // adds (ct > 0) the dva / dvp partials and the dU tile of a pass
+    return (size_t)rows * (hck + 1) + (size_t)epb * nR + (size_t)PTR_NW * epb * hck + (size_t)epb * Hd +
+           (ct ? (size_t)PTR_NW * hck + (size_t)hck * (ct + 1) : 0);
+}
+inline PtrGeom ptr_geom(int B, int nR, int rows, int Hd, bool backward)
+{
+    PtrGeom g;
+    g.planes = rows > 64 ? 2 : 1;
+    g.hpl = (g.planes == 1 && Hd > 64) ? 2 : 1;
+    g.hck = 64 * g.hpl;
+    g.nch = Hd / g.hck;
+    g.ct = backward ? std::min(nR, 4096 / g.hck) : 0;
+    g.epb = std::max(1, B / 1024);                                         // about four workgroups per CU before a second env
+    while (g.epb > 1 && ptr_lds_floats(nR, rows, Hd, g.hck, g.epb, g.ct) * sizeof(float) > PTR_LDS_BUDGET) g.epb >>= 1;
+    g.blocks = (B + g.epb - 1) / g.epb;
+    g.lds = ptr_lds_floats(nR, rows, Hd, g.hck, g.epb, g.ct) * sizeof(float);   // at most 60 KB: a lone env needs under 56 KB
+    return g;
+}
+
+struct PtrArgs {
+    const float *proj;              // (B, 3, nR, Hd)
+    const unsigned long long *bits; // (B, planes, nR)
+    const float *M, *k;             // (3 Hd, rows), (3 Hd,)
+    const float *q, *va, *vp;       // (B, Hd), (Hd,), (Hd,)
+    float *logits, *attn, *t;       // (B, nR), (B, nR), (B, Hd): the forward's outputs, the backward's inputs (logits unused there)
+    const float *g;                 // backward: (B, nR)
+    float *dU, *dq, *part;          // backward: (B, 3 Hd, nR), (B, Hd), (blocks, 2, Hd)
+    int B, nR, rows, Hd, planes, epb, ct;
+};
+
+__device__ __forceinline__ float ptr_wave_sum(float v)
+{
+#pragma unroll
+    for (int o = 32; o; o >>= 1) v = v + __shfl_xor(v, o);                // every lane ends with the same sum
+    return v;
+}
+__device__ __forceinline__ float ptr_wave_max(float v)
+{
+#pragma unroll
+    for (int o = 32; o; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+
+// what a phase keeps of its segment's chunk: the LDS copy of the folded weights and the lane's k
+template <int HPL>
+struct PtrSeg {
+    static constexpr int HCK = 64 * HPL, S = HCK + 1;
+    const float *lw;
+    float kk[HPL];
+    unsigned long long m0, m1;
+
+    // M[x0 + hl][r] -> lw[r * S + hl]: global reads in memory order, LDS writes at the odd stride S.  The caller's barriers
+    // stand before (the previous chunk has been consumed) and after.
+    __device__ void fill(const PtrArgs &a, float *lds, int seg, int ch, int tid, int lane)
+    {
+        const int x0 = seg * a.Hd + ch * HCK, rows = a.rows;
+        for (int i = tid; i < HCK * rows; i += TAP_BLOCK) {
+            const int hl = i / rows, r = i - hl * rows;
+            lds[r * S + hl] = a.M[(size_t)x0 * rows + i];
+        }
+#pragma unroll
+        for (int i = 0; i < HPL; ++i) kk[i] = a.k[x0 + i * 64 + lane];
+        lw = lds;
+        // bits at positions >= rows are ignored: masked off each plane's word
+        m0 = rows >= 64 ? ~0ull : (1ull << rows) - 1;
+        m1 = rows >= 128 ? ~0ull : rows > 64 ? (1ull << (rows - 64)) - 1 : 0ull;
+    }
+
+    // U[x0 + lane + 64 i, c] of env b = proj + (k + the M columns of the set rows, ascending), in two halves: load()
+    // issues the loads of the column's shadow word(s) and proj values, finish() runs the scalar loop over the set bits
+    // and adds its sum to proj
+    __device__ __forceinline__ void load(const PtrArgs &a, int b, int seg, int ch, int c, int lane, float (&u)[HPL],
+                                         unsigned long long (&w)[2]) const
+    {
+        const unsigned long long *wp = a.bits + (size_t)b * (a.planes * a.nR);
+        w[0] = wp[c];
+        w[1] = a.planes == 2 ? wp[a.nR + c] : 0ull;
+        const float *pp = a.proj + (((size_t)b * 3 + seg) * a.nR + c) * a.Hd + ch * HCK + lane;
+#pragma unroll
+        for (int i = 0; i < HPL; ++i) u[i] = pp[i * 64];
+    }
+    __device__ __forceinline__ void finish(int lane, float (&u)[HPL], const unsigned long long (&w)[2]) const
+    {
+        const unsigned long long w0 = w[0] & m0, w1 = w[1] & m1;
+        const unsigned piece[4] = {(unsigned)w0, (unsigned)(w0 >> 32), (unsigned)w1, (unsigned)(w1 >> 32)};
+        float acc[HPL];
+#pragma unroll
+        for (int i = 0; i < HPL; ++i) acc[i] = kk[i];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {                                      // ascending rows: plane 0 before plane 1
+            unsigned x = (unsigned)__builtin_amdgcn_readfirstlane((int)piece[p]);
+            while (x) {                                                    // scalar: one trip per SET row
+                const int r = 32 * p + __builtin_ctz(x);
+                x &= x - 1;
+                const float *lp = lw + r * S + lane;
+#pragma unroll
+                for (int i = 0; i < HPL; ++i) acc[i] = acc[i] + lp[i * 64];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < HPL; ++i) u[i] = u[i] + acc[i];
+    }
+
+    // the wavefront's columns of env b in [cbeg, cend) (cbeg + wave, + 4, ...) in ascending order, use(c, u) on each.  The proj loads of
+    // PTR_AHEAD columns are issued before the first of them is consumed: a wavefront alone keeps 256 HPL PTR_AHEAD
+    // bytes in flight (one column at a time left the step waiting on memory latency, not bandwidth: DESIGN 7f)
+    template <class F>
+    __device__ __forceinline__ void columns(const PtrArgs &a, int b, int seg, int ch, int cbeg, int cend, int wave, int lane,
+                                            F &&use) const
+    {
+        for (int c0 = cbeg + wave; c0 < cend; c0 += PTR_NW * PTR_AHEAD) {
+            float u[PTR_AHEAD][HPL];
+            unsigned long long w[PTR_AHEAD][2];
+#pragma unroll
+            for (int j = 0; j < PTR_AHEAD; ++j) load(a, b, seg, ch, min(c0 + j * PTR_NW, cend - 1), lane, u[j], w[j]);
+#pragma unroll
+            for (int j = 0; j < PTR_AHEAD; ++j) {
+                const int c = c0 + j * PTR_NW;
+                if (c < cend) {                                            // wave-uniform
+                    finish(lane, u[j], w[j]);
+                    use(c, u[j]);
+                }
+            }
+        }
+    }
+};
+
+// the four wavefronts' partials tp[(wave * E + e) * HCK + jl], added in wavefront order
+__device__ __forceinline__ float ptr_add_waves(const float *tp, int E, int HCK, int e, int jl)
+{
+    float v = tp[(size_t)e * HCK + jl];
+#pragma unroll
+    for (int w = 1; w < PTR_NW; ++w) v = v + tp[((size_t)w * E + e) * HCK + jl];
+    return v;
+}
+
+template <int HPL>
+__global__ void __launch_bounds__(TAP_BLOCK) k_pointer_scores(PtrArgs a)
+{
+    constexpr int HCK = 64 * HPL, S = HCK + 1;
+    extern __shared__ float ptr_lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = TAP_WAVE_INDEX();
+    const int nR = a.nR, Hd = a.Hd, E = a.epb, nch = Hd / HCK;
+    float *lw = ptr_lds, *sl = lw + a.rows * S, *tp = sl + E * nR, *tl = tp + PTR_NW * E * HCK;
+    const int e0 = (int)blockIdx.x * E, ne = min(E, a.B - e0);
+    PtrSeg<HPL> sg;
+
+    // phase 1, segment 0: s[c] = sum_j va[j] tanh(U[j, c] + q[j]) -> sl[e][c]
+    for (int ch = 0; ch < nch; ++ch) {
+        __syncthreads();
+        sg.fill(a, lw, 0, ch, tid, lane);
+        float vv[HPL];
+#pragma unroll
+        for (int i = 0; i < HPL; ++i) vv[i] = a.va[ch * HCK + i * 64 + lane];
+        __syncthreads();
+        for (int e = 0; e < ne; ++e) {
+            float qq[HPL];
+#pragma unroll
+            for (int i = 0; i < HPL; ++i) qq[i] = a.q[(size_t)(e0 + e) * Hd + ch * HCK + i * 64 + lane];
+            sg.columns(a, e0 + e, 0, ch, 0, nR, wave, lane, [&](int c, float (&u)[HPL]) {
+                float p = vv[0] * tanhf(u[0] + qq[0]);
+#pragma unroll
+                for (int i = 1; i < HPL; ++i) p = p + vv[i] * tanhf(u[i] + qq[i]);
+                p = ptr_wave_sum(p);
+                if (lane == 0) sl[e * nR + c] = ch == 0 ? p : sl[e * nR + c] + p;
+            });
+        }
+    }
+    __syncthreads();
+    // attn = softmax over ALL nR columns: a wavefront per env, lanes along the columns
+    for (int e = wave; e < ne; e += PTR_NW) {
+        float m = -INFINITY;
+        for (int c = lane; c < nR; c += 64) m = fmaxf(m, sl[e * nR + c]);
+        m = ptr_wave_max(m);
+        float z = 0.f;
+        for (int c = lane; c < nR; c += 64) {
+            const float x = expf(sl[e * nR + c] - m);
+            sl[e * nR + c] = x;
+            z = z + x;
+        }
+        z = ptr_wave_sum(z);
+        for (int c = lane; c < nR; c += 64) {
+            const float x = sl[e * nR + c] / z;
+            sl[e * nR + c] = x;
+            a.attn[(size_t)(e0 + e) * nR + c] = x;
+        }
+    }
+    // phase 2, segment 2: t[j] = sum_c attn[c] U[2 Hd + j, c] -> tl[e][j]
+    for (int ch = 0; ch < nch; ++ch) {
+        __syncthreads();                                                   // (the first one publishes attn)
+        sg.fill(a, lw, 2, ch, tid, lane);
+        __syncthreads();
+        for (int e = 0; e < ne; ++e) {
+            float tw[HPL];
+#pragma unroll
+            for (int i = 0; i < HPL; ++i) tw[i] = 0.f;
+            sg.columns(a, e0 + e, 2, ch, 0, nR, wave, lane, [&](int c, float (&u)[HPL]) {
+                const float at = sl[e * nR + c];
+#pragma unroll
+                for (int i = 0; i < HPL; ++i) tw[i] = tw[i] + at * u[i];
+            });
+#pragma unroll
+            for (int i = 0; i < HPL; ++i) tp[(wave * E + e) * HCK + i * 64 + lane] = tw[i];
+        }
+        __syncthreads();
+        for (int i = tid; i < ne * HCK; i += TAP_BLOCK) {
+            const int e = i / HCK, jl = i - e * HCK;
+            const float v = ptr_add_waves(tp, E, HCK, e, jl);
+            tl[e * Hd + ch * HCK + jl] = v;
+            a.t[(size_t)(e0 + e) * Hd + ch * HCK + jl] = v;
+        }
+    }
+    // phase 3, segment 1: logits[c] = sum_j vp[j] tanh(U[Hd + j, c] + t[j]) -> sl[e][c] (attn has been consumed)
+    for (int ch = 0; ch < nch; ++ch) {
+        __syncthreads();
+        sg.fill(a, lw, 1, ch, tid, lane);
+        float vv[HPL];
+#pragma unroll
+        for (int i = 0; i < HPL; ++i) vv[i] = a.vp[ch * HCK + i * 64 + lane];
+        __syncthreads();
+        for (int e = 0; e < ne; ++e) {
+            float tt[HPL];
+#pragma unroll
+            for (int i = 0; i < HPL; ++i) tt[i] = tl[e * Hd + ch * HCK + i * 64 + lane];
+            sg.columns(a, e0 + e, 1, ch, 0, nR, wave, lane, [&](int c, float (&u)[HPL]) {
+                float p = vv[0] * tanhf(u[0] + tt[0]);
+#pragma unroll
+                for (int i = 1; i < HPL; ++i) p = p + vv[i] * tanhf(u[i] + tt[i]);
+                p = ptr_wave_sum(p);
+                if (lane == 0) sl[e * nR + c] = ch == 0 ? p : sl[e * nR + c] + p;
+            });
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < ne * nR; i += TAP_BLOCK) a.logits[(size_t)e0 * nR + i] = sl[i];
+}
+
+// ---- backward -----------------------------------------------------------------------------------------------------
+// the backward's dU tile of a pass, tile[hl * TS + column] (TS odd: the wavefronts' writes, lanes along hl, are
+// conflict-free), to dst[hl * nR + column] as float4s, consecutive threads consecutive 16-byte pieces; ncol % 4 == 0.
+// A barrier before (the tile is complete) and after (the next pass may overwrite it).
+__device__ __forceinline__ void ptr_store_tile(const float *tile, int TS, int ncol, int HCK, float *dst, int nR, int tid)
+{
+    __syncthreads();
+    const int q4 = ncol >> 2, total = HCK * q4;
+    for (int j = tid; j < total; j += TAP_BLOCK) {
+        const int hl = j / q4, k4 = j - hl * q4;
+        const float *t = tile + hl * TS + 4 * k4;
+        *reinterpret_cast<float4 *>(dst + (size_t)hl * nR + 4 * k4) = make_float4(t[0], t[1], t[2], t[3]);
+    }
+    __syncthreads();
+}
+
+template <int HPL>
+__global__ void __launch_bounds__(TAP_BLOCK) k_pointer_scores_bw(PtrArgs a)
+{
+    constexpr int HCK = 64 * HPL, S = HCK + 1;
+    extern __shared__ float ptr_lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = TAP_WAVE_INDEX();
+    const int nR = a.nR, Hd = a.Hd, E = a.epb, nch = Hd / HCK;
+    float *lw = ptr_lds, *dl = lw + a.rows * S, *tp = dl + E * nR, *dtl = tp + PTR_NW * E * HCK, *vp4 = dtl + E * Hd;
+    float *tile = vp4 + PTR_NW * HCK;
+    const int CT = a.ct, TS = CT + 1;                                      // columns per pass of the dU tile
+    const int e0 = (int)blockIdx.x * E, ne = min(E, a.B - e0);
+    float *part = a.part + (size_t)blockIdx.x * 2 * Hd;                    // this workgroup's dva (Hd), then dvp (Hd)
+    PtrSeg<HPL> sg;
+
+    // phase 1, segment 1: G = U + t; dvp += g tanh(G); dG = g vp (1 - tanh^2) = dU[Hd + j]; dt[j] = sum_c dG[j, c]
+    for (int ch = 0; ch < nch; ++ch) {
+        __syncthreads();
+        sg.fill(a, lw, 1, ch, tid, lane);
+        float vv[HPL], dv[HPL];
+#pragma unroll
+        for (int i = 0; i < HPL; ++i) { vv[i] = a.vp[ch * HCK + i * 64 + lane]; dv[i] = 0.f; }
+        __syncthreads();
+        for (int e = 0; e < ne; ++e) {
+            const int b = e0 + e;
+            float tt[HPL], dw[HPL];
+#pragma unroll
+            for (int i = 0; i < HPL; ++i) { tt[i] = a.t[(size_t)b * Hd + ch * HCK + i * 64 + lane]; dw[i] = 0.f; }
+            for (int cb = 0; cb < nR; cb += CT) {
+                const int ncol = min(CT, nR - cb);
+                sg.columns(a, b, 1, ch, cb, cb + ncol, wave, lane, [&](int c, float (&u)[HPL]) {
+                    const float gc = a.g[(size_t)b * nR + c];
+#pragma unroll
+                    for (int i = 0; i < HPL; ++i) {
+                        const float th = tanhf(u[i] + tt[i]);
+                        dv[i] = dv[i] + gc * th;
+                        const float d = gc * vv[i] * (1.f - th * th);
+                        tile[(i * 64 + lane) * TS + c - cb] = d;
+                        dw[i] = dw[i] + d;
+                    }
+                });
+                ptr_store_tile(tile, TS, ncol, HCK, a.dU + ((size_t)b * 3 * Hd + Hd + ch * HCK) * nR + cb, nR, tid);
+            }
+#pragma unroll
+            for (int i = 0; i < HPL; ++i) tp[(wave * E + e) * HCK + i * 64 + lane] = dw[i];
+        }
+#pragma unroll
+        for (int i = 0; i < HPL; ++i) vp4[wave * HCK + i * 64 + lane] = dv[i];
+        __syncthreads();
+        for (int i = tid; i < ne * HCK; i += TAP_BLOCK) {
+            const int e = i / HCK, jl = i - e * HCK;
+            dtl[e * Hd + ch * HCK + jl] = ptr_add_waves(tp, E, HCK, e, jl);
+        }
+        for (int jl = tid; jl < HCK; jl += TAP_BLOCK) part[Hd + ch * HCK + jl] = ptr_add_waves(vp4, 1, HCK, 0, jl);
+    }
+    // phase 2, segment 2: dU[2 Hd + j, c] = attn[c] dt[j]; dattn[c] = sum_j dt[j] U[2 Hd + j, c] -> dl[e][c]
+    for (int ch = 0; ch < nch; ++ch) {
+        __syncthreads();                                                   // (the first one publishes dt)
+        sg.fill(a, lw, 2, ch, tid, lane);
+        __syncthreads();
+        for (int e = 0; e < ne; ++e) {
+            const int b = e0 + e;
+            float dt[HPL];
+#pragma unroll
+            for (int i = 0; i < HPL; ++i) dt[i] = dtl[e * Hd + ch * HCK + i * 64 + lane];
+            for (int cb = 0; cb < nR; cb += CT) {
+                const int ncol = min(CT, nR - cb);
+                sg.columns(a, b, 2, ch, cb, cb + ncol, wave, lane, [&](int c, float (&u)[HPL]) {
+                    const float at = a.attn[(size_t)b * nR + c];
+                    float p = dt[0] * u[0];
+#pragma unroll
+                    for (int i = 1; i < HPL; ++i) p = p + dt[i] * u[i];
+#pragma unroll
+                    for (int i = 0; i < HPL; ++i) tile[(i * 64 + lane) * TS + c - cb] = at * dt[i];
+                    p = ptr_wave_sum(p);
+                    if (lane == 0) dl[e * nR + c] = ch == 0 ? p : dl[e * nR + c] + p;
+                });
+                ptr_store_tile(tile, TS, ncol, HCK, a.dU + ((size_t)b * 3 * Hd + 2 * Hd + ch * HCK) * nR + cb, nR, tid);
+            }
+        }
+    }
+    __syncthreads();
+    // the softmax: ds[c] = attn[c] (dattn[c] - sum_c' attn[c'] dattn[c']), a wavefront per env
+    for (int e = wave; e < ne; e += PTR_NW) {
+        const float *at = a.attn + (size_t)(e0 + e) * nR;
+        float z = 0.f;
+        for (int c = lane; c < nR; c += 64) z = z + at[c] * dl[e * nR + c];
+        z = ptr_wave_sum(z);
+        for (int c = lane; c < nR; c += 64) dl[e * nR + c] = at[c] * (dl[e * nR + c] - z);
+    }
+    // phase 3, segment 0: A = U + q; dva += ds tanh(A); dA = ds va (1 - tanh^2) = dU[j]; dq[j] = sum_c dA[j, c]
+    for (int ch = 0; ch < nch; ++ch) {
+        __syncthreads();                                                   // (the first one publishes ds)
+        sg.fill(a, lw, 0, ch, tid, lane);
+        float vv[HPL], dv[HPL];
+#pragma unroll
+        for (int i = 0; i < HPL; ++i) { vv[i] = a.va[ch * HCK + i * 64 + lane]; dv[i] = 0.f; }
+        __syncthreads();
+        for (int e = 0; e < ne; ++e) {
+            const int b = e0 + e;
+            float qq[HPL], dw[HPL];
+#pragma unroll
+            for (int i = 0; i < HPL; ++i) { qq[i] = a.q[(size_t)b * Hd + ch * HCK + i * 64 + lane]; dw[i] = 0.f; }
+            for (int cb = 0; cb < nR; cb += CT) {
+                const int ncol = min(CT, nR - cb);
+                sg.columns(a, b, 0, ch, cb, cb + ncol, wave, lane, [&](int c, float (&u)[HPL]) {
+                    const float ds = dl[e * nR + c];
+#pragma unroll
+                    for (int i = 0; i < HPL; ++i) {
+                        const float th = tanhf(u[i] + qq[i]);
+                        dv[i] = dv[i] + ds * th;
+                        const float d = ds * vv[i] * (1.f - th * th);
+                        tile[(i * 64 + lane) * TS + c - cb] = d;
+                        dw[i] = dw[i] + d;
+                    }
+                });
+                ptr_store_tile(tile, TS, ncol, HCK, a.dU + ((size_t)b * 3 * Hd + ch * HCK) * nR + cb, nR, tid);
+            }
+#pragma unroll
+            for (int i = 0; i < HPL; ++i) tp[(wave * E + e) * HCK + i * 64 + lane] = dw[i];
+        }
+#pragma unroll
+        for (int i = 0; i < HPL; ++i) vp4[wave * HCK + i * 64 + lane] = dv[i];
+        __syncthreads();
+        for (int i = tid; i < ne * HCK; i += TAP_BLOCK) {
+            const int e = i / HCK, jl = i - e * HCK;
+            a.dq[(size_t)(e0 + e) * Hd + ch * HCK + jl] = ptr_add_waves(tp, E, HCK, e, jl);
+        }
+        for (int jl = tid; jl < HCK; jl += TAP_BLOCK) part[ch * HCK + jl] = ptr_add_waves(vp4, 1, HCK, 0, jl);
+    }
+}
+
+// dva[j] = part[0][0][j] + part[1][0][j] + ..., dvp likewise: workgroup order, the same bytes every call
+__global__ void __launch_bounds__(TAP_BLOCK) k_pointer_scores_bw_reduce(const float *part, int blocks, int Hd, float *dva, float *dvp)
+{
+    const int i = (int)blockIdx.x * TAP_BLOCK + (int)threadIdx.x;
+    if (i >= 2 * Hd) return;
+    float s = 0.f;
+    for (int k0 = 0; k0 < blocks; k0 += 32) {                              // runs of 32, then the runs: shorter chains of roundings
+        float p = 0.f;
+        for (int k = k0; k < min(blocks, k0 + 32); ++k) p = p + part[(size_t)k * 2 * Hd + i];
+        s = s + p;
+    }
+    if (i < Hd) dva[i] = s;
+    else dvp[i - Hd] = s;
+}
+
+// the checks of both entries in tap_policy_pick's order: dimensions, then the empty batch, then the caller's null
+// check, then the shapes without a kernel
+int ptr_check_dims(tap_ctx *ctx, const char *what, int B, int nR, int rows, int Hd)
+{
+    if (B < 0 || nR < 1 || rows < 1 || Hd < 1) return tap_fail(ctx, TAP_E_INVALID, "%s: B %d, nR %d, rows %d, Hd %d", what, B, nR, rows, Hd);
+    return TAP_OK;
+}
+inline bool ptr_shape_ok(int nR, int rows, int Hd) { return tap_bits_words(rows, nR) > 0 && (Hd == 64 || Hd == 128 || Hd == 256); }
+int ptr_check_shape(tap_ctx *ctx, const char *what, int nR, int rows, int Hd)
+{
+    if (!ptr_shape_ok(nR, rows, Hd))
+        return tap_fail(ctx, TAP_E_UNSUPPORTED, "%s: rows %d, nR %d, Hd %d (needs a bit shadow: rows <= 128, nR %% 4 == 0, nR <= 256; Hd 64, 128 or 256)",
+                        what, rows, nR, Hd);
+    return TAP_OK;
+}
+inline bool ptr_misaligned(const void *p, unsigned to) { return ((uintptr_t)p & (to - 1)) != 0; }
+
+} // namespace
+
+extern "C" int tap_pointer_scores(tap_ctx *ctx, const float *proj, const unsigned long long *bits, int B, int nR, int rows, int Hd,
+                                  const float *M, const float *k, const float *q, const float *va, const float *vp,
+                                  float *logits_out, float *attn_out, float *t_out, void *stream)
+{
+    int rc = ptr_check_dims(ctx, "pointer scores", B, nR, rows, Hd);
+    if (rc != TAP_OK) return rc;
+    if (B == 0) return TAP_OK; // an empty batch has no buffers to check
+    if (!proj || !bits || !M || !k || !q || !va || !vp || !logits_out || !attn_out || !t_out)
+        return tap_fail(ctx, TAP_E_INVALID, "pointer scores: null buffer");
+    if ((rc = ptr_check_shape(ctx, "pointer scores", nR, rows, Hd)) != TAP_OK) return rc;
+    const void *f32[] = {proj, M, k, q, va, vp, logits_out, attn_out, t_out};
+    bool bad = ptr_misaligned(bits, 8);
+    for (const void *p : f32) bad = bad || ptr_misaligned(p, 4);
+    if (bad) return tap_fail(ctx, TAP_E_INVALID, "pointer scores: bits must be 8-byte and the float buffers 4-byte aligned");
+    const PtrGeom geo = ptr_geom(B, nR, rows, Hd, false);
+    const PtrArgs a = {proj, bits, M, k, q, va, vp, logits_out, attn_out, t_out, nullptr, nullptr, nullptr, nullptr,
+                       B, nR, rows, Hd, geo.planes, geo.epb, 0};
+    hipStream_t st = (hipStream_t)stream;
+    if (geo.hpl == 1) hipLaunchKernelGGL((k_pointer_scores<1>), dim3((unsigned)geo.blocks), dim3(TAP_BLOCK), geo.lds, st, a);
+    else hipLaunchKernelGGL((k_pointer_scores<2>), dim3((unsigned)geo.blocks), dim3(TAP_BLOCK), geo.lds, st, a);
+    TAP_LAUNCH_CHECK(ctx, "k_pointer_scores");
+    tap_variant_hit(ctx, TAP_HIT_POINTER, 0, geo.hpl, TapVariant{geo.planes, geo.nch, 0}, 0);
+    return TAP_OK;
+}
+
+extern "C" size_t tap_pointer_scores_backward_scratch(int B, int nR, int rows, int Hd)
+{
+    if (B < 1 || nR < 1 || rows < 1 || Hd < 1 || !ptr_shape_ok(nR, rows, Hd)) return 0;
+    return (size_t)ptr_geom(B, nR, rows, Hd, true).blocks * 2 * (size_t)Hd * sizeof(float);
+}
+
+extern "C" int tap_pointer_scores_backward(tap_ctx *ctx, const float *proj, const unsigned long long *bits, int B, int nR, int rows,
+                                           int Hd, const float *M, const float *k, const float *q, const float *va, const float *vp,
+                                           const float *attn, const float *t, const float *g, float *dU_out, float *dq_out,
+                                           float *dva_out, float *dvp_out, void *scratch, size_t scratch_bytes, void *stream)
+{
+    int rc = ptr_check_dims(ctx, "pointer scores backward", B, nR, rows, Hd);
+    if (rc != TAP_OK) return rc;
+    if (B == 0) return TAP_OK; // (an empty batch leaves the outputs as they are)
+    if (!proj || !bits || !M || !k || !q || !va || !vp || !attn || !t || !g || !dU_out || !dq_out || !dva_out || !dvp_out)
+        return tap_fail(ctx, TAP_E_INVALID, "pointer scores backward: null buffer");
+    if ((rc = ptr_check_shape(ctx, "pointer scores backward", nR, rows, Hd)) != TAP_OK) return rc;
+    const size_t need = tap_pointer_scores_backward_scratch(B, nR, rows, Hd);
+    if (!scratch || scratch_bytes < need)
+        return tap_fail(ctx, TAP_E_INVALID, "pointer scores backward: scratch of %zu bytes, %zu needed", scratch ? scratch_bytes : (size_t)0, need);
+    const void *f32[] = {proj, M, k, q, va, vp, attn, t, g, dU_out, dq_out, dva_out, dvp_out, scratch};
+    bool bad = ptr_misaligned(bits, 8) || ptr_misaligned(dU_out, 16);      // dU leaves as float4s
+    for (const void *p : f32) bad = bad || ptr_misaligned(p, 4);
+    if (bad) return tap_fail(ctx, TAP_E_INVALID, "pointer scores backward: bits must be 8-byte, dU 16-byte and the other float buffers 4-byte aligned");
+    const PtrGeom geo = ptr_geom(B, nR, rows, Hd, true);
+    const PtrArgs a = {proj, bits, M, k, q, va, vp, nullptr, const_cast<float *>(attn), const_cast<float *>(t), g, dU_out, dq_out,
+                       static_cast<float *>(scratch), B, nR, rows, Hd, geo.planes, geo.epb, geo.ct};
+    hipStream_t st = (hipStream_t)stream;
+    if (geo.hpl == 1) hipLaunchKernelGGL((k_pointer_scores_bw<1>), dim3((unsigned)geo.blocks), dim3(TAP_BLOCK), geo.lds, st, a);
+    else hipLaunchKernelGGL((k_pointer_scores_bw<2>), dim3((unsigned)geo.blocks), dim3(TAP_BLOCK), geo.lds, st, a);
+    TAP_LAUNCH_CHECK(ctx, "k_pointer_scores_bw");
+    hipLaunchKernelGGL(k_pointer_scores_bw_reduce, dim3((unsigned)((2 * Hd + TAP_BLOCK - 1) / TAP_BLOCK)), dim3(TAP_BLOCK), 0, st,
+                       static_cast<const float *>(scratch), geo.blocks, Hd, dva_out, dvp_out);
+    TAP_LAUNCH_CHECK(ctx, "k_pointer_scores_bw_reduce");
+    tap_variant_hit(ctx, TAP_HIT_POINTER, 0, geo.hpl, TapVariant{geo.planes, geo.nch, 1}, 0);
+    return TAP_OK;
+}

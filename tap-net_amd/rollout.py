@@ -302,6 +302,127 @@ def encode_dynamic_bits(bits, weight, bias=None, rows=None):
     return out
 
 
+def pointer_scores_supported(rows, nR, Hd):
+    """whether tap_pointer_scores has a kernel for this shape: a window with a shadow and Hd 64, 128 or 256"""
+    return int(Hd) in (64, 128, 256) and _lib.lib().tap_bits_words(int(rows), int(nR)) > 0
+
+
+def _scores_into(proj, bits, M, k, q, va, vp, rows, logits, attn, t):
+    """tap_pointer_scores on prepared buffers: one launch on the current stream, nothing allocated"""
+    dev = proj.device
+    c = _lib.ctx(dev)
+    B, _, nR, Hd = (int(v) for v in proj.shape)
+    _lib.check(_lib.lib().tap_pointer_scores(c, _lib.ptr(proj), _lib.ptr(bits), B, nR, rows, Hd, _lib.ptr(M), _lib.ptr(k),
+                                             _lib.ptr(q), _lib.ptr(va), _lib.ptr(vp), _lib.ptr(logits), _lib.ptr(attn),
+                                             _lib.ptr(t), _lib.stream_of(dev)), c)
+
+
+class _PointerScores(torch.autograd.Function):
+    """pointer_scores under autograd: forward = the one launch, backward = tap_pointer_scores_backward (dU, dq, dva, dvp)
+    and tap_encode_bits_backward on dU (dM, dk).  What a step keeps beside its inputs: a CLONE of the shadow (the
+    stepper's shadow buffers alternate and are overwritten two steps later), attn (B, nR), t and q (B, Hd) -- nothing of
+    size Hd * nR per env; ``proj`` is the episode's one tensor, kept by reference."""
+
+    @staticmethod
+    def forward(ctx, proj, bits, M, k, q, va, vp, rows):
+        B, _, nR, Hd = (int(v) for v in proj.shape)
+        dev = proj.device
+        logits = torch.empty(B, nR, dtype=torch.float32, device=dev)
+        attn = torch.empty(B, nR, dtype=torch.float32, device=dev)
+        t = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+        _scores_into(proj, bits, M, k, q, va, vp, rows, logits, attn, t)
+        ctx.save_for_backward(proj, bits.clone(), M, k, q, va, vp, attn, t)
+        ctx.rows = rows
+        return logits
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        proj, bits, M, k, q, va, vp, attn, t = ctx.saved_tensors
+        B, _, nR, Hd = (int(v) for v in proj.shape)
+        rows, dev = ctx.rows, proj.device
+        L, c = _lib.lib(), _lib.ctx(dev)
+        dva = torch.empty(Hd, dtype=torch.float32, device=dev)
+        dvp = torch.empty(Hd, dtype=torch.float32, device=dev)
+        dM = torch.empty(3 * Hd, rows, dtype=torch.float32, device=dev)
+        dk = torch.empty(3 * Hd, dtype=torch.float32, device=dev)
+        dU = torch.empty(B, 3 * Hd, nR, dtype=torch.float32, device=dev)
+        dq = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+        if B == 0:
+            for z in (dva, dvp, dM, dk):
+                z.zero_()
+            return dU.view(B, 3, Hd, nR).transpose(2, 3), None, dM, dk, dq, dva, dvp, None
+        g = _as_f32(g, dev)
+        need = int(L.tap_pointer_scores_backward_scratch(B, nR, rows, Hd))
+        need2 = int(L.tap_encode_bits_backward_scratch(B, nR, rows, 3 * Hd))
+        scratch = torch.empty(max(need, need2, 16) // 4, dtype=torch.float32, device=dev)
+        st = _lib.stream_of(dev)
+        _lib.check(L.tap_pointer_scores_backward(c, _lib.ptr(proj), _lib.ptr(bits), B, nR, rows, Hd, _lib.ptr(M), _lib.ptr(k),
+                                                 _lib.ptr(q), _lib.ptr(va), _lib.ptr(vp), _lib.ptr(attn), _lib.ptr(t), _lib.ptr(g),
+                                                 _lib.ptr(dU), _lib.ptr(dq), _lib.ptr(dva), _lib.ptr(dvp), _lib.ptr(scratch), need,
+                                                 st), c)
+        # dM[x, r] = sum over (b, c) of dU[b, x, c] bit[b, r, c], dk[x] = sum of dU: the encoder's backward with H = 3 Hd
+        _lib.check(L.tap_encode_bits_backward(c, _lib.ptr(bits), _lib.ptr(dU), B, nR, rows, 3 * Hd, _lib.ptr(dM), _lib.ptr(dk),
+                                              _lib.ptr(scratch), need2, st), c)
+        # dproj is dU read in proj's layout (B, 3, nR, Hd): a view, not a copy
+        return dU.view(B, 3, Hd, nR).transpose(2, 3), None, dM, dk, dq, dva, dvp, None
+
+
+def pointer_scores(proj, bits, M, k, q, va, vp, rows=None):
+    """The pointer network's glimpse and logits on the bit shadow (tapenv.h: tap_pointer_scores; model.py:38-138 after
+    the GRU step) in ONE launch -> logits (B, nR) float32, the reference's ``probs`` before the head.
+    ``proj`` (B, 3, nR, Hd): the per-episode projection of static_hidden, segment-major and hidden fastest
+    (``tools.Pointer.project_static`` builds it); ``bits`` int64 in ``pack.dynamic_bits`` layout, (B, nR) -- (B, 2 * nR) or
+    (B, 2, nR) above 64 rows; ``M`` (3 Hd, rows) and ``k`` (3 Hd,) the dynamic encoder folded into the two W; ``q`` (B, Hd)
+    the decoder's part of the attention; ``va`` / ``vp`` (Hd,) the two v.  ``rows`` defaults to ``M.shape[1]``; bits at
+    positions >= rows are ignored.  Per env and column, in fp32 and in an order fixed by the shape:
+    U = proj + (k + the M columns of the set rows, ascending); s = va . tanh(U[:Hd] + q); attn = softmax over all columns;
+    t = U[2Hd:] . attn; logits = vp . tanh(U[Hd:2Hd] + t).  Floating inputs of another dtype, layout or device are converted
+    through ``.float()`` (autograd sees the cast).  With grad enabled and any floating input requiring grad the call runs
+    through a ``torch.autograd.Function`` whose backward is tap_pointer_scores_backward + tap_encode_bits_backward
+    (deterministic: no atomics); per step it keeps a clone of ``bits``, ``attn`` (B, nR), ``t`` and ``q`` (B, Hd).  A shape
+    without a kernel (``pointer_scores_supported``) raises ValueError."""
+    if bits.dtype is not torch.int64:
+        raise TypeError("bits must be the int64 shadow (pack.dynamic_bits), got %s" % (bits.dtype,))
+    if proj.dim() != 4 or int(proj.shape[1]) != 3 or not proj.is_floating_point():
+        raise ValueError("proj must be a floating (B, 3, nR, Hd) tensor, got %s %s" % (proj.dtype, tuple(proj.shape)))
+    B, _, nR, Hd = (int(v) for v in proj.shape)
+    if M.dim() != 2 or int(M.shape[0]) != 3 * Hd or not M.is_floating_point():
+        raise ValueError("M must be a floating (%d, rows) tensor, got %s %s" % (3 * Hd, M.dtype, tuple(M.shape)))
+    rows = int(M.shape[1]) if rows is None else int(rows)
+    if rows != int(M.shape[1]):
+        raise ValueError("M has %d rows' columns, rows is %d" % (int(M.shape[1]), rows))
+    for name, v, shape in (("k", k, (3 * Hd,)), ("q", q, (B, Hd)), ("va", va, (Hd,)), ("vp", vp, (Hd,))):
+        if tuple(v.shape) != shape or not v.is_floating_point():
+            raise ValueError("%s must be a floating %s tensor, got %s %s" % (name, shape, v.dtype, tuple(v.shape)))
+    planes = 2 if rows > 64 else 1
+    if rows < 1 or nR < 1 or not pointer_scores_supported(rows, nR, Hd):
+        raise ValueError("no pointer kernel for rows %d, nR %d, Hd %d (rows <= 128, nR %% 4 == 0, nR <= 256, Hd 64 / 128 / 256)"
+                         % (rows, nR, Hd))
+    if bits.dim() not in (2, 3) or int(bits.shape[0]) != B or int(math.prod(bits.shape[1:])) != planes * nR or \
+            (bits.dim() == 3 and tuple(bits.shape[1:]) != (planes, nR)):
+        raise ValueError("bits of shape %s is not the shadow of %d envs of a (%d, %d) window" % (tuple(bits.shape), B, rows, nR))
+    dev = _lib.resolve_device(bits.device)
+    if not bits.is_contiguous() or bits.device != dev:
+        bits = bits.to(dev).contiguous()
+
+    def prep(t):
+        if t.dtype is not torch.float32:
+            t = t.float()
+        if not t.is_contiguous() or t.device != dev:
+            t = t.to(dev).contiguous()
+        return t
+    args = [prep(v) for v in (proj, M, k, q, va, vp)]
+    if torch.is_grad_enabled() and any(v.requires_grad for v in args):
+        return _PointerScores.apply(args[0], bits, *args[1:], rows)
+    proj, M, k, q, va, vp = (v.detach() for v in args)
+    logits = torch.empty(B, nR, dtype=torch.float32, device=dev)
+    attn = torch.empty(B, nR, dtype=torch.float32, device=dev)
+    t = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+    _scores_into(proj, bits, M, k, q, va, vp, rows, logits, attn, t)
+    return logits
+
+
 class PointerHeadPolicy(object):
     """A pointer network's decoding head as a policy for ``run_episode`` and the steppers (model.py:356-372):
     ``scorer(step=, static=, dynamic=, current_mask=, mask=, decoder_static=, decoder_dynamic=)`` returns the logits

@@ -104,6 +104,107 @@ class DynamicBitsEncoder(nn.Module):
         return F.conv1d(x, self.conv.weight, self.conv.bias)
 
 
+class _Attention(nn.Module):
+    """The reference's Attention (model.py:38-74) as a parameter holder: ``v`` (1, 1, Hd) and ``W`` (1, Hd, 2 He + Hd),
+    columns [static | dynamic | decoder]; Pointer.forward does its arithmetic."""
+
+    def __init__(self, encoder_hidden_size, decoder_hidden_size):
+        super(_Attention, self).__init__()
+        self.v = nn.Parameter(torch.zeros((1, 1, decoder_hidden_size), requires_grad=True))
+        self.W = nn.Parameter(torch.zeros((1, decoder_hidden_size, 2 * encoder_hidden_size + decoder_hidden_size),
+                                          requires_grad=True))
+
+
+class Pointer(nn.Module):
+    """The reference actor's ``pointer`` (model.py:77-138; its Attention, model.py:38-74) with a second input form.  The
+    constructor is the reference's and so are the parameter names and shapes -- ``W`` (1, Hd, 4 He), ``v`` (1, 1, Hd),
+    ``encoder_attn.W`` (1, Hd, 2 He + Hd), ``encoder_attn.v``, ``gru.*`` --: a reference checkpoint's ``pointer.*`` loads
+    with ``strict=True``.  He / Hd are ``encoder_hidden_size`` / ``decoder_hidden_size``.
+
+    ``forward(static_hidden, dynamic_hidden, decoder_hidden, last_hh)`` -> (probs (B, nR), last_hh): the reference's
+    arithmetic in torch, any dtype and device.
+
+    ``project_static(static_hidden)`` -> proj (B, 3, nR, Hd), once per episode, differentiable: what the two W do to
+    static_hidden, in ``rollout.pointer_scores``' layout.  ``forward_bits(proj, bits, dynamic_encoder, decoder_hidden,
+    last_hh)`` -> (logits, last_hh): the GRU step and both dropouts in torch exactly as ``forward`` runs them, the
+    dynamic encoder's ``conv`` folded into the two W under autograd (M, k), q from the GRU's output, then ONE launch from
+    the int64 shadow ``bits`` (a stepper's ``dynamic_bits``) to the logits: no dynamic_hidden, no concatenation.  On a
+    shape without a kernel ``forward_bits`` runs ``forward`` on ``dynamic_encoder(bits)`` and the static_hidden that
+    ``project_static`` was given (the returned tensor carries it as ``proj.static_hidden``)."""
+
+    def __init__(self, encoder_hidden_size, decoder_hidden_size, decoder_input_type, input_type, num_layers=1, dropout=0.2):
+        super(Pointer, self).__init__()
+        self.encoder_hidden_size = encoder_hidden_size
+        self.decoder_hidden_size = decoder_hidden_size
+        self.num_layers = num_layers
+        self.decoder_input_type = decoder_input_type
+        self.input_type = input_type
+        self.v = nn.Parameter(torch.zeros((1, 1, decoder_hidden_size), requires_grad=True))
+        self.W = nn.Parameter(torch.zeros((1, decoder_hidden_size, 4 * encoder_hidden_size), requires_grad=True))
+        self.gru = nn.GRU(decoder_hidden_size, decoder_hidden_size, num_layers, batch_first=True,
+                          dropout=dropout if num_layers > 1 else 0)
+        self.encoder_attn = _Attention(encoder_hidden_size, decoder_hidden_size)
+        self.drop_rnn = nn.Dropout(p=dropout)
+        self.drop_hh = nn.Dropout(p=dropout)
+
+    def _gru_step(self, decoder_hidden, last_hh):
+        """model.py:108-115: the GRU step and the two dropouts -> rnn_out (B, Hd), last_hh"""
+        rnn_out, last_hh = self.gru(decoder_hidden.transpose(2, 1), last_hh)
+        rnn_out = self.drop_rnn(rnn_out.squeeze(1))
+        if self.num_layers == 1:
+            last_hh = self.drop_hh(last_hh)         # with more layers the GRU has applied it
+        return rnn_out, last_hh
+
+    def forward(self, static_hidden, dynamic_hidden, decoder_hidden, last_hh):
+        rnn_out, last_hh = self._gru_step(decoder_hidden, last_hh)
+        B, nR = static_hidden.size(0), static_hidden.shape[-1]
+        encoder_hidden = torch.cat((static_hidden, dynamic_hidden), 1)
+        # Attention.forward (model.py:55-74)
+        hidden = torch.cat((encoder_hidden, rnn_out.unsqueeze(2).repeat(1, 1, nR)), 1)
+        at = self.encoder_attn
+        attns = torch.bmm(at.v.expand(B, 1, -1), torch.tanh(torch.bmm(at.W.expand(B, -1, -1), hidden)))
+        enc_attn = F.softmax(attns, dim=2)
+        context = enc_attn.bmm(encoder_hidden.permute(0, 2, 1))                       # (B, 1, 2 He)
+        context = context.transpose(1, 2).expand_as(encoder_hidden)
+        energy = torch.cat((encoder_hidden, context), dim=1)
+        probs = torch.bmm(self.v.expand(B, -1, -1), torch.tanh(torch.bmm(self.W.expand(B, -1, -1), energy))).squeeze(1)
+        return probs, last_hh
+
+    def folded_weights(self):
+        """-> Ws, Wd (3 Hd, He): the columns of the two W that meet static_hidden / dynamic_hidden, stacked as the
+        attention's, the pointer's and the context's segment; Wq (Hd, Hd): the attention's columns for the decoder"""
+        He = self.encoder_hidden_size
+        Wa, Wp = self.encoder_attn.W[0], self.W[0]
+        Ws = torch.cat((Wa[:, :He], Wp[:, :He], Wp[:, 2 * He:3 * He]), 0)
+        Wd = torch.cat((Wa[:, He:2 * He], Wp[:, He:2 * He], Wp[:, 3 * He:4 * He]), 0)
+        return Ws, Wd, Wa[:, 2 * He:]
+
+    def project_static(self, static_hidden):
+        Ws = self.folded_weights()[0]
+        B, He, nR = static_hidden.shape
+        proj = torch.matmul(static_hidden.transpose(1, 2), Ws.t().to(static_hidden.dtype))       # (B, nR, 3 Hd)
+        proj = proj.view(B, nR, 3, self.decoder_hidden_size).permute(0, 2, 1, 3).contiguous()
+        proj.static_hidden = static_hidden
+        return proj
+
+    def forward_bits(self, proj, bits, dynamic_encoder, decoder_hidden, last_hh):
+        from .rollout import pointer_scores, pointer_scores_supported
+        conv = dynamic_encoder.conv
+        rows, nR, Hd = int(conv.weight.shape[1]), int(proj.shape[2]), self.decoder_hidden_size
+        if not pointer_scores_supported(rows, nR, Hd):
+            static_hidden = getattr(proj, "static_hidden", None)
+            if static_hidden is None:
+                raise ValueError("no pointer kernel for rows %d, nR %d, Hd %d, and proj does not come from project_static: "
+                                 "call forward(static_hidden, dynamic_encoder(bits), ...)" % (rows, nR, Hd))
+            return self.forward(static_hidden, dynamic_encoder(bits), decoder_hidden, last_hh)
+        rnn_out, last_hh = self._gru_step(decoder_hidden, last_hh)
+        _, Wd, Wq = self.folded_weights()
+        M = Wd.matmul(conv.weight[:, :, 0])
+        k = Wd.matmul(conv.bias) if conv.bias is not None else torch.zeros_like(Wd[:, 0])
+        q = rnn_out.matmul(Wq.t())
+        return pointer_scores(proj, bits, M, k, q, self.encoder_attn.v[0, 0], self.v[0, 0], rows=rows), last_hh
+
+
 class _EngineRow(object):
     """net.engines[b] after a PackRNN forward: the reference's per-instance PackEngine, read-only (get_heightap)"""
 
