@@ -12,11 +12,18 @@ replayed from a pre-computed feasible tape:
     [-> when N > 1, the (B,) reward vectors of 8 consecutive passes are all-gathered with one RCCL call]
 
 value = env-steps/s = (placements in all envs on all ranks) / wall time, inputs resident in HBM before
-the timed region.  After the timed region (outside it) the outputs of the LAST replayed pass are
-compared with the CPU oracle on a slice of the batch ("verified"); a mismatch exits non-zero.
+the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5|c6|k6] [--batch B]
-                    [--no-graph] [--no-cpu-baseline] [--no-variants] [--sweep [--sweep-out FILE]]
+A plain run does what that figure needs and nothing else: set-up, warm-up, the timed brackets, --dump-outputs,
+the one JSON line.  Everything else the benchmark measures or checks sits behind --full (off by default) and runs
+after the timed region, outside it: the outputs of the LAST replayed pass compared with the CPU oracle on a
+slice of the batch ("verified"; a mismatch exits non-zero), the per-kernel event times and the `roofline`
+object, `roofline.cold`, the other BASELINE configs (`configs`), `cpu_baseline`, `variants` and --sweep.  The
+--no-* options below trim a --full run; a plain run has nothing for them to trim.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5|c6|k6] [--batch B] [--no-graph]
+                    [--full [--configs LIST] [--no-cold] [--no-cpu-baseline] [--no-variants] [--no-verify]
+                            [--sweep [--sweep-out FILE]]]
 
 --gpus N > 1: launched by torch.distributed.run (one rank per GPU, RCCL) the ranks find each other
 through RANK / WORLD_SIZE / MASTER_*; launched as plain `python bench.py --gpus N` the script spawns the N
@@ -1782,8 +1789,13 @@ def main():
                     help="timed brackets of exactly --steps passes each (barrier + synchronize on both sides, MAX over "
                          "ranks); value is their median, the line carries all of them")
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run everything else the benchmark measures or checks: the oracle "
+                         "comparison of the last pass (`verified`), per-kernel event times and `roofline` (with "
+                         "`roofline.cold`), the other BASELINE configs (`configs`), `cpu_baseline`, `variants`, --sweep.  "
+                         "Off by default: a plain run sets up, warms up, times its steps and prints the line")
     ap.add_argument("--configs", default=None,
-                    help="comma-separated BASELINE configs measured after the headline and reported in the line's `configs` "
+                    help="with --full: comma-separated BASELINE configs measured after the headline and reported in the line's `configs` "
                          "object (default: c3,c4,c5 when the headline is c2 at its own batch on one GPU; 'none' to skip)")
     ap.add_argument("--configs-batch", type=int, default=None, help="per-GPU batch of the `configs` entries (self-tests)")
     ap.add_argument("--no-cold", action="store_true", help="skip roofline.cold (the pass with nothing cache-resident)")
@@ -1798,7 +1810,7 @@ def main():
                     help="c4: RAND-marginal synthetic instances instead of the reference-generated PPSG fixture tiled x128")
     ap.add_argument("--no-bits", action="store_true",
                     help="precedence update as an fp32 copy (tap_transition) instead of on the bit shadow (tap_transition_bits)")
-    ap.add_argument("--sweep", action="store_true", help="also run a batch sweep (stderr; --sweep-out appends JSON lines)")
+    ap.add_argument("--sweep", action="store_true", help="with --full: also run a batch sweep (stderr; --sweep-out appends JSON lines)")
     ap.add_argument("--sweep-out", default=None)
     ap.add_argument("--sweep-batches", default=None, help="comma-separated batch sizes (multiples of --batch) instead of the powers of two")
     ap.add_argument("--two-launch-rolling", action="store_true",
@@ -1815,6 +1827,13 @@ def main():
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="write what the headline's last timed pass computed as DIR/<name>.npy (rank 0's envs, at most 64 MB)")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: the headline figure only.  What asks for a reading that lives behind --full is refused, not
+        # dropped in silence; from here on a plain run is a --full run with every leg switched off
+        if args.sweep or args.configs not in (None, "none"):
+            ap.error("--sweep and --configs measure beyond the headline figure: add --full")
+        args.configs = "none"
+        args.no_verify = args.no_cold = args.no_cpu_baseline = args.no_variants = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # launched as plain `python bench.py --gpus N`: spawn the N ranks here (one process per GPU)
@@ -1860,7 +1879,7 @@ def main():
     total_steps = B * world * n * args.steps
     value = total_steps / dt
     # every rank checks its own last pass against the oracle; the line says "verified" only if all did
-    ver = dict(verified=None, why="--no-verify") if args.no_verify else hp.verify()
+    ver = dict(verified=None, why="--no-verify" if args.full else "a plain run: --full compares with the oracle") if args.no_verify else hp.verify()
     if getattr(hp, "gathered_ok", None) is not None and not args.no_verify:
         ver["gathered_rows_match"] = hp.gathered_ok           # this rank's block of the last all-gather == its rows
         if not hp.gathered_ok:
@@ -1915,7 +1934,8 @@ def main():
 
     out = None
     if rank == 0:
-        roof, kernels = roofline_of(hp, args.config, cfg, rolling, args.steps, graphs)
+        # the per-kernel event times replay the pass (eager, hooked, graphed) in runs of their own: --full only
+        roof, kernels = roofline_of(hp, args.config, cfg, rolling, args.steps, graphs) if args.full else (None, None)
         if rolling:
             inst = ("MIX (pack.py:67-97): envs [0,B/2) perfect-packing (PPSG) instances, [B/2,B) RAND, both device-generated "
                     "into a 7x7x250 initial container.  PPSG = generate_blocks_with_GT's steps on 5 stacked 10-block "
@@ -1973,9 +1993,10 @@ def main():
             "config": {"workload": name, "batch_per_gpu": B, "nodes": n, "window_nodes": hp.nw, "container": cs,
                        "reward_type": reward, "packing_strategy": strategy, "instances": inst, "pass": pas,
                        "launch": ("hipGraph replay, %d passes per graph launch" % getattr(hp, "passes_per_graph", GATHER_EVERY)) if use_graph else "eager"},
-            "roofline": roof,
-            "kernels": kernels,
+            "full": args.full,
         }
+        if args.full:
+            out["roofline"], out["kernels"] = roof, kernels
         if world == 1 and not args.no_cold and hp.kind in ("transition", "rolling") and not args.no_variants:
             try:
                 hp.cold = cold_reading(cfg, hp, rolling, dev, use_graph)

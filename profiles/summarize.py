@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
-"""Condense rocprofv3 output (gpurun_out/prof_<tag>*/) into the tracked summaries under profiles/.
+"""Condense rocprofv3 output ($PROFILE_OUT/prof_<tag>*/, default profile_out/ in the repository root) into the tracked summaries under profiles/.
 
     python profiles/summarize.py <tag> <config>      e.g.  r01 c2
 
 Inputs (written on the GPU box by the commands in profiles/README.md):
-    gpurun_out/prof_<tag>/<config>_kernel_stats.csv              rocprofv3 --kernel-trace --stats
-    gpurun_out/prof_<tag>_fetch/<config>_counter_collection.csv  rocprofv3 --kernel-trace --pmc FETCH_SIZE
-    gpurun_out/prof_<tag>_write/<config>_counter_collection.csv  rocprofv3 --kernel-trace --pmc WRITE_SIZE
+    <out>/prof_<tag>/<config>_kernel_stats.csv              rocprofv3 --kernel-trace --stats
+    <out>/prof_<tag>_fetch/<config>_counter_collection.csv  rocprofv3 --kernel-trace --pmc FETCH_SIZE
+    <out>/prof_<tag>_write/<config>_counter_collection.csv  rocprofv3 --kernel-trace --pmc WRITE_SIZE
 Outputs:
     profiles/<tag>_<config>_kernel_stats.csv   copy of the --stats summary
     profiles/<tag>_<config>_pmc_summary.csv    per-kernel mean FETCH_SIZE / WRITE_SIZE (KB, raw)
@@ -51,7 +51,7 @@ def short_name(k):
 def main():
     global tag, cfg
     tag, cfg = sys.argv[1], sys.argv[2]
-    src = os.path.join(ROOT, "gpurun_out")
+    src = os.environ.get("PROFILE_OUT") or os.path.join(ROOT, "profile_out")
     # the --stats summary, our kernels row by row, everything else (torch / rocprim / runtime copy and fill kernels of the
     # set-up code) summed in one line
     rows = list(csv.DictReader(open(os.path.join(src, "prof_%s" % tag, "%s_kernel_stats.csv" % cfg))))
@@ -105,7 +105,7 @@ def main():
                         "`profile` names the profile set (profiles/<profile>_<config>_*.csv) the entry comes from")
     traffic["_source"] = "profiles/summarize.py"
     json.dump(traffic, open(tpath, "w"), indent=1, sort_keys=True)
-    # bench lines under profiles/ come from clean runs (gpurun_out/bench_<tag>/<cfg>.json), never from the
+    # bench lines under profiles/ come from clean --full runs (<out>/bench_<tag>/<cfg>.json), never from the
     # profiled run, whose timings the tracer perturbs
     bj = os.path.join(src, "bench_%s" % tag, "%s.json" % cfg)
     if os.path.exists(bj) and os.path.getsize(bj):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Mean per launch of every counter of a rocprofv3 --pmc pass, per kernel:
     python profiles/summarize_sq.py <tag> <config> <name> [kernel-substring]
-reads gpurun_out/prof_<tag>_sq/<config>_<name>_counter_collection.csv, writes profiles/<tag>_<config>_<name>_summary.csv"""
+reads $PROFILE_OUT/prof_<tag>_sq/<config>_<name>_counter_collection.csv (default: profile_out/ in the repository root), writes profiles/<tag>_<config>_<name>_summary.csv"""
 import collections
 import csv
 import os
@@ -10,7 +10,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag, cfg, name = sys.argv[1:4]
 want = sys.argv[4] if len(sys.argv) > 4 else "k_"
-path = os.path.join(ROOT, "gpurun_out", "prof_%s_sq" % tag, "%s_%s_counter_collection.csv" % (cfg, name))
+path = os.path.join(os.environ.get("PROFILE_OUT") or os.path.join(ROOT, "profile_out"), "prof_%s_sq" % tag, "%s_%s_counter_collection.csv" % (cfg, name))
 acc = collections.defaultdict(list)
 for r in csv.DictReader(open(path)):
     if want in r["Kernel_Name"]:

@@ -35,7 +35,7 @@ else
   for rep in 1 2; do
   for v in $VARIANTS; do
     name=${v%%:*}
-    TAP_LIB_PATH=$PWD/build_prof/libtapenv_ab_$name.so python bench.py --config $cfg ${AB_FLAGS} --steps ${AB_STEPS:-100} --warmup 5 --no-variants --no-cpu-baseline 2>/dev/null | \
+    TAP_LIB_PATH=$PWD/build_prof/libtapenv_ab_$name.so python bench.py --config $cfg ${AB_FLAGS} --steps ${AB_STEPS:-100} --warmup 5 --full --no-variants --no-cpu-baseline 2>/dev/null | \
       python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%-10s %s  %8.1f M env-steps/s  %s %.3f us  verified %s' % ('$name', '$cfg', d['value']/1e6, d['roofline']['kernel'], d['roofline']['kernel_us'], d['verified']))"
   done; done; done
 fi

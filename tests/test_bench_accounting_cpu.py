@@ -1,7 +1,10 @@
 """bench.py's byte accounting (no GPU needed): the SURVEY 8(d) per-env-step figures the line reports as
-`frac_alg_survey`, and the compulsory bytes of the implemented kernels that `roofline.achieved` prices."""
+`frac_alg_survey`, and the compulsory bytes of the implemented kernels that `roofline.achieved` prices; and the command line's refusal of --full readings without --full."""
 import importlib.util
 import os
+import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -37,6 +40,19 @@ def test_compulsory_bytes_of_the_implemented_kernels():
     for D, cs, n in ((2, [5, 50], 10), (3, [5, 5, 50], 10), (2, [7, 100], 20)):
         env, mask = b.algorithmic_bytes(D, cs, n)
         assert b.compulsory_bytes("transition", D, cs, n) < env + mask
+
+
+@pytest.mark.parametrize("argv", [["--sweep"], ["--configs", "c3"], ["--gpus", "1", "--steps", "3", "--configs", "c3,c5"]],
+                         ids=lambda a: " ".join(a))
+def test_readings_behind_full_are_refused_without_it(argv, monkeypatch, capsys):
+    """--sweep and --configs ask for readings that live behind --full: without it the command line is refused
+    (argparse's exit status 2, the message names --full) before anything touches a GPU."""
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    with pytest.raises(SystemExit) as ex:
+        b.main()
+    assert ex.value.code == 2
+    assert "--full" in capsys.readouterr().err
 
 
 def test_configs_name_the_baseline_workloads():
