@@ -733,6 +733,23 @@ __device__ __forceinline__ void stream_wave_bits_r4(const MaskArgs &a, int senv0
 #else
     constexpr bool BJ_X = !BUILD && NC == 1 && NS == 1 && (C4S == 5 || C4S == 15);
 #endif
+    // NOMASK waves (two slabs of the 2D window, mode 77) take their inputs with TWO vector loads instead of six.  The wave
+    // needs 2 x (80 B of row 0 + 160 B of shadow words); the quad layout -- every lane loads the 32 bytes of its column quad,
+    // per slab, twelve lanes to a quad -- brings 4.6 KB back through the CU's vector-memory return path for them.  Here
+    // lane j < 40 loads word j of the wave's 40 contiguous words (one 8-byte load) and row-0 element j % 20 of slab j / 20
+    // (one dword load; lanes >= 40 repeat lane 39's addresses), the pick reads row 0 at lane p (slab 0) and 20 + p (slab 1), and the words reach
+    // the lanes' quads through the wave's own LDS tile: ds_write_b64 by the 40 lanes, the wave-level hand-off, 16-byte
+    // reads at tile + k * 160 + c4 * 32 (+ 16).  The new shadow words leave as ONE 8-byte store of the 40 lanes (320
+    // contiguous bytes, all 64 bits of a word & ~clear) instead of four 16-byte stores of the first_row lanes.  The
+    // expansion, its lane roles and its stores are what they were.  Same session, c2: 1 577 -> 1 616 M env-steps/s; the
+    // wave's inputs arrive 0.68 instead of 1.12 us (median) after the launch's first wave.
+    // -DTAP_STREAM_QUAD_LOADS: the quad loads (A/B builds).
+#ifdef TAP_STREAM_QUAD_LOADS
+    constexpr bool LDSIN = false;
+#else
+    constexpr bool LDSIN = NOMASK;
+#endif
+    static_assert(!LDSIN || (NS == 2 && NC == 1 && C4S == 5 && MERGED && !INPLACE), "the mask wave's stream waves: two slabs of the 10-node 2D window");
     typedef unsigned long long u64;
     static_assert(NS <= 2, "a stream wave expands one or two slabs");
     if (!on[0]) return;                                  // on[] is a prefix and wave-uniform: no env, nothing to do
@@ -770,19 +787,31 @@ __device__ __forceinline__ void stream_wave_bits_r4(const MaskArgs &a, int senv0
     for (int k = 0; k < NS; ++k) {
         const int env = on[k] ? senv0 + k : senv0;       // an idle slab re-reads the first one's inputs
         praw[k] = ptrp[has_ptr ? env : 0];
-        const float *strow = stp + (has_static ? (size_t)env * a.static_rows * nR : (size_t)0);
-        const float *mirow = mip + (has_mask ? (size_t)env * nR : (size_t)0);
+        if constexpr (!LDSIN) {
+            const float *strow = stp + (has_static ? (size_t)env * a.static_rows * nR : (size_t)0);
+            const float *mirow = mip + (has_mask ? (size_t)env * nR : (size_t)0);
 #pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const unsigned j = (unsigned)min(lane + 64 * c, nR - 1);
-            row0[k][c] = strow[has_static ? j : 0u];
-            if constexpr (!NOMASK) keep[k][c] = mirow[has_mask ? j : 0u];
+            for (int c = 0; c < NC; ++c) {
+                const unsigned j = (unsigned)min(lane + 64 * c, nR - 1);
+                row0[k][c] = strow[has_static ? j : 0u];
+                if constexpr (!NOMASK) keep[k][c] = mirow[has_mask ? j : 0u];
+            }
         }
+    }
+    u64 wrun = 0;                                        // LDSIN: word `lane` of the wave's run of NS * nR shadow words
+    if constexpr (LDSIN) {
+        // one scalar base per input and a lane offset: slab 1's row 0 lies static_rows * nR floats behind slab 0's
+        const unsigned j = (unsigned)min(lane, NS * nR - 1);
+        const unsigned js = j < (unsigned)nR ? j : j + (unsigned)(a.static_rows * nR - nR);
+        const float r0v = (a.static_ + (size_t)senv0 * a.static_rows * nR)[js];
+        wrun = (a.bits_in + (size_t)senv0 * nR)[j];
+#pragma unroll
+        for (int k = 0; k < NS; ++k) row0[k][0] = r0v;   // the pick reads it at lane k * nR + p
     }
 #ifdef TAP_STREAM_G2          // A/B builds: the shadow words requested only after the small inputs have arrived (round 3's order)
     __builtin_amdgcn_s_waitcnt(0x0F70);
 #endif
-    if (!BUILD) {
+    if (!BUILD && !LDSIN) {
 #pragma unroll
         for (int k = 0; k < NS; ++k) {
             const int env = on[k] ? senv0 + k : senv0;
@@ -824,6 +853,18 @@ __device__ __forceinline__ void stream_wave_bits_r4(const MaskArgs &a, int senv0
 #ifdef TAP_PROF
     TL_STAMP(1);
 #endif
+    if constexpr (LDSIN) {
+        // the run's words as loaded into the wave's tile (NS * nR words of its NS * 3 * nR floats, a multiple of 16 bytes
+        // behind the 16-byte aligned start of the dynamic LDS), then every lane's column quad of both slabs
+        if (lane < NS * nR) tile[lane] = wrun;
+        tap_wave_lds_sync_m();
+        const ulonglong2 *t4 = static_cast<const ulonglong2 *>(__builtin_assume_aligned(tile, 16)) + role.c4 * 2;
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+            w[k][0] = t4[k * (nR / 2)];
+            w[k][1] = t4[k * (nR / 2) + 1];
+        }
+    }
     const u64 nmask = (n >= 64) ? ~0ull : ((1ull << n) - 1ull);
     // v mod n for a column index (pack.py:314-316): a division by a constant for the compiled-in windows
     auto mod_n = [&](int v) -> int {
@@ -859,7 +900,7 @@ __device__ __forceinline__ void stream_wave_bits_r4(const MaskArgs &a, int senv0
             float r0 = -1.f;                                                  // pack.py:339 via shuffle; stays -1 for an index outside [0, nR)
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
-                const float t = __shfl(row0[k][c], p & 63);
+                const float t = __shfl(row0[k][c], LDSIN ? k * nR + p : p & 63);
                 if (valid && has_static && (p >> 6) == c) r0 = t;
             }
             real = (r0 > -1.f && r0 < (float)rows) ? (int)r0 : -1;            // .long() truncates; a row beyond the tensor clears nothing
@@ -870,7 +911,8 @@ __device__ __forceinline__ void stream_wave_bits_r4(const MaskArgs &a, int senv0
             float r0 = -1.f;
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
-                const float t = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(row0[k][c]), p & 63));
+                const int at = LDSIN ? k * nR + p : p & 63;                      // LDSIN: lane k * nR + j holds slab k's row 0 at j (p < nR)
+                const float t = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(row0[k][c]), at));
                 if (valid && has_static && (p >> 6) == c) r0 = t;
             }
             real = __builtin_amdgcn_readfirstlane((r0 > -1.f && r0 < (float)rows) ? (int)r0 : -1);
@@ -1010,7 +1052,10 @@ __device__ __forceinline__ void stream_wave_bits_r4(const MaskArgs &a, int senv0
                 }
             }
         }
-        if (first_row && o_bits) {
+        if constexpr (LDSIN) {
+            // the run's new words from the lanes that loaded them (NS * nR <= RP * C4: every one of them is lane_on)
+            if (lane < NS * nR && o_bits) (o_bits + (size_t)senv0 * nR)[lane] = wrun & ~(lane < nR ? clr[0] : clr[NS - 1]);
+        } else if (first_row && o_bits) {
 #pragma unroll
             for (int k = 0; k < NS; ++k) {
                 if (!on[k]) continue;
