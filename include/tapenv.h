@@ -593,7 +593,9 @@ int tap_policy_pick(tap_ctx *ctx, const float *logits, const float *mask, const 
                     int flags, int64_t *ptr_out, float *logp_out, float *probs_out /* or NULL */, void *stream);
 
 /* The backward of logp with respect to the logits (model.py:359-372 under autograd: log_softmax gathered at ptr):
- * dlogits_out[b, c] = g[b] * ((c == ptr[b]) - probs[b, c]) in fp32, one thread per element; probs / ptr / logp as
+ * dlogits_out[b, c] = -g[b] * probs[b, c] in fp32 for c != ptr[b], and the picked column = minus the fp64 sum of the
+ * row's other results, rounded once (g (1 - p[ptr]) with a row that sums to zero within one rounding, as the true
+ * gradient does); one thread per element; probs / ptr / logp as
  * tap_policy_pick wrote them, g (B,) f32 the gradient arriving at logp.  Rows whose logp is NaN (no selectable
  * column) are written as zeros whatever g holds.  The same argument checks (every buffer required). */
 int tap_policy_pick_backward(tap_ctx *ctx, const float *probs, const int64_t *ptr, const float *logp,

@@ -175,6 +175,9 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_policy_pick_wide(PickArgs a)
     }
 }
 
+// dlogits of a column that was not picked: -g p, one fp32 rounding (the picked column's thread recomputes exactly this)
+__device__ __forceinline__ float pick_bw_off(float g, float p) { return -(g * p); }
+
 __global__ void __launch_bounds__(TAP_BLOCK) k_policy_pick_backward(const float *probs, const int64_t *ptr, const float *logp,
                                                                     const float *g, size_t total, int nR, float *dlogits)
 {
@@ -182,9 +185,19 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_policy_pick_backward(const float 
     if (i >= total) return;
     const size_t b = i / (size_t)nR;
     const int c = (int)(i - b * (size_t)nR);
-    const float hit = ptr[b] == (int64_t)c ? 1.f : 0.f;
     const float lp = logp[b];
-    dlogits[i] = lp != lp ? 0.f : g[b] * (hit - probs[i]);      // an empty row (logp NaN) has no gradient
+    if (lp != lp) { dlogits[i] = 0.f; return; }                 // an empty row (logp NaN) has no gradient
+    const float gb = g[b];
+    if (ptr[b] != (int64_t)c) { dlogits[i] = pick_bw_off(gb, probs[i]); return; }
+    // the picked column: 1 - p[ptr] is the sum of the other probabilities, so the column is minus the fp64 sum of the
+    // row's other fp32 RESULTS, rounded once -- the row then sums to zero within that one rounding, as the true gradient
+    // does.  g * (1 - p[ptr]) leaves the roundings of every p in the row sum, and whatever reaches all columns alike
+    // downstream (the attention's context) reads that residue as a gradient
+    const float *row = probs + b * (size_t)nR;
+    double s = 0.0;
+    for (int j = 0; j < nR; ++j)
+        if (j != c) s += (double)pick_bw_off(gb, row[j]);
+    dlogits[i] = (float)-s;
 }
 
 template <int G> int launch_pick(tap_ctx *ctx, const PickArgs &a, bool greedy, hipStream_t st)

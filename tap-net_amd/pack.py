@@ -458,6 +458,15 @@ class EnvTransition(MaskStepper):
         return out, cur, new, feat, ratio
 
 
+def grad_copies(*tensors):
+    """Private copies of buffers a later launch overwrites, for handing to a caller while grad is enabled (None stays
+    None).  The step objects' launches write their buffers through raw pointers, so no version counter moves: an
+    ``nn.Conv1d`` that saved such a buffer for its weight gradient would read a LATER step's values in ``backward()``,
+    without an error.  A copy is what the reference's ``dynamic.clone()`` (pack.py:368) and ``gather`` (model.py:404-406)
+    hand out.  Every seam that publishes a buffer it re-uses calls this, and only when ``torch.is_grad_enabled()``."""
+    return [None if t is None else t.clone() for t in tensors]
+
+
 class NonBinaryDynamic(ValueError):
     """A ``dynamic`` tensor handed to an EpisodeStepper held values other than 0 and 1 (it carries the tensor as
     its bit shadow); rollout.run_episode falls back to the general EnvTransition path."""
@@ -471,10 +480,17 @@ class EpisodeStepper(object):
     arguments -- no tensor is allocated and no torch op is issued between the policy's calls.
 
     After ``begin`` / ``step`` the attributes ``dynamic``, ``current_mask``, ``mask``, ``decoder_dynamic``,
-    ``decoder_static`` hold the values model.py's loop variables of the same names would; they are views of the
-    stepper's buffers: a step overwrites the phase written two steps ago (``inplace_dynamic=True``: ``dynamic`` is ONE
-    tensor that every step updates in place), the next ``begin`` everything -- clone what must outlive that.  ``static`` / ``dynamic`` given to ``begin`` are only read (the trainer re-uses them,
-    trainer.py:214) and are kept referenced for the episode.
+    ``decoder_static`` hold the values model.py's loop variables of the same names would.  Under ``torch.no_grad()`` they
+    are the stepper's own buffers, no copy and no torch op: a step overwrites ``decoder_*`` and the phase of ``dynamic``
+    and the masks written two steps ago, the next ``begin`` everything -- clone what must outlive that.  While grad is
+    enabled (``torch.is_grad_enabled()`` at ``begin`` / ``step``) they are private copies of what the launch just wrote
+    (``grad_copies``: four small copy launches per step), so a network that saves its inputs for ``backward()`` keeps
+    each step's own values, as with the reference's ``dynamic.clone()`` and ``gather``.  ``dynamic_bits`` is always the
+    buffer: ``rollout``'s autograd functions clone the shadow themselves.  ``inplace_dynamic=True`` (``dynamic`` is ONE
+    tensor that every step updates in place) is for loops under ``no_grad``: with grad enabled a step marks that tensor
+    as modified (``torch.autograd.graph.increment_version``), so a ``backward()`` through a network that saved it raises
+    autograd's "modified by an inplace operation" RuntimeError instead of using later values.  ``static`` / ``dynamic``
+    given to ``begin`` are only read (the trainer re-uses them, trainer.py:214) and are kept referenced for the episode.
 
     Shapes are fixed at construction from the example tensors; needs a window with a bit shadow
     (``bits_supported``) and 0/1-valued ``dynamic`` tensors: under ``set_binary_check('check')`` ``begin`` reads
@@ -530,8 +546,10 @@ class EpisodeStepper(object):
         fshape = env._feature_shape()
         flen = int(np.prod(fshape[1:]))
         self._dec = torch.zeros(self.B * (flen + D), **f32)
-        self.decoder_dynamic = self._dec[:self.B * flen].view(fshape)
-        self.decoder_static = self._dec[self.B * flen:].view(self.B, D, 1)
+        self._dec_split = (self.B * flen, tuple(fshape), (self.B, D, 1))
+        self._dec_views = self._split_dec(self._dec)
+        self.decoder_dynamic, self.decoder_static = self._dec_views
+        self._private = False                             # True while decoder_* are grad-mode copies, not the buffer's views
         self.ratio = torch.empty(self.B, **f32)
         # ``tour``: write the picks into columns tour_col0 .. tour_col0 + steps - 1 of the caller's (B, stride) int64
         # tensor (a rolling episode's last window continues the roller's tour) instead of an own (B, steps) one
@@ -576,6 +594,36 @@ class EpisodeStepper(object):
         if h:
             self._destroy(h)
 
+    def _split_dec(self, flat):
+        cut, fshape, sshape = self._dec_split
+        return flat[:cut].view(fshape), flat[cut:].view(sshape)
+
+    def _hand_out_decoder(self):
+        """``decoder_dynamic`` / ``decoder_static`` after a launch (or a copy) wrote the flat buffer: its views under
+        no_grad, views of ONE private copy of it while grad is enabled"""
+        if torch.is_grad_enabled():
+            self.decoder_dynamic, self.decoder_static = self._split_dec(grad_copies(self._dec)[0])
+            self._private = True
+        elif self._private:
+            self.decoder_dynamic, self.decoder_static = self._dec_views
+            self._private = False
+
+    def _hand_out_copies(self, dyn, cur, mask):
+        """grad enabled: what the launch just wrote, as private copies (see the class docstring)"""
+        if self.inplace_dynamic and dyn is not None:
+            torch.autograd.graph.increment_version(dyn)   # ONE tensor by contract: a saved one must not be used silently
+            self.dynamic = dyn
+            self.current_mask, self.mask = grad_copies(cur, mask)
+        else:
+            self.dynamic, self.current_mask, self.mask = grad_copies(dyn, cur, mask)
+        self._hand_out_decoder()
+
+    def load_decoder_inputs(self, flat):
+        """Continue from another step object's decoder inputs (its flat ``_dec`` buffer: a rolling episode's last
+        window goes on from the last rolling step): one copy into the stepper's buffer"""
+        self._dec.copy_(flat)
+        self._hand_out_decoder()
+
     @property
     def launches_per_step(self):
         """1 when a step of this shape is ONE kernel, 2 when the entry point runs the precedence update and the
@@ -604,12 +652,11 @@ class EpisodeStepper(object):
         self.dynamic_bits = self._bits[1] if initial_mask and not self._copy else None
         self._count_in_step0 = not initial_mask and not self._copy
         self._dec.zero_()
-        if self._copy:                                        # begin always makes its launches there: masks and the count exist
+        self._hand_out_decoder()
+        if self._copy or initial_mask:                        # (without a shadow begin always makes its launches: masks and the count exist)
             self.current_mask, self.mask = self._cur[1], self._mask[1]
-            if _binary_mode == 'check':
-                self._raise_nonbinary()
-        elif initial_mask:
-            self.current_mask, self.mask = self._cur[1], self._mask[1]
+            if torch.is_grad_enabled():
+                self.current_mask, self.mask = grad_copies(self.current_mask, self.mask)
             if _binary_mode == 'check':
                 self._raise_nonbinary()
         else:
@@ -634,6 +681,7 @@ class EpisodeStepper(object):
         self.static, self.dynamic, self.k, self._bits0 = static, dynamic, 0, bits
         self.dynamic_bits = bits                          # the caller's shadow is what step 0 reads
         self.current_mask, self.mask = current_mask, self._ones
+        self._hand_out_decoder()
         return self
 
     def step(self, ptr):
@@ -649,8 +697,13 @@ class EpisodeStepper(object):
             _lib.check(rc, self._ctx)
         w = self.k & 1
         self.k += 1
-        self.dynamic, self.current_mask, self.mask = self._views[w]
         self.dynamic_bits = self._bits[w]
+        if torch.is_grad_enabled():
+            self._hand_out_copies(*self._views[w])
+        else:
+            self.dynamic, self.current_mask, self.mask = self._views[w]
+            if self._private:
+                self._hand_out_decoder()
         if self.k == 1 and self._count_in_step0 and _binary_mode == 'check':
             # begin(initial_mask=False) made no launch: step 0 built the shadow and counted the elements that are neither
             # 0 nor 1 -- under 'check' that count is read here (one host sync per episode, as begin() does otherwise)

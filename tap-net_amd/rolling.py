@@ -9,7 +9,7 @@ import torch
 
 from . import _lib
 from .env import BatchedContainer
-from .pack import EnvTransition, EpisodeStepper, bits_supported
+from .pack import EnvTransition, EpisodeStepper, bits_supported, grad_copies
 from .rollout import _flagged_reward
 
 
@@ -181,8 +181,12 @@ class RollingStepper(object):
 
     ``begin(windows)`` emits the first window of a freshly initialised ``RollingWindows`` (of the shape given at
     construction); after it and after every ``step(ptr)`` the attributes ``static``, ``dynamic``, ``nodes``,
-    ``bits`` / ``colsum``, ``current_mask``, ``decoder_dynamic``, ``decoder_static`` describe the CURRENT window --
-    views of the stepper's buffers, overwritten by later steps."""
+    ``bits`` / ``colsum``, ``current_mask``, ``decoder_dynamic``, ``decoder_static`` describe the CURRENT window.  Under
+    ``torch.no_grad()`` they are the stepper's own buffers, overwritten by the next step (``static``: two steps later).
+    While grad is enabled at ``begin`` / ``step``, ``static``, ``dynamic``, ``current_mask`` and ``decoder_*`` are private
+    copies of what the launch wrote (``pack.grad_copies``, as ``pack.EpisodeStepper`` hands them out), so a network
+    that saves its inputs for ``backward()`` keeps each window's own values; ``bits``, ``colsum`` and ``nodes`` stay the
+    buffers."""
 
     def __init__(self, windows, env, want_masks=True, expand_dynamic=True):
         rw = self.windows = windows
@@ -199,9 +203,9 @@ class RollingStepper(object):
         self._nodes = [torch.empty(B, child, dtype=torch.int32, device=dev) for _ in range(2)]
         self.bits = rw._new_bits(nRc) if want_masks else None
         # expand_dynamic=False: no fp32 precedence tensor (``dynamic`` is None, the windows exist as ``bits`` only)
-        self.dynamic = rw._new_dynamic(nRc, self.bits, expand_dynamic)
+        self._dynamic = self.dynamic = rw._new_dynamic(nRc, self.bits, expand_dynamic)
         self.colsum = torch.empty(B, 3, nRc, **f32) if want_masks and self.bits is None else None
-        self.current_mask = torch.empty(B, nRc, **f32) if want_masks else None
+        self._current_mask = self.current_mask = torch.empty(B, nRc, **f32) if want_masks else None
         self._err = torch.zeros(B, dtype=torch.int32, device=dev)
         self._ones = torch.ones(B, nRc, **f32)            # the `mask` of a one-step window (rolling.py:353: a fresh forward)
         fshape = env._feature_shape()
@@ -209,17 +213,19 @@ class RollingStepper(object):
         for v in fshape[1:]:
             flen *= int(v)
         self._dec = torch.zeros(B * (flen + D), **f32)
-        self.decoder_dynamic = self._dec[:B * flen].view(fshape)
-        self.decoder_static = self._dec[B * flen:].view(B, D, 1)
+        self._dec_split = (B * flen, tuple(fshape), (B, D, 1))
+        self._dec_views = self._split_dec(self._dec)
+        self.decoder_dynamic, self.decoder_static = self._dec_views
+        self._private = False                             # True while the attributes are grad-mode copies, not the buffers
         self.tour = torch.zeros(B, N, dtype=torch.int64, device=dev)
         self.picked = torch.zeros(B, N, dtype=torch.int32, device=dev)
         buf = _lib.RollerBuffers()
         for w in range(2):
             buf.static_[w], buf.nodes[w] = self._static[w].data_ptr(), self._nodes[w].data_ptr()
-        buf.dynamic = self.dynamic.data_ptr() if self.dynamic is not None else None
+        buf.dynamic = self._dynamic.data_ptr() if self._dynamic is not None else None
         buf.bits = self.bits.data_ptr() if self.bits is not None else None
         buf.colsum = self.colsum.data_ptr() if self.colsum is not None else None
-        buf.current_mask = self.current_mask.data_ptr() if self.current_mask is not None else None
+        buf.current_mask = self._current_mask.data_ptr() if self._current_mask is not None else None
         buf.err, buf.feature = self._err.data_ptr(), self.decoder_dynamic.data_ptr()
         buf.decoder_static, buf.tour, buf.picked = self.decoder_static.data_ptr(), self.tour.data_ptr(), self.picked.data_ptr()
         buf.tour_stride = N
@@ -237,6 +243,26 @@ class RollingStepper(object):
         if h:
             self._destroy(h)
 
+    def _split_dec(self, flat):
+        cut, fshape, sshape = self._dec_split
+        return flat[:cut].view(fshape), flat[cut:].view(sshape)
+
+    def _hand_out(self, w):
+        """the current window's attributes after a launch wrote phase ``w``: the buffers under no_grad, private copies of
+        them while grad is enabled (see the class docstring)"""
+        self.nodes = self._nodes[w]
+        if torch.is_grad_enabled():
+            self.static, self.dynamic, self.current_mask, dec = grad_copies(self._static[w], self._dynamic,
+                                                                            self._current_mask, self._dec)
+            self.decoder_dynamic, self.decoder_static = self._split_dec(dec)
+            self._private = True
+            return
+        self.static = self._static[w]
+        if self._private:
+            self.dynamic, self.current_mask = self._dynamic, self._current_mask
+            self.decoder_dynamic, self.decoder_static = self._dec_views
+            self._private = False
+
     def begin(self, windows=None):
         """First window of ``windows`` (default: the RollingWindows given at construction; any freshly initialised
         one of the same shape) -- its ``state`` is consumed by the episode."""
@@ -253,7 +279,7 @@ class RollingStepper(object):
         rw._err = self._err
         self._dec.zero_()
         self.k = 0
-        self.static, self.nodes = self._static[0], self._nodes[0]
+        self._hand_out(0)
         return self
 
     def step(self, ptr):
@@ -269,7 +295,7 @@ class RollingStepper(object):
         self.k += 1
         self.windows.steps_done += 1
         w = self.k & 1
-        self.static, self.nodes = self._static[w], self._nodes[w]
+        self._hand_out(w)
         return w
 
     def is_last_graph(self):
@@ -381,7 +407,7 @@ def _run_rolling_steppers(rw, policy, container_width, container_height, reward_
         env = roll.env
         # the pair's buffers fix whether the fp32 tensors exist: a call that asks for the other mode would hand the
         # policy a tensor it did not ask for (or None where it expects one)
-        pair_expands = roll.dynamic is not None
+        pair_expands = roll._dynamic is not None
         if pair_expands != bool(expand_dynamic) or bool(last.expand_dynamic) != bool(expand_dynamic):
             raise ValueError("steppers were built with expand_dynamic=%s, this call asks for expand_dynamic=%s: "
                              "build a new pair (steppers=None) for the other mode" % (pair_expands, bool(expand_dynamic)))
@@ -403,7 +429,7 @@ def _run_rolling_steppers(rw, policy, container_width, container_height, reward_
     else:                                                        # two-word shadow: step 0 builds it from the tensor
         last.begin(roll.static, roll.dynamic, initial_mask=False, keep_container=True, current_mask=roll.current_mask)
         last.mask = roll._ones
-    last._dec.copy_(roll._dec)                                   # the decoder inputs go on from the last rolling step
+    last.load_decoder_inputs(roll._dec)                          # the decoder inputs go on from the last rolling step
     static_last = roll.static
     for t in range(child):
         ptr = policy(step=step, static=static_last, dynamic=last.dynamic, current_mask=last.current_mask,

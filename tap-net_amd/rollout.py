@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from .env import BatchedContainer
-from .pack import EnvTransition, EpisodeStepper, MaskStepper, NonBinaryDynamic, bits_supported
+from .pack import EnvTransition, EpisodeStepper, MaskStepper, NonBinaryDynamic, bits_supported, grad_copies
 
 
 class TapePolicy(object):
@@ -178,7 +178,8 @@ def pointer_pick(logits, mask, u=None, want_probs=False):
     Tensors of another dtype, layout or device are converted as ``BatchedContainer.trial_scores`` converts its inputs
     (half / bf16 logits through ``.float()``, so autograd sees the cast).  With grad enabled and
     ``logits.requires_grad``, ``logp`` carries its gradient to ``logits`` through one backward launch
-    (g * (onehot(ptr) - probs), zeros on rows whose logp is NaN); ``ptr`` and ``probs`` are not differentiable."""
+    (-g * probs off the pick, the picked column minus the sum of the others so that a row sums to zero, zeros on rows whose
+    logp is NaN); ``ptr`` and ``probs`` are not differentiable."""
     if logits.dim() != 2 or int(logits.shape[1]) < 1:
         raise ValueError("logits must be (B, nR) with nR >= 1, got %s" % (tuple(logits.shape),))
     dev = _lib.resolve_device(logits.device)
@@ -614,8 +615,9 @@ def _run_episode_pack(static, dynamic, policy, pack_policy, container_width, con
     masks = MaskStepper(static.to(dev), dynamic.to(dev), input_type, allow_rot, bits)
     static_part = masks.static[:, 1:, :]
     W = env.desc.W
-    # two buffers for the pack policy's input, alternating: the one a policy was handed is never overwritten by the
-    # step that follows it (a recorded episode keeps every step's input)
+    # two buffers for the pack policy's input, alternating: the one a policy was handed is not overwritten by the step
+    # that follows it, but by the one after that -- while grad is enabled the pack policy gets a private copy
+    # (pack.grad_copies), so a network that saves its input for backward() keeps this step's height-map
     pnet = [torch.zeros(B, 1, W, dtype=torch.float32, device=dev) for _ in range(2)]
     decoder_static = torch.zeros(B, D, 1, device=dev)
     decoder_dynamic = torch.zeros(env._feature_shape(), device=dev)
@@ -626,6 +628,8 @@ def _run_episode_pack(static, dynamic, policy, pack_policy, container_width, con
         masks.step(ptr)                                                                     # model.py:1118-1128
         decoder_static = torch.gather(static_part, 2, ptr.view(-1, 1, 1).expand(-1, D, 1))  # model.py:1164-1167
         pin, pout = pnet[step % 2], pnet[(step + 1) % 2]
+        if torch.is_grad_enabled():
+            pin, = grad_copies(pin)
         out = pack_policy(pin, decoder_static.transpose(2, 1))
         if out.dim() == 2:                                                                  # probabilities, model.py:1200-1202
             best = out.max(1)

@@ -179,6 +179,10 @@ def test_backward_against_torch_autograd(nR):
             want[live] = ref.grad.numpy()
             assert (np.abs(got - want) <= 2.0 ** -22 * np.abs(g)[:, None]).all(), np.abs(got - want).max()
             assert (got[mask == 0] == 0).all() and (got[~live] == 0).all()
+            # a row sums to zero within the ONE rounding of its picked column, as the true gradient does: that column is
+            # minus the fp64 sum of the others (whose own error, <= nR additions of 2^-53, is far below)
+            picked = np.abs(got[np.arange(B), ptr].astype(np.float64))
+            assert (np.abs(got.astype(np.float64).sum(1)) <= 2.0 ** -24 * picked + 2.0 ** -45 * np.abs(g)).all()
     # the forward is the same without grad; half logits come back as a half gradient (autograd handles the cast)
     with torch.no_grad():
         assert not T.pointer_pick(x, torch.from_numpy(mask).to(DEV))[1].requires_grad
