@@ -104,7 +104,7 @@ const char *tap_last_error(const tap_ctx *ctx);
  * hipGraph counts once, at capture.  tap_variant_hits writes up to `cap` rows of 8 ints (the key, then the count) and
  * returns the number of rows the record holds (TAP_E_INVALID if a key found no slot since the last reset);
  * tap_variant_hits_reset empties it. */
-/* The whole-episode and rolling kernels count on the same record, under kinds 16 .. 28 (tap_common.h: TapHitKind; 25: trial.hip, 26: policy.hip, 27: encode.hip, 28: pointer.hip), after
+/* The whole-episode and rolling kernels count on the same record, under kinds 16 .. 29 (tap_common.h: TapHitKind; 25: trial.hip, 26: policy.hip, 27: encode.hip, 28: pointer.hip, 29: decoder.hip), after
  * the stream-wave kinds 0 .. 6.  Their keys, fields (kind, D, G, nc, mode, extra, wt):
  *   16 k_episode<D, G, SOFT>                      (16, D, G, SOFT, 0, 0, 0)
  *   17 k_episode_macs2<G, WIDE>                   (17, 2, G, WIDE, 0, 0, 0)
@@ -126,6 +126,8 @@ const char *tap_last_error(const tap_ctx *ctx);
  *      k_encode_bits_bw_partial + _reduce         (27, 0, 0, PLANES, BIAS, 1, 0) BIAS 1 = dbias wanted (one count per call)
  *   28 k_pointer_scores<HPL>                      (28, 0, HPL, PLANES, CHUNKS, 0, 0) CHUNKS = Hd / (64 HPL) hidden chunks per segment
  *      k_pointer_scores_bw<HPL> + _bw_reduce      (28, 0, HPL, PLANES, CHUNKS, 1, 0) (one count per call)
+ *   29 k_decoder_step                             (29, 0, TE, CHUNKS, H, 0, 0) TE = 16 envs per workgroup, CHUNKS = Hd / 64, H 1 = h given
+ *      k_decoder_step_bw                          (29, 0, TE, CHUNKS, H, 1, 0)
  * wt is the launch's RollArgs::wt (the window's fp32 stores; the init kernels store none), 0 for the episode kernels. */
 int tap_variant_hits(tap_ctx *ctx, int32_t *out, int cap);
 int tap_variant_hits_reset(tap_ctx *ctx);
@@ -692,6 +694,49 @@ int tap_pointer_scores_backward(tap_ctx *ctx, const float *proj, const unsigned 
                                 float *dva_out, float *dvp_out, void *scratch, size_t scratch_bytes, void *stream);
 /* bytes of scratch the backward needs for this shape (0 for a shape the entry refuses) */
 size_t tap_pointer_scores_backward_scratch(int B, int nR, int rows, int Hd);
+
+/* The decoder side of a decoding step in ONE launch (model.py:347-354 and the GRU step of 108-115, then the decoder's
+ * columns of the attention's W): from the stepper's decoder buffers and last_hh to the new hidden state and the q that
+ * tap_pointer_scores takes.  The decoder's encoders are 1x1 convolutions, so the caller folds them into the GRU's input
+ * weights once per episode (tools.Pointer.fold_decoder): P (3 Hd, K) and c (3 Hd,), K = Ks + Kd, gate order r, z, n as
+ * nn.GRU lays weight_ih_l0 out.  Per env, with xs (Ks) the chosen block's sides, xd (Kd) the container feature and h (Hd)
+ * the previous hidden state:
+ *   gi = P . [xs ; xd] + c        gh = w_hh . h + b_hh          (w_hh (3 Hd, Hd), b_hh (3 Hd,): weight_hh_l0, bias_hh_l0)
+ *   r = sigmoid(gi_r + gh_r)      z = sigmoid(gi_z + gh_z)      n = tanh(gi_n + r gh_n)
+ *   h' = (1 - z) n + z h          q = wq . h'                   (wq (Hd, Hd) = encoder_attn.W[0][:, 2 He:])
+ * fp32 throughout, sigmoid(x) = 1 / (1 + expf(-x)).  Every sum is one chain of fmaf in ascending term order: gi_g[j] starts
+ * from c[g Hd + j] and takes the K inputs, static columns first; gh_g[j] starts from b_hh[g Hd + j] and takes the Hd hidden
+ * terms; q[j] starts from 0 and takes the Hd terms of h'.  The products r gh_n, (1 - z) n and z h are rounded before they
+ * are added (no contraction).  No atomics, no cross-lane sums: two calls give the same bytes, and an env's result does not
+ * depend on the batch around it.
+ *   xs (B, Ks) and xd (B, Kd) are two buffers of their own (a stepper's flat decoder buffer holds the feature part
+ *   first, then the block part: no concatenation is needed); xs may be null iff Ks == 0, xd iff Kd == 0.  h (B, Hd), or
+ *   NULL for the zero state of step 0: gh is then exactly b_hh and w_hh is not read.  h_out, q_out (B, Hd).  gates_out
+ *   (B, 4, Hd) = r, z, n, gh_n -- what the backward reads -- or NULL: written only when given.
+ * One launch, no allocation, no host read, no stream synchronisation (capturable in a hipGraph).  k_decoder_step
+ * (decoder.hip): a workgroup per 16 consecutive envs with their h and h' rows in the LDS, a wavefront per 4 of them, a lane
+ * per hidden row and its three gates; the weights pass through the LDS in blocks of 64 hidden rows x 32 terms, the hidden
+ * chunk outermost; one barrier completes h' of the tile before q.  Launch record key (29, 0, TE, Hd / 64, H, 0, 0): TE = 16
+ * envs per workgroup, H 1 = h given.
+ * Shapes: Hd 64, 128 or 256 and 1 <= Ks + Kd <= Hd + 16; anything else -> TAP_E_UNSUPPORTED.  Checks, in
+ * tap_pointer_scores' order: B, Ks or Kd < 0 or Hd < 1 -> TAP_E_INVALID; B == 0 -> TAP_OK; a null required buffer ->
+ * TAP_E_INVALID; a shape outside the list -> TAP_E_UNSUPPORTED; a buffer that is not 4-byte aligned -> TAP_E_INVALID (every
+ * load and store of the kernel's is 4 bytes wide: xs / xd are views into the stepper's flat buffer). */
+int tap_decoder_step(tap_ctx *ctx, const float *xs, int Ks, const float *xd, int Kd, const float *h, int B, int Hd,
+                     const float *P, const float *c, const float *w_hh, const float *b_hh, const float *wq,
+                     float *h_out, float *q_out, float *gates_out, void *stream);
+
+/* The element-wise part of tap_decoder_step's backward, one launch: from gates (B, 4, Hd) as the forward wrote them, h
+ * (or NULL, as the forward had it) and g_h (B, Hd), the gradient arriving at h' (the caller has added wq^T . dq to it):
+ *   da_n = g_h (1 - z) (1 - n^2)      da_r = da_n gh_n r (1 - r)      da_z = g_h (h - n) z (1 - z)
+ *   dgi_out (B, 3 Hd) = [da_r | da_z | da_n];  dghn_out (B, Hd) = da_n r (the n gate's hidden side; the r and z parts of
+ *   dgh equal those of dgi);  dh_carry_out (B, Hd) = g_h z.
+ * The sums over the batch (dP, dc, dw_hh, db_hh, dwq) and dh = carry + dgh . w_hh are the caller's GEMMs.  Element-wise:
+ * two calls give the same bytes.  Checks: B < 0 or Hd < 1 -> TAP_E_INVALID; B == 0 -> TAP_OK; a null buffer (h excepted)
+ * -> TAP_E_INVALID; Hd not 64, 128 or 256 -> TAP_E_UNSUPPORTED; 4-byte alignment.  Launch record key (29, 0, TE, Hd / 64, H,
+ * 1, 0). */
+int tap_decoder_step_backward(tap_ctx *ctx, int B, int Hd, const float *gates, const float *h, const float *g_h,
+                              float *dgi_out, float *dghn_out, float *dh_carry_out, void *stream);
 
 /* ---- the step object of a decoding loop ----------------------------------------------------- */
 /* DRL.forward's loop (model.py:342-496) runs its policy network between the environment steps, so the loop is

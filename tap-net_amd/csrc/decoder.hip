@@ -1,0 +1,246 @@
+// decoder.hip -- the decoder side of a decoding step: the reference's decoder_static / decoder_dynamic encoders, their
+// concatenation, the GRU cell of its pointer (one layer, one step) and the decoder's part of the attention, q (model.py:
+// 347-354 and 108-115; tapenv.h: tap_decoder_step has the contract).  The encoders are 1x1 convolutions, so they fold into
+// the GRU's input weights: gi = P . [xs ; xd] + c with K = Ks + Kd raw decoder values per env instead of Hd encoded ones.
+// One launch goes from the stepper's two decoder buffers and last_hh to the new hidden state and q.
+//
+// Geometry.  Every product here is (a few hundred weight rows) x (a tile of envs), and the weights do not fit the LDS
+// whole (W_hh is 196 KB at Hd = 128), so a workgroup takes DEC_TE = 4 DEC_E consecutive envs, keeps their h rows and
+// their h' rows in the LDS for the whole launch, and streams the weights through the LDS in blocks of (64 hidden rows x
+// their gates) x (DEC_KC = 32 terms): the hidden chunk is the OUTER loop, the term chunk the inner one, and the sums stay
+// in registers across the term chunks.  A lane owns one hidden row j of the chunk and all three of its gates -- rows j,
+// Hd + j, 2 Hd + j of the weights --, so the gate arithmetic needs no exchange; a wavefront owns DEC_E envs of the tile.
+// Per four terms a lane reads one 16-byte piece per gate from the weight block (row stride DEC_WS = 36 floats: the 16
+// lanes of a ds_read_b128 group fall on 16 different 4-bank slots) and one 16-byte piece per env from the activation
+// tile (one address for the whole wavefront: a broadcast), and issues 12 DEC_E fused multiply-adds.  The input product
+// runs the same code on a block of P and a (DEC_TE x DEC_KC) tile of [xs ; xd], zero-padded to a multiple of four terms;
+// q runs it with one row per lane on Wq and the h' tile, after the barrier that completes h' of the tile.
+//
+// Every sum is ONE chain of fmaf in ascending term order: gi_g[j] from c[g Hd + j] over the K inputs (static columns
+// first), gh_g[j] from b_hh[g Hd + j] over the Hd hidden terms, q[j] from 0 over the Hd terms of h'.  No atomics, no
+// cross-lane sums, nothing depends on the batch or the tile: two calls give the same bytes, and an env's result does not
+// depend on which other envs share its launch.
+//
+// Backward: element-wise only (k_decoder_step_bw), from the saved gates; the sums over the batch are the caller's GEMMs.
+#include "tap_common.h"
+
+namespace {
+
+constexpr int TAP_HIT_DECODER = 29;         // launch record (tapenv.h: tap_variant_hits), after pointer.hip's 28
+constexpr int DEC_E = 4;                    // envs per wavefront
+constexpr int DEC_TE = (TAP_BLOCK / 64) * DEC_E;   // envs per workgroup
+constexpr int DEC_KC = 32;                  // terms per weight block
+constexpr int DEC_WS = DEC_KC + 4;          // row stride of the weight block in the LDS, floats
+constexpr int DEC_WROWS = 3 * 64;           // rows of the largest weight block: 64 hidden rows x 3 gates
+static_assert((64 * DEC_KC) % TAP_BLOCK == 0 && (DEC_TE * DEC_KC) % TAP_BLOCK == 0, "the fills' trip counts are fixed");
+
+struct DecArgs {
+    const float *xs, *xd, *h;               // (B, Ks), (B, Kd), (B, Hd) or null
+    const float *P, *c, *w_hh, *b_hh, *wq;  // (3 Hd, K), (3 Hd,), (3 Hd, Hd), (3 Hd,), (Hd, Hd)
+    float *h_out, *q_out, *gates_out;       // (B, Hd), (B, Hd), (B, 4, Hd) or null
+    int B, Hd, Ks, Kd;
+};
+
+inline size_t dec_lds_bytes(int Hd)
+{
+    return ((size_t)DEC_WROWS * DEC_WS + (size_t)DEC_TE * DEC_KC + 2 * (size_t)DEC_TE * Hd) * sizeof(float);   // 61 KB at Hd = 256
+}
+
+// rows [g * gstride + row0 + (0 .. 63)] for g < NG, terms [k0, k0 + kn) of a row-major matrix of row length ld ->
+// lw[(g * 64 + r) * DEC_WS + k], zeros up to DEC_KC.  Global reads along the rows, LDS writes of a 32-lane half on 32
+// consecutive banks.  The caller's barriers stand before (the previous block has been consumed) and after.
+template <int NG>
+__device__ __forceinline__ void dec_fill_weights(float *lw, const float *W, int ld, int gstride, int row0, int k0, int kn, int tid)
+{
+    constexpr int N = NG * 64 * DEC_KC / TAP_BLOCK;                        // a fixed trip count: the loads of a block are all
+    float v[N];                                                            // issued before the first LDS write waits for one
+#pragma unroll
+    for (int it = 0; it < N; ++it) {
+        const int i = it * TAP_BLOCK + tid, r = i / DEC_KC, k = i - r * DEC_KC;
+        const int row = (r >> 6) * gstride + row0 + (r & 63);
+        v[it] = k < kn ? W[(unsigned)(row * ld + k0 + k)] : 0.f;              // (a weight matrix has at most 3 * 256 * 272 elements)
+    }
+#pragma unroll
+    for (int it = 0; it < N; ++it) {
+        const int i = it * TAP_BLOCK + tid, r = i / DEC_KC, k = i - r * DEC_KC;
+        lw[r * DEC_WS + k] = v[it];
+    }
+}
+
+// acc[g][e] = fmaf(w[g][k], act[e][k], acc[g][e]) over 4 * k4n terms in ascending order
+template <int NG>
+__device__ __forceinline__ void dec_mac(const float *lw, const float *act, int astride, int k4n, int lane, float (&acc)[NG][DEC_E])
+{
+    for (int k4 = 0; k4 < k4n; ++k4) {
+        float4 w[NG];
+#pragma unroll
+        for (int g = 0; g < NG; ++g) w[g] = *reinterpret_cast<const float4 *>(lw + (g * 64 + lane) * DEC_WS + 4 * k4);
+#pragma unroll
+        for (int e = 0; e < DEC_E; ++e) {
+            const float4 x = *reinterpret_cast<const float4 *>(act + e * astride + 4 * k4);
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+                float s = acc[g][e];
+                s = fmaf(w[g].x, x.x, s);
+                s = fmaf(w[g].y, x.y, s);
+                s = fmaf(w[g].z, x.z, s);
+                s = fmaf(w[g].w, x.w, s);
+                acc[g][e] = s;
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ float dec_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
+
+__global__ void __launch_bounds__(TAP_BLOCK) k_decoder_step(DecArgs a)
+{
+    extern __shared__ float4 dec_lds4[];                                   // (float4: the 16-byte reads need the base aligned)
+    float *lw = reinterpret_cast<float *>(dec_lds4), *xa = lw + DEC_WROWS * DEC_WS, *hl = xa + DEC_TE * DEC_KC;
+    const int tid = threadIdx.x, lane = tid & 63, wave = TAP_WAVE_INDEX();
+    const int B = a.B, Hd = a.Hd, Ks = a.Ks, K = a.Ks + a.Kd;
+    float *hn = hl + DEC_TE * Hd;
+    const int e0 = (int)blockIdx.x * DEC_TE, ew = wave * DEC_E;            // the tile's first env; the wavefront's first env in the tile
+    const bool have_h = a.h != nullptr;
+
+    // the tile's h rows (zeros for a null h and for the envs past the batch); the first block's barriers publish them
+#pragma unroll 4
+    for (int i = tid; i < DEC_TE * Hd; i += TAP_BLOCK) {
+        const int e = i / Hd, k = i - e * Hd;
+        hl[i] = (have_h && e0 + e < B) ? a.h[(size_t)(e0 + e) * Hd + k] : 0.f;
+    }
+    for (int jc = 0; jc < Hd / 64; ++jc) {
+        const int j = jc * 64 + lane;
+        float gi[3][DEC_E], gh[3][DEC_E];
+#pragma unroll
+        for (int g = 0; g < 3; ++g) {
+            const float ci = a.c[g * Hd + j], bi = a.b_hh[g * Hd + j];
+#pragma unroll
+            for (int e = 0; e < DEC_E; ++e) { gi[g][e] = ci; gh[g][e] = bi; }
+        }
+        // gi += P . [xs ; xd]
+        for (int k0 = 0; k0 < K; k0 += DEC_KC) {
+            const int kn = min(DEC_KC, K - k0);
+            __syncthreads();
+            dec_fill_weights<3>(lw, a.P, K, Hd, jc * 64, k0, kn, tid);
+#pragma unroll
+            for (int it = 0; it < DEC_TE * DEC_KC / TAP_BLOCK; ++it) {
+                const int i = it * TAP_BLOCK + tid, e = i / DEC_KC, kk = k0 + (i - e * DEC_KC), b = e0 + e;
+                float v = 0.f;
+                if (b < B && kk < K) v = kk < Ks ? a.xs[(size_t)b * Ks + kk] : a.xd[(size_t)b * a.Kd + (kk - Ks)];
+                xa[i] = v;
+            }
+            __syncthreads();
+            dec_mac<3>(lw, xa + ew * DEC_KC, DEC_KC, (kn + 3) >> 2, lane, gi);
+        }
+        // gh += W_hh . h (a null h is the zero state: gh stays b_hh)
+        if (have_h)
+            for (int k0 = 0; k0 < Hd; k0 += DEC_KC) {
+                __syncthreads();
+                dec_fill_weights<3>(lw, a.w_hh, Hd, Hd, jc * 64, k0, DEC_KC, tid);
+                __syncthreads();
+                dec_mac<3>(lw, hl + ew * Hd + k0, Hd, DEC_KC / 4, lane, gh);
+            }
+#pragma unroll
+        for (int e = 0; e < DEC_E; ++e) {
+            const int b = e0 + ew + e;
+            const float r = dec_sigmoid(gi[0][e] + gh[0][e]), z = dec_sigmoid(gi[1][e] + gh[1][e]);
+            const float n = tanhf(gi[2][e] + r * gh[2][e]);
+            const float hv = (1.f - z) * n + z * hl[(ew + e) * Hd + j];
+            hn[(ew + e) * Hd + j] = hv;
+            if (b < B) {
+                a.h_out[(size_t)b * Hd + j] = hv;
+                if (a.gates_out) {
+                    float *go = a.gates_out + (size_t)b * 4 * Hd + j;
+                    go[0] = r;
+                    go[Hd] = z;
+                    go[2 * Hd] = n;
+                    go[3 * Hd] = gh[2][e];
+                }
+            }
+        }
+    }
+    // q = Wq . h': the first block's barrier completes h' of the tile
+    for (int jc = 0; jc < Hd / 64; ++jc) {
+        const int j = jc * 64 + lane;
+        float acc[1][DEC_E];
+#pragma unroll
+        for (int e = 0; e < DEC_E; ++e) acc[0][e] = 0.f;
+        for (int k0 = 0; k0 < Hd; k0 += DEC_KC) {
+            __syncthreads();
+            dec_fill_weights<1>(lw, a.wq, Hd, 0, jc * 64, k0, DEC_KC, tid);
+            __syncthreads();
+            dec_mac<1>(lw, hn + ew * Hd + k0, Hd, DEC_KC / 4, lane, acc);
+        }
+#pragma unroll
+        for (int e = 0; e < DEC_E; ++e)
+            if (e0 + ew + e < B) a.q_out[(size_t)(e0 + ew + e) * Hd + j] = acc[0][e];
+    }
+}
+
+// from h' = (1 - z) n + z h, n = tanh(gi_n + r gh_n), r / z = sigmoid(gi + gh): per element
+//   carry = g z;  da_n = g (1 - z) (1 - n^2);  dgh_n = da_n r;  da_r = da_n gh_n r (1 - r);  da_z = g (h - n) z (1 - z)
+__global__ void __launch_bounds__(TAP_BLOCK) k_decoder_step_bw(const float *gates, const float *h, const float *g_h, float *dgi, float *dghn,
+                                                               float *carry, size_t total, int Hd)
+{
+    const size_t i = (size_t)blockIdx.x * TAP_BLOCK + threadIdx.x;
+    if (i >= total) return;
+    const size_t b = i / (size_t)Hd;
+    const int j = (int)(i - b * (size_t)Hd);
+    const float *gp = gates + b * 4 * (size_t)Hd + j;
+    const float r = gp[0], z = gp[Hd], n = gp[2 * Hd], ghn = gp[3 * Hd];
+    const float g = g_h[i], hp = h ? h[i] : 0.f;
+    const float dan = g * (1.f - z) * (1.f - n * n);
+    float *dp = dgi + b * 3 * (size_t)Hd + j;
+    dp[0] = dan * ghn * (r * (1.f - r));
+    dp[Hd] = g * (hp - n) * (z * (1.f - z));
+    dp[2 * Hd] = dan;
+    dghn[i] = dan * r;
+    carry[i] = g * z;
+}
+
+inline bool dec_hd_ok(int Hd) { return Hd == 64 || Hd == 128 || Hd == 256; }
+inline bool dec_misaligned(const void *p) { return ((uintptr_t)p & 3) != 0; }
+
+} // namespace
+
+extern "C" int tap_decoder_step(tap_ctx *ctx, const float *xs, int Ks, const float *xd, int Kd, const float *h, int B, int Hd,
+                                const float *P, const float *c, const float *w_hh, const float *b_hh, const float *wq, float *h_out,
+                                float *q_out, float *gates_out, void *stream)
+{
+    if (B < 0 || Ks < 0 || Kd < 0 || Hd < 1) return tap_fail(ctx, TAP_E_INVALID, "decoder step: B %d, Ks %d, Kd %d, Hd %d", B, Ks, Kd, Hd);
+    if (B == 0) return TAP_OK; // an empty batch has no buffers to check
+    if ((Ks > 0 && !xs) || (Kd > 0 && !xd) || !P || !c || !w_hh || !b_hh || !wq || !h_out || !q_out)
+        return tap_fail(ctx, TAP_E_INVALID, "decoder step: null buffer");
+    if (!dec_hd_ok(Hd) || Ks + Kd < 1 || Ks + Kd > Hd + 16)
+        return tap_fail(ctx, TAP_E_UNSUPPORTED, "decoder step: Ks %d, Kd %d, Hd %d (needs Hd 64, 128 or 256 and 1 <= Ks + Kd <= Hd + 16)", Ks, Kd, Hd);
+    const void *f32[] = {xs, xd, h, P, c, w_hh, b_hh, wq, h_out, q_out, gates_out};
+    bool bad = false;
+    for (const void *p : f32) bad = bad || dec_misaligned(p);
+    if (bad) return tap_fail(ctx, TAP_E_INVALID, "decoder step: every buffer must be 4-byte aligned");
+    const DecArgs a = {xs, xd, h, P, c, w_hh, b_hh, wq, h_out, q_out, gates_out, B, Hd, Ks, Kd};
+    const unsigned blocks = (unsigned)((B + DEC_TE - 1) / DEC_TE);
+    hipLaunchKernelGGL(k_decoder_step, dim3(blocks), dim3(TAP_BLOCK), dec_lds_bytes(Hd), (hipStream_t)stream, a);
+    TAP_LAUNCH_CHECK(ctx, "k_decoder_step");
+    tap_variant_hit(ctx, TAP_HIT_DECODER, 0, DEC_TE, TapVariant{Hd / 64, h ? 1 : 0, 0}, 0);
+    return TAP_OK;
+}
+
+extern "C" int tap_decoder_step_backward(tap_ctx *ctx, int B, int Hd, const float *gates, const float *h, const float *g_h, float *dgi_out,
+                                         float *dghn_out, float *dh_carry_out, void *stream)
+{
+    if (B < 0 || Hd < 1) return tap_fail(ctx, TAP_E_INVALID, "decoder step backward: B %d, Hd %d", B, Hd);
+    if (B == 0) return TAP_OK; // (an empty batch leaves the outputs as they are)
+    if (!gates || !g_h || !dgi_out || !dghn_out || !dh_carry_out) return tap_fail(ctx, TAP_E_INVALID, "decoder step backward: null buffer");
+    if (!dec_hd_ok(Hd)) return tap_fail(ctx, TAP_E_UNSUPPORTED, "decoder step backward: Hd %d (needs 64, 128 or 256)", Hd);
+    const void *f32[] = {gates, h, g_h, dgi_out, dghn_out, dh_carry_out};
+    bool bad = false;
+    for (const void *p : f32) bad = bad || dec_misaligned(p);
+    if (bad) return tap_fail(ctx, TAP_E_INVALID, "decoder step backward: every buffer must be 4-byte aligned");
+    const size_t total = (size_t)B * Hd;
+    hipLaunchKernelGGL(k_decoder_step_bw, dim3((unsigned)((total + TAP_BLOCK - 1) / TAP_BLOCK)), dim3(TAP_BLOCK), 0, (hipStream_t)stream, gates, h,
+                       g_h, dgi_out, dghn_out, dh_carry_out, total, Hd);
+    TAP_LAUNCH_CHECK(ctx, "k_decoder_step_bw");
+    tap_variant_hit(ctx, TAP_HIT_DECODER, 0, DEC_TE, TapVariant{Hd / 64, h ? 1 : 0, 1}, 0);
+    return TAP_OK;
+}

@@ -424,6 +424,132 @@ def pointer_scores(proj, bits, M, k, q, va, vp, rows=None):
     return logits
 
 
+def decoder_step_supported(Ks, Kd, Hd):
+    """whether tap_decoder_step has a kernel for this shape: Hd 64, 128 or 256 and 1 <= Ks + Kd <= Hd + 16"""
+    Ks, Kd, Hd = int(Ks), int(Kd), int(Hd)
+    return Hd in (64, 128, 256) and Ks >= 0 and Kd >= 0 and 1 <= Ks + Kd <= Hd + 16
+
+
+def _decoder_into(xs, xd, h, P, c, w_hh, b_hh, wq, h_out, q_out, gates):
+    """tap_decoder_step on prepared buffers (xs / xd (B, Ks) / (B, Kd) or None, h (B, Hd) or None, gates (B, 4, Hd) or
+    None): one launch on the current stream, nothing allocated"""
+    dev = P.device
+    c_ = _lib.ctx(dev)
+    B, Hd = int(h_out.shape[0]), int(h_out.shape[1])
+    Ks = 0 if xs is None else int(xs.shape[1])
+    Kd = 0 if xd is None else int(xd.shape[1])
+    _lib.check(_lib.lib().tap_decoder_step(c_, _lib.ptr(xs), Ks, _lib.ptr(xd), Kd, _lib.ptr(h), B, Hd, _lib.ptr(P), _lib.ptr(c),
+                                           _lib.ptr(w_hh), _lib.ptr(b_hh), _lib.ptr(wq), _lib.ptr(h_out), _lib.ptr(q_out),
+                                           _lib.ptr(gates), _lib.stream_of(dev)), c_)
+
+
+def _decoder_backward_into(gates, h, g, dgi, dghn, carry):
+    """tap_decoder_step_backward on prepared buffers: one launch on the current stream, nothing allocated"""
+    dev = gates.device
+    c_ = _lib.ctx(dev)
+    B, Hd = int(g.shape[0]), int(g.shape[1])
+    _lib.check(_lib.lib().tap_decoder_step_backward(c_, B, Hd, _lib.ptr(gates), _lib.ptr(h), _lib.ptr(g), _lib.ptr(dgi),
+                                                    _lib.ptr(dghn), _lib.ptr(carry), _lib.stream_of(dev)), c_)
+
+
+class _DecoderStep(torch.autograd.Function):
+    """decoder_step under autograd: forward = the one launch with the gates kept, backward = tap_decoder_step_backward
+    (element-wise) and the sums over the batch as matmuls.  What a step keeps: xs, xd and h BY REFERENCE (a stepper hands
+    out private copies of its decoder buffers while grad is enabled, and h is the previous step's own output), h', and
+    gates (B, 4, Hd) = r, z, n, gh_n; the parameters by reference."""
+
+    @staticmethod
+    def forward(ctx, xs, xd, h, P, c, w_hh, b_hh, wq):
+        B = int((xs if xs is not None else xd).shape[0])
+        Hd, dev = int(wq.shape[0]), P.device
+        h_new = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+        q = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+        gates = torch.empty(B, 4, Hd, dtype=torch.float32, device=dev)
+        _decoder_into(xs, xd, h, P, c, w_hh, b_hh, wq, h_new, q, gates)
+        ctx.save_for_backward(xs, xd, h, h_new, gates, P, w_hh, wq)
+        return h_new, q
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_h, g_q):
+        xs, xd, h, h_new, gates, P, w_hh, wq = ctx.saved_tensors
+        B, Hd = (int(v) for v in h_new.shape)
+        dev = h_new.device
+        need = ctx.needs_input_grad
+        g_q = _as_f32(g_q, dev)
+        g = _as_f32(g_h, dev) + g_q.matmul(wq)                     # q = h' . wq^T: wq^T . dq joins the gradient arriving at h'
+        dgi = torch.empty(B, 3 * Hd, dtype=torch.float32, device=dev)
+        dghn = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+        carry = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+        _decoder_backward_into(gates, h, g, dgi, dghn, carry)
+        dgh = torch.cat((dgi[:, :2 * Hd], dghn), dim=1)            # the r and z parts of dgh are those of dgi
+        Ks = 0 if xs is None else int(xs.shape[1])
+        x = xd if xs is None else xs if xd is None else torch.cat((xs, xd), dim=1)
+        dxs = dgi.matmul(P[:, :Ks]) if xs is not None and need[0] else None
+        dxd = dgi.matmul(P[:, Ks:]) if xd is not None and need[1] else None
+        dh = carry + dgh.matmul(w_hh) if h is not None and need[2] else None
+        dP = dgi.t().matmul(x) if need[3] else None
+        dc = dgi.sum(0) if need[4] else None
+        dw_hh = (torch.zeros_like(w_hh) if h is None else dgh.t().matmul(h)) if need[5] else None
+        db_hh = dgh.sum(0) if need[6] else None
+        dwq = g_q.t().matmul(h_new) if need[7] else None
+        return dxs, dxd, dh, dP, dc, dw_hh, db_hh, dwq
+
+
+def decoder_step(xs, xd, h, P, c, w_hh, b_hh, wq):
+    """The decoder side of a decoding step (tapenv.h: tap_decoder_step; model.py:347-354, the GRU step of 108-115 and the
+    decoder's columns of the attention) in ONE launch -> (h_new (B, Hd), q (B, Hd)) float32: the decoder's 1x1 encoders
+    folded into the GRU's input weights (``P`` (3 Hd, Ks + Kd), ``c`` (3 Hd,): ``tools.Pointer.fold_decoder``), the GRU cell
+    (``w_hh`` (3 Hd, Hd), ``b_hh`` (3 Hd,): weight_hh_l0 / bias_hh_l0, gates r, z, n) and q = wq . h' (``wq`` (Hd, Hd)), what
+    ``pointer_scores`` takes.  ``xs`` (B, Ks[, 1]) the chosen block's sides and ``xd`` (B, ...) the container feature, flattened
+    to (B, Kd) -- a stepper's ``decoder_static`` / ``decoder_dynamic``, read as two buffers: no concatenation --; either may be
+    None (a single encoder).  ``h`` (B, Hd) the previous hidden state, or None for the zero state of step 0.  fp32, every sum
+    one chain of fmaf in ascending term order (static columns first): the same bytes on every call.  Floating inputs of
+    another dtype, layout or device are converted through ``.float()`` (autograd sees the cast).  With grad enabled and any
+    input requiring grad the call runs through a ``torch.autograd.Function``: the backward is one element-wise launch
+    (tap_decoder_step_backward) and torch matmuls for the sums over the batch; per step it keeps ``gates`` (B, 4, Hd) and
+    h', and ``xs`` / ``xd`` / ``h`` by reference, so the caller must not overwrite them before ``backward()`` (a stepper's
+    grad-mode attributes are private copies).  A shape without a kernel (``decoder_step_supported``) raises ValueError."""
+    if P.dim() != 2 or int(P.shape[0]) % 3 or not P.is_floating_point():
+        raise ValueError("P must be a floating (3 Hd, Ks + Kd) tensor, got %s %s" % (P.dtype, tuple(P.shape)))
+    Hd = int(P.shape[0]) // 3
+    if xs is None and xd is None:
+        raise ValueError("decoder_step needs xs, xd or both")
+    B = int((xs if xs is not None else xd).shape[0])
+    for name, v in (("xs", xs), ("xd", xd)):
+        if v is not None and (v.dim() < 2 or int(v.shape[0]) != B or not v.is_floating_point()):
+            raise ValueError("%s must be a floating (%d, ...) tensor, got %s %s" % (name, B, v.dtype, tuple(v.shape)))
+    xs = None if xs is None else xs.reshape(B, -1)
+    xd = None if xd is None else xd.reshape(B, -1)
+    Ks, Kd = (0 if v is None else int(v.shape[1]) for v in (xs, xd))
+    xs, xd = (None if v is None or int(v.shape[1]) == 0 else v for v in (xs, xd))
+    if Ks + Kd != int(P.shape[1]):
+        raise ValueError("P has %d columns, xs and xd have %d + %d values per env" % (int(P.shape[1]), Ks, Kd))
+    for name, v, shape in (("c", c, (3 * Hd,)), ("w_hh", w_hh, (3 * Hd, Hd)), ("b_hh", b_hh, (3 * Hd,)), ("wq", wq, (Hd, Hd))) + \
+            ((("h", h, (B, Hd)),) if h is not None else ()):
+        if tuple(v.shape) != shape or not v.is_floating_point():
+            raise ValueError("%s must be a floating %s tensor, got %s %s" % (name, shape, v.dtype, tuple(v.shape)))
+    if not decoder_step_supported(Ks, Kd, Hd):
+        raise ValueError("no decoder-step kernel for Ks %d, Kd %d, Hd %d (Hd 64 / 128 / 256, 1 <= Ks + Kd <= Hd + 16)" % (Ks, Kd, Hd))
+    dev = _lib.resolve_device(P.device)
+
+    def prep(t):
+        if t is None:
+            return None
+        if t.dtype is not torch.float32:
+            t = t.float()
+        if not t.is_contiguous() or t.device != dev:
+            t = t.to(dev).contiguous()
+        return t
+    args = [prep(v) for v in (xs, xd, h, P, c, w_hh, b_hh, wq)]
+    if torch.is_grad_enabled() and any(v is not None and v.requires_grad for v in args):
+        return _DecoderStep.apply(*args)
+    h_new = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+    q = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+    _decoder_into(*(None if v is None else v.detach() for v in args), h_new, q, None)
+    return h_new, q
+
+
 class PointerHeadPolicy(object):
     """A pointer network's decoding head as a policy for ``run_episode`` and the steppers (model.py:356-372):
     ``scorer(step=, static=, dynamic=, current_mask=, mask=, decoder_static=, decoder_dynamic=)`` returns the logits

@@ -130,7 +130,12 @@ class Pointer(nn.Module):
     dynamic encoder's ``conv`` folded into the two W under autograd (M, k), q from the GRU's output, then ONE launch from
     the int64 shadow ``bits`` (a stepper's ``dynamic_bits``) to the logits: no dynamic_hidden, no concatenation.  On a
     shape without a kernel ``forward_bits`` runs ``forward`` on ``dynamic_encoder(bits)`` and the static_hidden that
-    ``project_static`` was given (the returned tensor carries it as ``proj.static_hidden``)."""
+    ``project_static`` was given (the returned tensor carries it as ``proj.static_hidden``).
+
+    ``fold_decoder(...)`` -> (P, c) and ``fold_episode(dynamic_encoder, P, c)`` -> fold, once per episode, differentiable:
+    the decoder's 1x1 encoders folded into the GRU's input weights, and everything else of a step that depends on the
+    parameters alone (M, k, Wq).  ``forward_step(proj, bits, fold, decoder_static, decoder_dynamic, last_hh)`` -> (logits,
+    last_hh) is then TWO launches: ``rollout.decoder_step`` (input product, GRU cell and q) and ``rollout.pointer_scores``."""
 
     def __init__(self, encoder_hidden_size, decoder_hidden_size, decoder_input_type, input_type, num_layers=1, dropout=0.2):
         super(Pointer, self).__init__()
@@ -203,6 +208,113 @@ class Pointer(nn.Module):
         k = Wd.matmul(conv.bias) if conv.bias is not None else torch.zeros_like(Wd[:, 0])
         q = rnn_out.matmul(Wq.t())
         return pointer_scores(proj, bits, M, k, q, self.encoder_attn.v[0, 0], self.v[0, 0], rows=rows), last_hh
+
+    def fold_decoder(self, static_decoder=None, dynamic_decoder=None, combine='cat', identity_dynamic=0):
+        """-> P (3 Hd, K), c (3 Hd,): the decoder's encoders (model.py:218-221, 352-354) folded into the GRU's input weights,
+        differentiable, once per episode: gi = weight_ih_l0 . decoder_hidden + bias_ih_l0 = P . [xs ; xd] + c.  An encoder
+        is anything with a kernel-size-1 ``.conv`` (the reference's Encoder, ``DynamicBitsEncoder``) or an ``nn.Conv1d``
+        itself; either may be None.  ``combine='cat'``: decoder_hidden = cat(static(xs), dynamic(xd)), the encoders' rows
+        adding up to Hd; ``'sum'``: static(xs) + dynamic(xd), Hd rows each.  ``identity_dynamic=m`` (instead of a dynamic
+        encoder): the caller passes an already encoded dynamic half of m rows as xd -- the reference's 3D
+        HeightmapEncoder, which has leaky-ReLUs and does not fold -- and the fold takes m identity columns for it.  K =
+        the static encoder's inputs + the dynamic encoder's inputs (or m).  P carries what ``forward_step``'s fallback
+        needs (``P.static_decoder``, ``P.dynamic_decoder``, ``P.combine``, ``P.identity_dynamic``)."""
+        if combine not in ('cat', 'sum'):
+            raise ValueError("combine must be 'cat' or 'sum', not %r" % (combine,))
+        m = int(identity_dynamic)
+        if m < 0 or (m and dynamic_decoder is not None):
+            raise ValueError("identity_dynamic stands in for the dynamic encoder: pass one of them")
+        if static_decoder is None and dynamic_decoder is None and not m:
+            raise ValueError("fold_decoder needs at least one encoder")
+        Hd = self.decoder_hidden_size
+        W_ih = self.gru.weight_ih_l0
+        parts = []                                      # (weight (rows, inputs), bias (rows,)) of each half of decoder_hidden
+        for enc in (static_decoder, dynamic_decoder):
+            if enc is None:
+                continue
+            conv = getattr(enc, "conv", enc)
+            w = conv.weight
+            if w.dim() != 3 or int(w.shape[2]) != 1:
+                raise ValueError("a decoder encoder must be a kernel-size-1 convolution, got a weight of shape %s" % (tuple(w.shape),))
+            w = w[:, :, 0].to(W_ih.dtype)
+            parts.append((w, conv.bias.to(W_ih.dtype) if conv.bias is not None else torch.zeros_like(w[:, 0])))
+        if m:
+            parts.append((torch.eye(m, dtype=W_ih.dtype, device=W_ih.device), torch.zeros(m, dtype=W_ih.dtype, device=W_ih.device)))
+        widths = [int(w.shape[0]) for w, _ in parts]
+        if (sum(widths) != Hd) if combine == 'cat' else any(v != Hd for v in widths):
+            raise ValueError("the encoders give %s rows; the GRU takes %d (combine=%r)" % (widths, Hd, combine))
+        if combine == 'cat':
+            cuts = [sum(widths[:i]) for i in range(len(widths) + 1)]
+            P = torch.cat([W_ih[:, cuts[i]:cuts[i + 1]].matmul(w) for i, (w, _) in enumerate(parts)], dim=1)
+            c = W_ih.matmul(torch.cat([b for _, b in parts]))
+        else:
+            P = torch.cat([W_ih.matmul(w) for w, _ in parts], dim=1)
+            c = W_ih.matmul(sum(b for _, b in parts))
+        if self.gru.bias:
+            c = c + self.gru.bias_ih_l0
+        P.static_decoder, P.dynamic_decoder, P.combine, P.identity_dynamic = static_decoder, dynamic_decoder, combine, m
+        return P, c
+
+    def fold_episode(self, dynamic_encoder, P, c):
+        """-> the record ``forward_step`` takes, once per episode, differentiable: everything of a step that depends on the
+        parameters alone -- M, k (the dynamic encoder folded into the two W, as ``forward_bits`` folds it per step), P, c
+        (``fold_decoder``), Wq (the attention's columns for the decoder, contiguous), the two v and the GRU's four tensors."""
+        conv = dynamic_encoder.conv
+        _, Wd, Wq = self.folded_weights()
+        fold = StepFold()
+        fold.dynamic_encoder, fold.rows = dynamic_encoder, int(conv.weight.shape[1])
+        fold.M = Wd.matmul(conv.weight[:, :, 0])
+        fold.k = Wd.matmul(conv.bias) if conv.bias is not None else torch.zeros_like(Wd[:, 0])
+        fold.P, fold.c, fold.Wq = P, c, Wq.contiguous()
+        fold.va, fold.vp = self.encoder_attn.v[0, 0], self.v[0, 0]
+        fold.w_ih, fold.w_hh = self.gru.weight_ih_l0, self.gru.weight_hh_l0
+        fold.b_ih, fold.b_hh = (self.gru.bias_ih_l0, self.gru.bias_hh_l0) if self.gru.bias else (None, None)
+        fold.static_decoder, fold.dynamic_decoder = getattr(P, "static_decoder", None), getattr(P, "dynamic_decoder", None)
+        fold.combine, fold.identity_dynamic = getattr(P, "combine", None), getattr(P, "identity_dynamic", 0)
+        return fold
+
+    def _decoder_hidden(self, fold, decoder_static, decoder_dynamic):
+        """the unfolded decoder_hidden (B, Hd, 1) of model.py:352-354 from the encoders ``fold_decoder`` was given"""
+        if fold.combine is None:
+            raise ValueError("fold.P does not come from fold_decoder: the torch path needs the decoder's encoders")
+        B = int((decoder_static if decoder_static is not None else decoder_dynamic).shape[0])
+        halves = []
+        if fold.static_decoder is not None:
+            halves.append(fold.static_decoder(decoder_static.reshape(B, -1, 1)))
+        if fold.dynamic_decoder is not None:
+            halves.append(fold.dynamic_decoder(decoder_dynamic.reshape(B, -1, 1)))
+        elif fold.identity_dynamic:
+            halves.append(decoder_dynamic.reshape(B, -1, 1))
+        return torch.cat(halves, dim=1) if fold.combine == 'cat' else sum(halves)
+
+    def forward_step(self, proj, bits, fold, decoder_static, decoder_dynamic, last_hh):
+        """A decoding step in TWO launches -> (logits (B, nR), last_hh (1, B, Hd)): ``rollout.decoder_step`` from the stepper's
+        ``decoder_static`` / ``decoder_dynamic`` and ``last_hh`` (the reference's (1, B, Hd), or None for zeros) to the new
+        hidden state and q, then ``rollout.pointer_scores`` from the shadow ``bits`` to the logits.  ``proj`` from
+        ``project_static``, ``fold`` from ``fold_episode`` (both once per episode).  Either input may be None when
+        ``fold_decoder`` had no encoder for it.  The torch path -- ``_gru_step`` on the unfolded decoder_hidden, then what
+        ``forward_bits`` does: today's result -- runs instead when dropout would be active (training with p > 0), with more
+        than one GRU layer, with a GRU without bias, off the GPU, or on a shape without a kernel for either launch."""
+        from .rollout import decoder_step, decoder_step_supported, pointer_scores, pointer_scores_supported
+        Hd, nR = self.decoder_hidden_size, int(proj.shape[2])
+        Ks = 0 if decoder_static is None or fold.static_decoder is None else int(decoder_static[0].numel())
+        Kd = 0 if decoder_dynamic is None or (fold.dynamic_decoder is None and not fold.identity_dynamic) else int(decoder_dynamic[0].numel())
+        dropping = self.training and (self.drop_rnn.p > 0 or self.drop_hh.p > 0)
+        if dropping or self.num_layers != 1 or not self.gru.bias or not bits.is_cuda or Ks + Kd != int(fold.P.shape[1]) or \
+                not decoder_step_supported(Ks, Kd, Hd) or not pointer_scores_supported(fold.rows, nR, Hd):
+            decoder_hidden = self._decoder_hidden(fold, decoder_static, decoder_dynamic)
+            return self.forward_bits(proj, bits, fold.dynamic_encoder, decoder_hidden, last_hh)
+        h_new, q = decoder_step(decoder_static if Ks else None, decoder_dynamic if Kd else None,
+                                None if last_hh is None else last_hh[0], fold.P, fold.c, fold.w_hh, fold.b_hh, fold.Wq)
+        logits = pointer_scores(proj, bits, fold.M, fold.k, q, fold.va, fold.vp, rows=fold.rows)
+        return logits, h_new.unsqueeze(0)
+
+
+class StepFold(object):
+    """What ``Pointer.fold_episode`` returns: the per-episode tensors of ``Pointer.forward_step`` (M, k, P, c, Wq, va, vp, the
+    GRU's w_ih / w_hh / b_ih / b_hh) and, for the torch path, the encoders and how the decoder's two are combined."""
+    __slots__ = ("dynamic_encoder", "rows", "M", "k", "P", "c", "Wq", "va", "vp", "w_ih", "w_hh", "b_ih", "b_hh",
+                 "static_decoder", "dynamic_decoder", "combine", "identity_dynamic")
 
 
 class _EngineRow(object):
