@@ -104,7 +104,7 @@ const char *tap_last_error(const tap_ctx *ctx);
  * hipGraph counts once, at capture.  tap_variant_hits writes up to `cap` rows of 8 ints (the key, then the count) and
  * returns the number of rows the record holds (TAP_E_INVALID if a key found no slot since the last reset);
  * tap_variant_hits_reset empties it. */
-/* The whole-episode and rolling kernels count on the same record, under kinds 16 .. 29 (tap_common.h: TapHitKind; 25: trial.hip, 26: policy.hip, 27: encode.hip, 28: pointer.hip, 29: decoder.hip), after
+/* The whole-episode and rolling kernels count on the same record, under kinds 16 .. 30 (tap_common.h: TapHitKind; 25: trial.hip, 26: policy.hip, 27: encode.hip, 28: pointer.hip, 29: decoder.hip, 30: heightmap.hip), after
  * the stream-wave kinds 0 .. 6.  Their keys, fields (kind, D, G, nc, mode, extra, wt):
  *   16 k_episode<D, G, SOFT>                      (16, D, G, SOFT, 0, 0, 0)
  *   17 k_episode_macs2<G, WIDE>                   (17, 2, G, WIDE, 0, 0, 0)
@@ -128,6 +128,7 @@ const char *tap_last_error(const tap_ctx *ctx);
  *      k_pointer_scores_bw<HPL> + _bw_reduce      (28, 0, HPL, PLANES, CHUNKS, 1, 0) (one count per call)
  *   29 k_decoder_step                             (29, 0, TE, CHUNKS, H, 0, 0) TE = 16 envs per workgroup, CHUNKS = Hd / 64, H 1 = h given
  *      k_decoder_step_bw                          (29, 0, TE, CHUNKS, H, 1, 0)
+ *   30 k_decoder_step_hm                          (30, C, NP, CHUNKS, H, 0, 0)   C height-map planes, NP = ceil(W / 4) ceil(L / 4) positions read
  * wt is the launch's RollArgs::wt (the window's fp32 stores; the init kernels store none), 0 for the episode kernels. */
 int tap_variant_hits(tap_ctx *ctx, int32_t *out, int cap);
 int tap_variant_hits_reset(tap_ctx *ctx);
@@ -737,6 +738,39 @@ int tap_decoder_step(tap_ctx *ctx, const float *xs, int Ks, const float *xd, int
  * 1, 0). */
 int tap_decoder_step_backward(tap_ctx *ctx, int B, int Hd, const float *gates, const float *h, const float *g_h,
                               float *dgi_out, float *dghn_out, float *dh_carry_out, void *stream);
+
+/* tap_decoder_step with the reference's 3D dynamic_decoder in front of it, in the SAME launch: a HeightmapEncoder
+ * (model.py:21-35) has two leaky-ReLUs and does not fold into the GRU's input weights, but it is small.  conv1 and conv2 have
+ * kernel size 1 and stride 2, and conv3's kernel covers what is left of the map, so the output is 1 x 1 and only the cells
+ * (4i, 4j) of each plane are read.  With hm (B, C, W, L) the stepper's decoder_dynamic, nw = ceil(W / 4), nl = ceil(L / 4),
+ * Np = nw nl, position p = i nl + j, C1 = m / 4, C2 = m / 2 and m the encoder's hidden size, per env b:
+ *   a1[p, o] = leaky(b1[o] + sum_c  w1[o, c]  hm[b, c, 4i, 4j])      o < C1, c ascending       (w1 (C1, C), conv1.weight)
+ *   a2[p, o] = leaky(b2[o] + sum_c1 w2[o, c1] a1[p, c1])             o < C2, c1 ascending      (w2 (C2, C1), conv2.weight)
+ *   enc[o]   = b3[o] + sum_t w3[o, t] a2flat[t]                      o < m, t = c2 Np + p ascending
+ *   leaky(x) = x > 0 ? x : 0.01f x
+ * t is conv3.weight's own memory order: (m, C2, nw, nl) read as (m, C2 Np).  After that the step is tap_decoder_step's
+ * contract, word for word, with xd = enc and Kd = m: gi = P . [xs ; enc] + c with P (3 Hd, Ks + m), the GRU cell, h' and
+ * q = wq . h'; the same sum orders, the products rounded in the same places, h == NULL the zero state.  fp32 throughout; every
+ * sum of the encoder stage is one chain of fmaf in the ascending order above, starting from its bias.  No atomics, no sum
+ * depends on the batch or the tile: two calls give the same bytes, and an env's result does not depend on the envs around
+ * it.
+ *   xs (B, Ks), null iff Ks == 0.  h (B, Hd) or NULL.  h_out, q_out (B, Hd); gates_out (B, 4, Hd) = r, z, n, gh_n or NULL;
+ *   enc_out (B, m) or NULL -- what the caller's backward of the encoder starts from.  Both optional outputs are written
+ *   only when given.
+ * One launch, no allocation, no host read, no stream synchronisation (capturable in a hipGraph).  k_decoder_step_hm
+ * (heightmap.hip): tap_decoder_step's geometry -- a workgroup per 16 consecutive envs, a wavefront per 4 of them, a lane per
+ * output row, weights through the LDS in 64 row x 32 term blocks.  The encoder stage runs first on the tile and leaves a2
+ * (16 x C2 Np) and then enc (16 x m) in the LDS; the input product takes its dynamic terms from that enc tile.  Envs past B
+ * in the last tile read nothing and write nothing.  Launch record key (30, C, Np, Hd / 64, H, 0, 0), H 1 = h given.
+ * Shapes: Hd 64, 128 or 256; m = Hd / 2 or Hd; C 1, 2 or 4; 1 <= W, L <= 12 (Np <= 9); 0 <= Ks <= 16 and Ks + m <= Hd + 16;
+ * anything else -> TAP_E_UNSUPPORTED.  Checks, in tap_decoder_step's order: B or Ks < 0, or C, W, L, Hd or m < 1 ->
+ * TAP_E_INVALID; B == 0 -> TAP_OK; a null required buffer -> TAP_E_INVALID; a shape outside the list -> TAP_E_UNSUPPORTED; a
+ * buffer that is not 4-byte aligned -> TAP_E_INVALID.  The backward is tap_decoder_step_backward from gates_out plus the
+ * caller's matmuls (rollout.decoder_step_heightmap). */
+int tap_decoder_step_hm(tap_ctx *ctx, const float *xs, int Ks, const float *hm, int C, int W, int L, const float *h, int B,
+                        int Hd, int m, const float *w1, const float *b1, const float *w2, const float *b2, const float *w3,
+                        const float *b3, const float *P, const float *c, const float *w_hh, const float *b_hh,
+                        const float *wq, float *h_out, float *q_out, float *gates_out, float *enc_out, void *stream);
 
 /* ---- the step object of a decoding loop ----------------------------------------------------- */
 /* DRL.forward's loop (model.py:342-496) runs its policy network between the environment steps, so the loop is

@@ -31,6 +31,7 @@ TAP_HIT_POLICY_PICK = 26                                       # policy.hip: k_p
 TAP_HIT_ENCODE_BITS = 27                                       # encode.hip: k_encode_bits<HPL> / _bw_partial + _bw_reduce
 TAP_HIT_POINTER = 28                                           # pointer.hip: k_pointer_scores<HPL> / _bw<HPL> + _bw_reduce
 TAP_HIT_DECODER = 29                                           # decoder.hip: k_decoder_step / k_decoder_step_bw
+TAP_HIT_HEIGHTMAP = 30                                         # heightmap.hip: k_decoder_step_hm
 TAP_P_GREEDY = 1
 
 
@@ -102,6 +103,7 @@ _PROTOS = {
     "tap_pointer_scores_backward_scratch": (_sz, [_i, _i, _i, _i]),
     "tap_decoder_step": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tap_decoder_step_backward": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tap_decoder_step_hm": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _i] + [_vp] * 16),
     "tap_env_feature": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp]),
     "tap_env_ratio": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp, _vp, _vp]),
     "tap_env_export": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -550,6 +550,163 @@ def decoder_step(xs, xd, h, P, c, w_hh, b_hh, wq):
     return h_new, q
 
 
+def decoder_step_heightmap_supported(Ks, C, W, L, m, Hd):
+    """whether tap_decoder_step_hm has a kernel for this shape: Hd 64, 128 or 256, m = Hd / 2 or Hd, C 1, 2 or 4,
+    1 <= W, L <= 12, 0 <= Ks <= 16 and Ks + m <= Hd + 16"""
+    Ks, C, W, L, m, Hd = int(Ks), int(C), int(W), int(L), int(m), int(Hd)
+    return Hd in (64, 128, 256) and m in (Hd // 2, Hd) and C in (1, 2, 4) and 1 <= W <= 12 and 1 <= L <= 12 and \
+        0 <= Ks <= 16 and Ks + m <= Hd + 16
+
+
+def _decoder_hm_into(xs, hm, h, enc_w, P, c, w_hh, b_hh, wq, h_out, q_out, gates, enc_out):
+    """tap_decoder_step_hm on prepared buffers (xs (B, Ks) or None, hm (B, C, W, L), h (B, Hd) or None, enc_w = (w1, b1, w2,
+    b2, w3, b3) with w3's leading axis m, gates (B, 4, Hd) or None, enc_out (B, m) or None): one launch on the current
+    stream, nothing allocated"""
+    dev = P.device
+    c_ = _lib.ctx(dev)
+    B, Hd = int(h_out.shape[0]), int(h_out.shape[1])
+    Ks = 0 if xs is None else int(xs.shape[1])
+    C, W, L = (int(v) for v in hm.shape[1:])
+    p = _lib.ptr
+    _lib.check(_lib.lib().tap_decoder_step_hm(c_, p(xs), Ks, p(hm), C, W, L, p(h), B, Hd, int(enc_w[4].shape[0]), *(p(w) for w in enc_w),
+                                              p(P), p(c), p(w_hh), p(b_hh), p(wq), p(h_out), p(q_out), p(gates), p(enc_out),
+                                              _lib.stream_of(dev)), c_)
+
+
+def _leaky_slope(z):
+    return torch.where(z > 0, torch.ones_like(z), torch.full_like(z, 0.01))
+
+
+class _DecoderStepHeightmap(torch.autograd.Function):
+    """decoder_step_heightmap under autograd: forward = the one launch with gates and enc kept; backward = _DecoderStep's
+    (tap_decoder_step_backward and the matmuls over the batch, with xd = enc), then the encoder's six gradients and hm's from
+    d_enc by recomputing a1 / a2 in torch on the gathered cells hm[:, :, ::4, ::4].  Inputs by reference, as _DecoderStep."""
+
+    @staticmethod
+    def forward(ctx, xs, hm, h, w1, b1, w2, b2, w3, b3, P, c, w_hh, b_hh, wq):
+        B, Hd, dev = int(hm.shape[0]), int(wq.shape[0]), P.device
+        h_new = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+        q = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+        gates = torch.empty(B, 4, Hd, dtype=torch.float32, device=dev)
+        enc = torch.empty(B, int(w3.shape[0]), dtype=torch.float32, device=dev)
+        _decoder_hm_into(xs, hm, h, (w1, b1, w2, b2, w3, b3), P, c, w_hh, b_hh, wq, h_new, q, gates, enc)
+        ctx.save_for_backward(xs, hm, h, h_new, gates, enc, w1, b1, w2, b2, w3, P, w_hh, wq)
+        return h_new, q
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_h, g_q):
+        xs, hm, h, h_new, gates, enc, w1, b1, w2, b2, w3, P, w_hh, wq = ctx.saved_tensors
+        B, Hd = (int(v) for v in h_new.shape)
+        dev = h_new.device
+        need = ctx.needs_input_grad
+        g_q = _as_f32(g_q, dev)
+        g = _as_f32(g_h, dev) + g_q.matmul(wq)
+        dgi = torch.empty(B, 3 * Hd, dtype=torch.float32, device=dev)
+        dghn = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+        carry = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+        _decoder_backward_into(gates, h, g, dgi, dghn, carry)
+        dgh = torch.cat((dgi[:, :2 * Hd], dghn), dim=1)
+        Ks = 0 if xs is None else int(xs.shape[1])
+        x = enc if xs is None else torch.cat((xs, enc), dim=1)
+        dxs = dgi.matmul(P[:, :Ks]) if xs is not None and need[0] else None
+        dh = carry + dgh.matmul(w_hh) if h is not None and need[2] else None
+        dP = dgi.t().matmul(x) if need[9] else None
+        dc = dgi.sum(0) if need[10] else None
+        dw_hh = (torch.zeros_like(w_hh) if h is None else dgh.t().matmul(h)) if need[11] else None
+        db_hh = dgh.sum(0) if need[12] else None
+        dwq = g_q.t().matmul(h_new) if need[13] else None
+        dhm = dw1 = db1 = dw2 = db2 = dw3 = db3 = None
+        if need[1] or any(need[3:9]):
+            d_enc = dgi.matmul(P[:, Ks:])                             # (B, m)
+            cells = hm[:, :, ::4, ::4]                                # (B, C, nw, nl)
+            C, nw, nl = (int(v) for v in cells.shape[1:])
+            Np, C1, C2 = nw * nl, int(w1.shape[0]), int(w2.shape[0])
+            cells = cells.reshape(B, C, Np).transpose(1, 2)           # (B, Np, C)
+            z1 = cells.matmul(w1.t()) + b1
+            a1 = z1 * _leaky_slope(z1)                                # (B, Np, C1)
+            z2 = a1.matmul(w2.t()) + b2
+            a2 = z2 * _leaky_slope(z2)                                # (B, Np, C2); conv3 reads it as t = c2 Np + p
+            dw3 = d_enc.t().matmul(a2.transpose(1, 2).reshape(B, C2 * Np)) if need[7] else None
+            db3 = d_enc.sum(0) if need[8] else None
+            dz2 = d_enc.matmul(w3).view(B, C2, Np).transpose(1, 2) * _leaky_slope(z2)
+            dw2 = dz2.reshape(B * Np, C2).t().matmul(a1.reshape(B * Np, C1)) if need[5] else None
+            db2 = dz2.sum((0, 1)) if need[6] else None
+            dz1 = dz2.matmul(w2) * _leaky_slope(z1)
+            dw1 = dz1.reshape(B * Np, C1).t().matmul(cells.reshape(B * Np, C)) if need[3] else None
+            db1 = dz1.sum((0, 1)) if need[4] else None
+            if need[1]:
+                dhm = torch.zeros_like(hm)
+                dhm[:, :, ::4, ::4] = dz1.matmul(w1).transpose(1, 2).reshape(B, C, nw, nl)
+        return dxs, dhm, dh, dw1, db1, dw2, db2, dw3, db3, dP, dc, dw_hh, db_hh, dwq
+
+
+def decoder_step_heightmap(xs, hm, h, encoder, P, c, w_hh, b_hh, wq):
+    """``decoder_step`` for a 3D actor, still ONE launch (tapenv.h: tap_decoder_step_hm) -> (h_new (B, Hd), q (B, Hd)) float32:
+    the reference's ``HeightmapEncoder`` (model.py:21-35; two leaky-ReLUs, so it does not fold) runs on the tile of envs in
+    front of the input product, which takes its dynamic terms enc (B, m) from the LDS.  ``xs`` (B, Ks[, 1]) the chosen
+    block's sides, or None; ``hm`` (B, C, W, L) the stepper's ``decoder_dynamic``; ``h`` (B, Hd) or None for the zero state;
+    ``encoder`` a ``tools.HeightmapEncoder`` or anything with ``conv1`` (m / 4, C, 1, 1), ``conv2`` (m / 2, m / 4, 1, 1) and
+    ``conv3`` (m, m / 2, ceil(W / 4), ceil(L / 4)), all with a bias; ``P`` (3 Hd, Ks + m) and ``c`` from
+    ``tools.Pointer.fold_decoder(static, encoder)`` (m identity columns for the dynamic half); the rest as ``decoder_step``.
+    fp32, every sum one chain of fmaf in ascending order, the encoder's from their biases: the same bytes on every call.
+    With grad enabled and any input requiring grad the call runs through a ``torch.autograd.Function``: the backward reuses
+    tap_decoder_step_backward and ``decoder_step``'s matmuls, and gets the encoder's six parameter gradients -- and ``hm``'s,
+    scattered back to the cells (4i, 4j) -- from d_enc by recomputing the two hidden layers in torch; per step it keeps
+    ``gates``, h' and enc, and the inputs by reference.  A shape without a kernel
+    (``decoder_step_heightmap_supported``) raises ValueError."""
+    if P.dim() != 2 or int(P.shape[0]) % 3 or not P.is_floating_point():
+        raise ValueError("P must be a floating (3 Hd, Ks + m) tensor, got %s %s" % (P.dtype, tuple(P.shape)))
+    Hd = int(P.shape[0]) // 3
+    if hm is None or hm.dim() != 4 or not hm.is_floating_point():
+        raise ValueError("hm must be a floating (B, C, W, L) tensor, got %s" % (None if hm is None else "%s %s" % (hm.dtype, tuple(hm.shape)),))
+    B, C, W, L = (int(v) for v in hm.shape)
+    if xs is not None and (xs.dim() < 2 or int(xs.shape[0]) != B or not xs.is_floating_point()):
+        raise ValueError("xs must be a floating (%d, ...) tensor, got %s %s" % (B, xs.dtype, tuple(xs.shape)))
+    xs = None if xs is None else xs.reshape(B, -1)
+    Ks = 0 if xs is None else int(xs.shape[1])
+    xs = xs if Ks else None
+    convs = [getattr(encoder, name, None) for name in ("conv1", "conv2", "conv3")]
+    if any(cv is None or getattr(cv, "weight", None) is None or cv.weight.dim() != 4 or getattr(cv, "bias", None) is None for cv in convs):
+        raise ValueError("encoder must have conv1, conv2 and conv3 with four-axis weights and biases (tools.HeightmapEncoder)")
+    m = int(convs[2].weight.shape[0])
+    nw, nl = (W + 3) // 4, (L + 3) // 4
+    shapes = ((m // 4, C, 1, 1), (m // 2, m // 4, 1, 1), (m, m // 2, nw, nl))
+    for name, cv, shape in zip(("conv1", "conv2", "conv3"), convs, shapes):
+        if m % 4 or tuple(cv.weight.shape) != shape or tuple(cv.bias.shape) != shape[:1] or not cv.weight.is_floating_point():
+            raise ValueError("encoder.%s must be a floating %s convolution for a %s map and hidden size %d, got %s"
+                             % (name, shape, (C, W, L), m, tuple(cv.weight.shape)))
+    if Ks + m != int(P.shape[1]):
+        raise ValueError("P has %d columns, xs and the encoder have %d + %d values per env" % (int(P.shape[1]), Ks, m))
+    for name, v, shape in (("c", c, (3 * Hd,)), ("w_hh", w_hh, (3 * Hd, Hd)), ("b_hh", b_hh, (3 * Hd,)), ("wq", wq, (Hd, Hd))) + \
+            ((("h", h, (B, Hd)),) if h is not None else ()):
+        if tuple(v.shape) != shape or not v.is_floating_point():
+            raise ValueError("%s must be a floating %s tensor, got %s %s" % (name, shape, v.dtype, tuple(v.shape)))
+    if not decoder_step_heightmap_supported(Ks, C, W, L, m, Hd):
+        raise ValueError("no height-map decoder-step kernel for Ks %d, C %d, W %d, L %d, m %d, Hd %d (Hd 64 / 128 / 256, m = Hd / 2 or Hd, "
+                         "C 1 / 2 / 4, W and L <= 12, Ks <= 16, Ks + m <= Hd + 16)" % (Ks, C, W, L, m, Hd))
+    dev = _lib.resolve_device(P.device)
+
+    def prep(t):
+        if t is None:
+            return None
+        if t.dtype is not torch.float32:
+            t = t.float()
+        if not t.is_contiguous() or t.device != dev:
+            t = t.to(dev).contiguous()
+        return t
+    enc_w = (convs[0].weight.reshape(m // 4, C), convs[0].bias, convs[1].weight.reshape(m // 2, m // 4), convs[1].bias,
+             convs[2].weight.reshape(m, (m // 2) * nw * nl), convs[2].bias)
+    args = [prep(v) for v in (xs, hm, h) + enc_w + (P, c, w_hh, b_hh, wq)]
+    if torch.is_grad_enabled() and any(v is not None and v.requires_grad for v in args):
+        return _DecoderStepHeightmap.apply(*args)
+    h_new = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+    q = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+    d = [None if v is None else v.detach() for v in args]
+    _decoder_hm_into(d[0], d[1], d[2], tuple(d[3:9]), *d[9:], h_new, q, None, None)
+    return h_new, q
+
+
 class PointerHeadPolicy(object):
     """A pointer network's decoding head as a policy for ``run_episode`` and the steppers (model.py:356-372):
     ``scorer(step=, static=, dynamic=, current_mask=, mask=, decoder_static=, decoder_dynamic=)`` returns the logits

@@ -1,5 +1,6 @@
 """Names the reference's ``tools`` module exports on the hot path (model.py:4 does ``import tools``
 and builds ``tools.Container`` per env, model.py:294), backed by the HIP kernels."""
+import math
 import os
 
 import numpy as np
@@ -104,6 +105,35 @@ class DynamicBitsEncoder(nn.Module):
         return F.conv1d(x, self.conv.weight, self.conv.bias)
 
 
+class HeightmapEncoder(nn.Module):
+    """The reference's 3D ``dynamic_decoder`` (model.py:21-35) with its constructor and its children ``conv1``, ``conv2``,
+    ``conv3`` only: a checkpoint's ``dynamic_decoder.*`` loads with ``strict=True``.  ``hidden_size`` = m; conv1
+    (m / 4, input_size, 1, 1) and conv2 (m / 2, m / 4, 1, 1) have stride 2, conv3 (m, m / 2, ceil(W / 4), ceil(L / 4)) covers
+    what is left of the map, so ``forward(hm (B, input_size, W, L))`` -> (B, m, 1) reads the cells (4i, 4j) only.  ``forward``
+    is the reference's arithmetic in torch, any dtype and device; on the device the encoder runs inside the decoder step's
+    launch (``rollout.decoder_step_heightmap``, ``Pointer.fold_decoder(dynamic_decoder=<HeightmapEncoder>)``)."""
+
+    def __init__(self, input_size, hidden_size, map_size):
+        super(HeightmapEncoder, self).__init__()
+        self.input_size, self.hidden_size = int(input_size), int(hidden_size)
+        self.map_size = (int(map_size[0]), int(map_size[1]))
+        self.conv1 = nn.Conv2d(input_size, int(hidden_size / 4), stride=2, kernel_size=1)
+        self.conv2 = nn.Conv2d(int(hidden_size / 4), int(hidden_size / 2), stride=2, kernel_size=1)
+        self.conv3 = nn.Conv2d(int(hidden_size / 2), int(hidden_size),
+                               kernel_size=(math.ceil(map_size[0] / 4), math.ceil(map_size[1] / 4)))
+
+    def forward(self, input):
+        output = F.leaky_relu(self.conv1(input))
+        output = F.leaky_relu(self.conv2(output))
+        return self.conv3(output).squeeze(-1)
+
+
+def _is_heightmap_encoder(enc):
+    """a HeightmapEncoder, or anything with conv1 .. conv3 whose weights have four axes"""
+    return all(getattr(getattr(enc, name, None), "weight", None) is not None and getattr(enc, name).weight.dim() == 4
+               for name in ("conv1", "conv2", "conv3"))
+
+
 class _Attention(nn.Module):
     """The reference's Attention (model.py:38-74) as a parameter holder: ``v`` (1, 1, Hd) and ``W`` (1, Hd, 2 He + Hd),
     columns [static | dynamic | decoder]; Pointer.forward does its arithmetic."""
@@ -135,7 +165,8 @@ class Pointer(nn.Module):
     ``fold_decoder(...)`` -> (P, c) and ``fold_episode(dynamic_encoder, P, c)`` -> fold, once per episode, differentiable:
     the decoder's 1x1 encoders folded into the GRU's input weights, and everything else of a step that depends on the
     parameters alone (M, k, Wq).  ``forward_step(proj, bits, fold, decoder_static, decoder_dynamic, last_hh)`` -> (logits,
-    last_hh) is then TWO launches: ``rollout.decoder_step`` (input product, GRU cell and q) and ``rollout.pointer_scores``."""
+    last_hh) is then TWO launches: ``rollout.decoder_step`` (input product, GRU cell and q; with a ``HeightmapEncoder`` as the
+    dynamic decoder ``rollout.decoder_step_heightmap``, which runs that encoder too) and ``rollout.pointer_scores``."""
 
     def __init__(self, encoder_hidden_size, decoder_hidden_size, decoder_input_type, input_type, num_layers=1, dropout=0.2):
         super(Pointer, self).__init__()
@@ -215,10 +246,13 @@ class Pointer(nn.Module):
         is anything with a kernel-size-1 ``.conv`` (the reference's Encoder, ``DynamicBitsEncoder``) or an ``nn.Conv1d``
         itself; either may be None.  ``combine='cat'``: decoder_hidden = cat(static(xs), dynamic(xd)), the encoders' rows
         adding up to Hd; ``'sum'``: static(xs) + dynamic(xd), Hd rows each.  ``identity_dynamic=m`` (instead of a dynamic
-        encoder): the caller passes an already encoded dynamic half of m rows as xd -- the reference's 3D
-        HeightmapEncoder, which has leaky-ReLUs and does not fold -- and the fold takes m identity columns for it.  K =
-        the static encoder's inputs + the dynamic encoder's inputs (or m).  P carries what ``forward_step``'s fallback
-        needs (``P.static_decoder``, ``P.dynamic_decoder``, ``P.combine``, ``P.identity_dynamic``)."""
+        encoder): the caller passes an already encoded dynamic half of m rows as xd, and the fold takes m identity columns
+        for it.  A ``HeightmapEncoder`` as ``dynamic_decoder`` (the reference's 3D one; anything with four-axis ``conv1`` ..
+        ``conv3``) has leaky-ReLUs and does not fold: the fold takes m = its hidden size identity columns and no bias for that
+        half -- conv3's bias lives in the encoder's output --, and the encoder itself runs inside the step's launch
+        (``rollout.decoder_step_heightmap``).  K = the static encoder's inputs + the dynamic encoder's inputs (or m).  P
+        carries what ``forward_step`` needs (``P.static_decoder``, ``P.dynamic_decoder``, ``P.combine``,
+        ``P.identity_dynamic``)."""
         if combine not in ('cat', 'sum'):
             raise ValueError("combine must be 'cat' or 'sum', not %r" % (combine,))
         m = int(identity_dynamic)
@@ -228,8 +262,9 @@ class Pointer(nn.Module):
             raise ValueError("fold_decoder needs at least one encoder")
         Hd = self.decoder_hidden_size
         W_ih = self.gru.weight_ih_l0
+        heightmap = dynamic_decoder is not None and _is_heightmap_encoder(dynamic_decoder)
         parts = []                                      # (weight (rows, inputs), bias (rows,)) of each half of decoder_hidden
-        for enc in (static_decoder, dynamic_decoder):
+        for enc in (static_decoder, None if heightmap else dynamic_decoder):
             if enc is None:
                 continue
             conv = getattr(enc, "conv", enc)
@@ -238,8 +273,9 @@ class Pointer(nn.Module):
                 raise ValueError("a decoder encoder must be a kernel-size-1 convolution, got a weight of shape %s" % (tuple(w.shape),))
             w = w[:, :, 0].to(W_ih.dtype)
             parts.append((w, conv.bias.to(W_ih.dtype) if conv.bias is not None else torch.zeros_like(w[:, 0])))
-        if m:
-            parts.append((torch.eye(m, dtype=W_ih.dtype, device=W_ih.device), torch.zeros(m, dtype=W_ih.dtype, device=W_ih.device)))
+        mi = int(dynamic_decoder.conv3.weight.shape[0]) if heightmap else m
+        if mi:
+            parts.append((torch.eye(mi, dtype=W_ih.dtype, device=W_ih.device), torch.zeros(mi, dtype=W_ih.dtype, device=W_ih.device)))
         widths = [int(w.shape[0]) for w, _ in parts]
         if (sum(widths) != Hd) if combine == 'cat' else any(v != Hd for v in widths):
             raise ValueError("the encoders give %s rows; the GRU takes %d (combine=%r)" % (widths, Hd, combine))
@@ -271,6 +307,7 @@ class Pointer(nn.Module):
         fold.b_ih, fold.b_hh = (self.gru.bias_ih_l0, self.gru.bias_hh_l0) if self.gru.bias else (None, None)
         fold.static_decoder, fold.dynamic_decoder = getattr(P, "static_decoder", None), getattr(P, "dynamic_decoder", None)
         fold.combine, fold.identity_dynamic = getattr(P, "combine", None), getattr(P, "identity_dynamic", 0)
+        fold.heightmap = fold.dynamic_decoder if fold.dynamic_decoder is not None and _is_heightmap_encoder(fold.dynamic_decoder) else None
         return fold
 
     def _decoder_hidden(self, fold, decoder_static, decoder_dynamic):
@@ -281,7 +318,9 @@ class Pointer(nn.Module):
         halves = []
         if fold.static_decoder is not None:
             halves.append(fold.static_decoder(decoder_static.reshape(B, -1, 1)))
-        if fold.dynamic_decoder is not None:
+        if fold.heightmap is not None:
+            halves.append(fold.heightmap(decoder_dynamic))      # (B, C, W, L) as the stepper hands it out -> (B, m, 1)
+        elif fold.dynamic_decoder is not None:
             halves.append(fold.dynamic_decoder(decoder_dynamic.reshape(B, -1, 1)))
         elif fold.identity_dynamic:
             halves.append(decoder_dynamic.reshape(B, -1, 1))
@@ -292,29 +331,46 @@ class Pointer(nn.Module):
         ``decoder_static`` / ``decoder_dynamic`` and ``last_hh`` (the reference's (1, B, Hd), or None for zeros) to the new
         hidden state and q, then ``rollout.pointer_scores`` from the shadow ``bits`` to the logits.  ``proj`` from
         ``project_static``, ``fold`` from ``fold_episode`` (both once per episode).  Either input may be None when
-        ``fold_decoder`` had no encoder for it.  The torch path -- ``_gru_step`` on the unfolded decoder_hidden, then what
+        ``fold_decoder`` had no encoder for it.  With a ``HeightmapEncoder`` as the fold's dynamic decoder (a 3D actor) the first
+        launch is ``rollout.decoder_step_heightmap`` -- the encoder runs inside it -- and ``decoder_dynamic`` is the stepper's 4-D
+        (B, C, W, L) feature, which the torch path hands to the encoder as it is.  The torch path -- ``_gru_step`` on the unfolded decoder_hidden, then what
         ``forward_bits`` does: today's result -- runs instead when dropout would be active (training with p > 0), with more
         than one GRU layer, with a GRU without bias, off the GPU, or on a shape without a kernel for either launch."""
-        from .rollout import decoder_step, decoder_step_supported, pointer_scores, pointer_scores_supported
+        from .rollout import (decoder_step, decoder_step_heightmap, decoder_step_heightmap_supported, decoder_step_supported,
+                              pointer_scores, pointer_scores_supported)
         Hd, nR = self.decoder_hidden_size, int(proj.shape[2])
         Ks = 0 if decoder_static is None or fold.static_decoder is None else int(decoder_static[0].numel())
         Kd = 0 if decoder_dynamic is None or (fold.dynamic_decoder is None and not fold.identity_dynamic) else int(decoder_dynamic[0].numel())
         dropping = self.training and (self.drop_rnn.p > 0 or self.drop_hh.p > 0)
-        if dropping or self.num_layers != 1 or not self.gru.bias or not bits.is_cuda or Ks + Kd != int(fold.P.shape[1]) or \
-                not decoder_step_supported(Ks, Kd, Hd) or not pointer_scores_supported(fold.rows, nR, Hd):
+        hm = fold.heightmap
+        if hm is not None:
+            m = int(hm.conv3.weight.shape[0])
+            launch = decoder_dynamic is not None and decoder_dynamic.dim() == 4 and Ks + m == int(fold.P.shape[1]) and \
+                int(hm.conv1.weight.shape[1]) == int(decoder_dynamic.shape[1]) and \
+                tuple(hm.conv3.weight.shape[2:]) == tuple((int(v) + 3) // 4 for v in decoder_dynamic.shape[2:]) and \
+                decoder_step_heightmap_supported(Ks, *decoder_dynamic.shape[1:], m, Hd)
+        else:
+            launch = Ks + Kd == int(fold.P.shape[1]) and decoder_step_supported(Ks, Kd, Hd)
+        if dropping or self.num_layers != 1 or not self.gru.bias or not bits.is_cuda or not launch or \
+                not pointer_scores_supported(fold.rows, nR, Hd):
             decoder_hidden = self._decoder_hidden(fold, decoder_static, decoder_dynamic)
             return self.forward_bits(proj, bits, fold.dynamic_encoder, decoder_hidden, last_hh)
-        h_new, q = decoder_step(decoder_static if Ks else None, decoder_dynamic if Kd else None,
-                                None if last_hh is None else last_hh[0], fold.P, fold.c, fold.w_hh, fold.b_hh, fold.Wq)
+        if hm is not None:
+            h_new, q = decoder_step_heightmap(decoder_static if Ks else None, decoder_dynamic, None if last_hh is None else last_hh[0],
+                                              hm, fold.P, fold.c, fold.w_hh, fold.b_hh, fold.Wq)
+        else:
+            h_new, q = decoder_step(decoder_static if Ks else None, decoder_dynamic if Kd else None,
+                                    None if last_hh is None else last_hh[0], fold.P, fold.c, fold.w_hh, fold.b_hh, fold.Wq)
         logits = pointer_scores(proj, bits, fold.M, fold.k, q, fold.va, fold.vp, rows=fold.rows)
         return logits, h_new.unsqueeze(0)
 
 
 class StepFold(object):
     """What ``Pointer.fold_episode`` returns: the per-episode tensors of ``Pointer.forward_step`` (M, k, P, c, Wq, va, vp, the
-    GRU's w_ih / w_hh / b_ih / b_hh) and, for the torch path, the encoders and how the decoder's two are combined."""
+    GRU's w_ih / w_hh / b_ih / b_hh) and, for the torch path, the encoders and how the decoder's two are combined;
+    ``heightmap`` is the dynamic decoder when it is a ``HeightmapEncoder`` (it runs inside the step's launch), else None."""
     __slots__ = ("dynamic_encoder", "rows", "M", "k", "P", "c", "Wq", "va", "vp", "w_ih", "w_hh", "b_ih", "b_hh",
-                 "static_decoder", "dynamic_decoder", "combine", "identity_dynamic")
+                 "static_decoder", "dynamic_decoder", "combine", "identity_dynamic", "heightmap")
 
 
 class _EngineRow(object):
