@@ -4,7 +4,8 @@ model.py:38-74) on the CPU in float64, eval mode: for (He, Hd) = (32, 32) and (1
 xavier-uniform parameters (the reference's own initialisation of every parameter with more than one axis) -- the state
 dict, the four inputs (static_hidden, dynamic_hidden, decoder_hidden, last_hh), and the outputs probs and last_hh.
 Parameters and inputs are drawn in float32 and widened, so the fixture stores them as float32 without loss; the outputs
-are float64.  Data only.  Like make_golden.py it runs only where the reference checkout is present.  Usage:
+are float64.  No kernel exists for Hd = 32, so these cases reach the package's torch path only; the kernel path is pinned to
+the reference by make_golden_actor.py's fixtures (the whole DRL at He = 32, Hd = 64).  Data only.  Like make_golden.py it runs only where the reference checkout is present.  Usage:
 
     python tests/golden/make_golden_pointer.py
 """
