@@ -104,7 +104,7 @@ const char *tap_last_error(const tap_ctx *ctx);
  * hipGraph counts once, at capture.  tap_variant_hits writes up to `cap` rows of 8 ints (the key, then the count) and
  * returns the number of rows the record holds (TAP_E_INVALID if a key found no slot since the last reset);
  * tap_variant_hits_reset empties it. */
-/* The whole-episode and rolling kernels count on the same record, under kinds 16 .. 30 (tap_common.h: TapHitKind; 25: trial.hip, 26: policy.hip, 27: encode.hip, 28: pointer.hip, 29: decoder.hip, 30: heightmap.hip), after
+/* The whole-episode and rolling kernels count on the same record, under kinds 16 .. 31 (tap_common.h: TapHitKind; 25: trial.hip, 26: policy.hip, 27: encode.hip, 28: pointer.hip, 29: decoder.hip, 30: heightmap.hip, 31: critic.hip), after
  * the stream-wave kinds 0 .. 6.  Their keys, fields (kind, D, G, nc, mode, extra, wt):
  *   16 k_episode<D, G, SOFT>                      (16, D, G, SOFT, 0, 0, 0)
  *   17 k_episode_macs2<G, WIDE>                   (17, 2, G, WIDE, 0, 0, 0)
@@ -129,6 +129,8 @@ const char *tap_last_error(const tap_ctx *ctx);
  *   29 k_decoder_step                             (29, 0, TE, CHUNKS, H, 0, 0) TE = 16 envs per workgroup, CHUNKS = Hd / 64, H 1 = h given
  *      k_decoder_step_bw                          (29, 0, TE, CHUNKS, H, 1, 0)
  *   30 k_decoder_step_hm                          (30, C, NP, CHUNKS, H, 0, 0)   C height-map planes, NP = ceil(W / 4) ceil(L / 4) positions read
+ *   31 k_critic_value<HPL>                        (31, RES, HPL, PLANES, MALL, 0, 0) HPL = H / 64 hidden rows per lane, RES 1 = U resident in LDS (0: recomputed per block), MALL 1 = all of M staged (0: a 64-row slab at a time)
+ *      k_critic_value_bw<HPL> + _bw_reduce        (31, RES, HPL, PLANES, MALL, 1, 0) RES 1 = dU accumulated in LDS (0: in dU_out) (one count per call)
  * wt is the launch's RollArgs::wt (the window's fp32 stores; the init kernels store none), 0 for the episode kernels. */
 int tap_variant_hits(tap_ctx *ctx, int32_t *out, int cap);
 int tap_variant_hits_reset(tap_ctx *ctx);
@@ -695,6 +697,60 @@ int tap_pointer_scores_backward(tap_ctx *ctx, const float *proj, const unsigned 
                                 float *dva_out, float *dvp_out, void *scratch, size_t scratch_bytes, void *stream);
 /* bytes of scratch the backward needs for this shape (0 for a shape the entry refuses) */
 size_t tap_pointer_scores_backward_scratch(int B, int nR, int rows, int Hd);
+
+/* The state critic's value estimate in ONE launch from the critic's static input and the bit shadow (critic.hip): the
+ * reference's realCritic (trainer.py:18-94) after its GRU step.  With Es, bs / Ed, bd the static / dynamic encoder's
+ * conv, W = attention.W[0] = [Was | Wad | Waq] (H, 3H), v = attention.v[0, 0], F1, f1 = fc.0 and w2, b2 = fc.2 the caller
+ * folds, from the parameters alone (tools.StateCritic.fold):
+ *   G = [Was Es ; Waq Es ; F1 Es] (3H, S), g = [Was bs + Wad bd ; Waq bs ; F1 bs + f1] (3H,), M = Wad Ed (H, rows),
+ *   q0 = Waq . rnn_out (B, H) -- or ONE row for the whole batch, q0_stride 0.
+ * Per env b, in fp32, n = blocks:
+ *   U[j, c]    = g[j] + the M[j, r] of the rows r set in column c (ASCENDING, plane 0 before plane 1), then
+ *                fmaf(G[j, i], x[b, i, c], .) for i = 0 .. S - 1
+ *   for i in 0 .. n - 1:
+ *     s[c]       = sum_j v[j] tanhf(U[j, c] + q_i[j]);  p_i = softmax_c(s) over ALL nR columns, unmasked
+ *     xbar_i[k]  = sum_c p_i[c] x[b, k, c]
+ *     q_{i+1}[j] = g[H + j], then fmaf(G[H + j, k], xbar_i[k], .) for k ascending       (not after the last block)
+ *   z[j]       = g[2H + j], then fmaf(G[2H + j, k], xbar_{n-1}[k], .)
+ *   value      = b2 + sum_j w2[j] max(z[j], 0)
+ * which equals the reference's arithmetic in exact arithmetic: every context is static_hidden . p with sum p = 1, i.e.
+ * Es (x . p) + bs.
+ *   x (B, S, nR) f32; bits (B, tap_bits_words(rows, nR)) the shadow in tap_dyn_bits' layout, bits at positions >= rows are
+ *   IGNORED; an all-zero shadow gives U without M entering, whatever M holds; G, M row-major; q0 (B, H) with q0_stride = H
+ *   or (H,) with q0_stride = 0; b2 a device pointer to one float.
+ *   value_out (B,), z_out (B, H), p_out (B, n, nR), xbar_out (B, n, S), q_out (B, n, H) with q_out[:, 0] = q0: what the
+ *   backward reads.
+ * The order of every sum is fixed by the shape (a lane's hidden rows in order, an xor butterfly over the 64 lanes, the
+ * 64-row slabs in order where M is staged by slabs; a lane's columns in order, then the butterfly): two calls give the
+ * same bytes.  No atomics, no contraction beyond the fmafs above.  One launch, no allocation, no host read, no stream
+ * synchronisation (capturable in a hipGraph).  k_critic_value<HPL>: a wavefront per env, four envs per workgroup, lanes
+ * along the hidden rows (HPL = H / 64 rows per lane).  Launch record key (31, RES, HPL, PLANES, MALL, 0, 0).
+ * Shapes: every window with a shadow (rows <= 128, nR % 4 == 0, nR <= 256), H 64, 128 or 256, S <= 8, blocks <= 8,
+ * q0_stride 0 or H; anything else -> TAP_E_UNSUPPORTED.  Checks, in tap_pointer_scores' order: B < 0 or nR / rows / H / S /
+ * blocks < 1 -> TAP_E_INVALID; B == 0 -> TAP_OK; a null buffer -> TAP_E_INVALID; a shape outside the list ->
+ * TAP_E_UNSUPPORTED; a misaligned buffer (bits 8 bytes, floats 4) -> TAP_E_INVALID. */
+int tap_critic_value(tap_ctx *ctx, const float *x, const unsigned long long *bits, int B, int nR, int rows, int H, int S,
+                     int blocks, const float *G, const float *g, const float *M, const float *q0, int q0_stride,
+                     const float *v, const float *w2, const float *b2, float *value_out, float *z_out, float *p_out,
+                     float *xbar_out, float *q_out, void *stream);
+
+/* The backward of tap_critic_value from dz (B, H) = g_value w2 [z > 0] (the caller's element-wise product): q and p as
+ * the forward wrote them, the forward's inputs; U and the tanh arguments are recomputed.  For i = n - 1 down to 0:
+ * dxbar_i = G2^T dz for the last block, else G1^T dq_{i+1}; dp[c] = sum_k dxbar_i[k] x[k, c]; ds = p_i (dp - sum p_i dp);
+ * dA[j, c] = ds[c] v[j] (1 - tanh^2); dU += dA; dq_i[j] = sum_c dA[j, c]; dv[j] += sum_c ds[c] tanh(.).  Writes
+ *   dU_out (B, H, nR) f32, columns fastest -- tap_encode_bits_backward with g = dU_out gives dM and the bias sum --;
+ *   dq_out (B, n, H); dv_out (H,).
+ * dv goes through one partial per workgroup in `scratch` (at least tap_critic_value_backward_scratch(...) bytes; a
+ * smaller scratch_bytes or a null scratch -> TAP_E_INVALID) and a second launch that adds them in workgroup order: no
+ * atomics, two calls give the same bytes.  The forward's checks in the forward's order (every buffer required), then the
+ * scratch, then the alignment (dU_out leaves as float4s: 16 bytes); B == 0 -> TAP_OK with nothing written.
+ * Launch record key (31, RES, HPL, PLANES, MALL, 1, 0), one count per call. */
+int tap_critic_value_backward(tap_ctx *ctx, const float *x, const unsigned long long *bits, int B, int nR, int rows, int H,
+                              int S, int blocks, const float *G, const float *g, const float *M, const float *v,
+                              const float *q, const float *p, const float *dz, float *dU_out, float *dq_out,
+                              float *dv_out, void *scratch, size_t scratch_bytes, void *stream);
+/* bytes of scratch the backward needs for this shape (0 for a shape the entry refuses) */
+size_t tap_critic_value_backward_scratch(int B, int nR, int rows, int H, int S, int blocks);
 
 /* The decoder side of a decoding step in ONE launch (model.py:347-354 and the GRU step of 108-115, then the decoder's
  * columns of the attention's W): from the stepper's decoder buffers and last_hh to the new hidden state and the q that

@@ -32,6 +32,7 @@ TAP_HIT_ENCODE_BITS = 27                                       # encode.hip: k_e
 TAP_HIT_POINTER = 28                                           # pointer.hip: k_pointer_scores<HPL> / _bw<HPL> + _bw_reduce
 TAP_HIT_DECODER = 29                                           # decoder.hip: k_decoder_step / k_decoder_step_bw
 TAP_HIT_HEIGHTMAP = 30                                         # heightmap.hip: k_decoder_step_hm
+TAP_HIT_CRITIC = 31                                            # critic.hip: k_critic_value<HPL> / _bw<HPL> + _bw_reduce
 TAP_P_GREEDY = 1
 
 
@@ -101,6 +102,9 @@ _PROTOS = {
     "tap_pointer_scores_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                          _vp, _sz, _vp]),
     "tap_pointer_scores_backward_scratch": (_sz, [_i, _i, _i, _i]),
+    "tap_critic_value": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i] + [_vp] * 9),
+    "tap_critic_value_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i] + [_vp] * 11 + [_sz, _vp]),
+    "tap_critic_value_backward_scratch": (_sz, [_i, _i, _i, _i, _i, _i]),
     "tap_decoder_step": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tap_decoder_step_backward": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tap_decoder_step_hm": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _i] + [_vp] * 16),

@@ -424,6 +424,145 @@ def pointer_scores(proj, bits, M, k, q, va, vp, rows=None):
     return logits
 
 
+def critic_value_supported(rows, nR, H, S, blocks):
+    """whether tap_critic_value has a kernel for this shape: a window with a shadow, H 64, 128 or 256, 1 <= S <= 8 static
+    rows and 1 <= blocks <= 8 process blocks"""
+    return int(H) in (64, 128, 256) and 1 <= int(S) <= 8 and 1 <= int(blocks) <= 8 and \
+        _lib.lib().tap_bits_words(int(rows), int(nR)) > 0
+
+
+def _critic_into(x, bits, G, g, M, q0, v, w2, b2, blocks, rows, value, z, p, xbar, q):
+    """tap_critic_value on prepared buffers: one launch on the current stream, nothing allocated.  q0 (B, H) or (1, H):
+    one row serves the whole batch (stride 0)"""
+    dev = x.device
+    c = _lib.ctx(dev)
+    B, S, nR = (int(d) for d in x.shape)
+    H = int(M.shape[0])
+    stride = 0 if int(q0.shape[0]) == 1 else H
+    _lib.check(_lib.lib().tap_critic_value(c, _lib.ptr(x), _lib.ptr(bits), B, nR, rows, H, S, blocks, _lib.ptr(G), _lib.ptr(g),
+                                           _lib.ptr(M), _lib.ptr(q0), stride, _lib.ptr(v), _lib.ptr(w2), _lib.ptr(b2),
+                                           _lib.ptr(value), _lib.ptr(z), _lib.ptr(p), _lib.ptr(xbar), _lib.ptr(q),
+                                           _lib.stream_of(dev)), c)
+
+
+def _critic_buffers(B, S, nR, H, blocks, dev):
+    f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    return f(B), f(B, H), f(B, blocks, nR), f(B, blocks, S), f(B, blocks, H)
+
+
+class _CriticValue(torch.autograd.Function):
+    """critic_value under autograd: forward = the one launch, backward = tap_critic_value_backward (dU, dq, dv) and
+    tap_encode_bits_backward on dU (dM and the shared bias sum); the sums over the batch are torch ops on those tensors.
+    What a call keeps beside its parameters: a CLONE of the shadow (the stepper's shadow buffers alternate), ``x`` by
+    reference, z (B, H), p (B, n, nR), xbar (B, n, S) and q (B, n, H) -- nothing of size H * nR per env."""
+
+    @staticmethod
+    def forward(ctx, x, bits, G, g, M, q0, v, w2, b2, blocks, rows):
+        B, S, nR = (int(d) for d in x.shape)
+        H = int(M.shape[0])
+        value, z, p, xbar, q = _critic_buffers(B, S, nR, H, blocks, x.device)
+        _critic_into(x, bits, G, g, M, q0, v, w2, b2, blocks, rows, value, z, p, xbar, q)
+        ctx.save_for_backward(x, bits.clone(), G, g, M, v, w2, z, p, xbar, q)
+        ctx.dims = (B, S, nR, H, blocks, rows, int(q0.shape[0]))
+        return value
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gv):
+        x, bits, G, g, M, v, w2, z, p, xbar, q = ctx.saved_tensors
+        B, S, nR, H, n, rows, q0_rows = ctx.dims
+        dev = x.device
+        L, c = _lib.lib(), _lib.ctx(dev)
+        f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        if B == 0:
+            zero = lambda t: torch.zeros_like(t)
+            return None, None, zero(G), zero(g), zero(M), f(q0_rows, H).zero_(), zero(v), zero(w2), f(1).zero_(), None, None
+        gv = _as_f32(gv, dev)
+        relu = z.clamp_min(0)
+        dz = gv.unsqueeze(1) * w2.unsqueeze(0) * (z > 0).to(torch.float32)
+        dU, dq, dv, dM, dk = f(B, H, nR), f(B, n, H), f(H), f(H, rows), f(H)
+        need = int(L.tap_critic_value_backward_scratch(B, nR, rows, H, S, n))
+        need2 = int(L.tap_encode_bits_backward_scratch(B, nR, rows, H))
+        scratch = f(max(need, need2, 16) // 4)
+        st = _lib.stream_of(dev)
+        _lib.check(L.tap_critic_value_backward(c, _lib.ptr(x), _lib.ptr(bits), B, nR, rows, H, S, n, _lib.ptr(G), _lib.ptr(g),
+                                               _lib.ptr(M), _lib.ptr(v), _lib.ptr(q), _lib.ptr(p), _lib.ptr(dz), _lib.ptr(dU),
+                                               _lib.ptr(dq), _lib.ptr(dv), _lib.ptr(scratch), need, st), c)
+        # dM[j, r] = sum over (b, c) of dU[b, j, c] bit[b, r, c], dk[j] = sum of dU: the encoder's backward
+        _lib.check(L.tap_encode_bits_backward(c, _lib.ptr(bits), _lib.ptr(dU), B, nR, rows, H, _lib.ptr(dM), _lib.ptr(dk),
+                                              _lib.ptr(scratch), need2, st), c)
+        dq1 = dq[:, 1:].reshape(-1, H)
+        # dG0 = sum_b dU[b] x[b]^T: one batched product that reads dU once, then the batch sum of (B, H, S)
+        dG = torch.cat((torch.bmm(dU, x.transpose(1, 2)).sum(0), dq1.t().matmul(xbar[:, :-1].reshape(-1, S)),
+                        dz.t().matmul(xbar[:, -1])), 0)
+        dg = torch.cat((dk, dq1.sum(0), dz.sum(0)), 0)
+        dq0 = dq[:, 0] if q0_rows == B else dq[:, 0].sum(0, keepdim=True)
+        return None, None, dG, dg, dM, dq0, dv, gv.matmul(relu), gv.sum().reshape(1), None, None
+
+
+def critic_value(x, bits, G, g, M, q0, v, w2, b2, blocks, rows=None):
+    """The state critic's value estimate on the bit shadow (tapenv.h: tap_critic_value; the reference's realCritic,
+    trainer.py:18-94, after its GRU step) in ONE launch -> value (B,) float32.
+    ``x`` (B, S, nR) the critic's static input; ``bits`` int64 in ``pack.dynamic_bits`` layout, (B, nR) -- (B, 2 * nR) or
+    (B, 2, nR) above 64 rows; ``G`` (3 H, S), ``g`` (3 H,), ``M`` (H, rows) the encoders folded into the attention's W and
+    fc.0 (``tools.StateCritic.fold`` builds them); ``q0`` (B, H), or (1, H) / (H,) for one row that serves the whole batch;
+    ``v`` / ``w2`` (H,); ``b2`` (1,) or a scalar tensor; ``blocks`` the number of process blocks.  ``rows`` defaults to
+    ``M.shape[1]``; bits at positions >= rows are ignored.  Per env, in fp32 and in an order fixed by the shape:
+    U = g[:H] + the M columns of the set rows (ascending) + G[:H] . x; per block s = v . tanh(U + q), p = softmax over all
+    columns, xbar = x . p, q = g[H:2H] + G[H:2H] . xbar; z = g[2H:] + G[2H:] . xbar; value = b2 + w2 . relu(z).
+    Floating inputs of another dtype, layout or device are converted through ``.float()`` (autograd sees the cast).  With
+    grad enabled and any parameter requiring grad the call runs through a ``torch.autograd.Function`` whose backward is
+    tap_critic_value_backward + tap_encode_bits_backward (deterministic: no atomics); it keeps a clone of ``bits``, ``x``
+    by reference, and z (B, H), p (B, blocks, nR), xbar (B, blocks, S), q (B, blocks, H).  ``x`` and ``bits`` get no
+    gradient.  A shape without a kernel (``critic_value_supported``) raises ValueError."""
+    if bits.dtype is not torch.int64:
+        raise TypeError("bits must be the int64 shadow (pack.dynamic_bits), got %s" % (bits.dtype,))
+    if x.dim() != 3 or not x.is_floating_point():
+        raise ValueError("x must be a floating (B, S, nR) tensor, got %s %s" % (x.dtype, tuple(x.shape)))
+    B, S, nR = (int(d) for d in x.shape)
+    if M.dim() != 2 or not M.is_floating_point():
+        raise ValueError("M must be a floating (H, rows) tensor, got %s %s" % (M.dtype, tuple(M.shape)))
+    H = int(M.shape[0])
+    rows = int(M.shape[1]) if rows is None else int(rows)
+    if rows != int(M.shape[1]):
+        raise ValueError("M has %d rows' columns, rows is %d" % (int(M.shape[1]), rows))
+    blocks = int(blocks)
+    if q0.dim() == 1:
+        q0 = q0.unsqueeze(0)
+    if b2.dim() == 0:
+        b2 = b2.reshape(1)
+    for name, t, shapes in (("G", G, ((3 * H, S),)), ("g", g, ((3 * H,),)), ("q0", q0, ((B, H), (1, H))), ("v", v, ((H,),)),
+                            ("w2", w2, ((H,),)), ("b2", b2, ((1,),))):
+        if tuple(t.shape) not in shapes or not t.is_floating_point():
+            raise ValueError("%s must be a floating %s tensor, got %s %s" % (name, " or ".join(str(s) for s in shapes), t.dtype,
+                                                                           tuple(t.shape)))
+    planes = 2 if rows > 64 else 1
+    if rows < 1 or nR < 1 or not critic_value_supported(rows, nR, H, S, blocks):
+        raise ValueError("no critic kernel for rows %d, nR %d, H %d, S %d, blocks %d (rows <= 128, nR %% 4 == 0, nR <= 256, "
+                         "H 64 / 128 / 256, S 1..8, blocks 1..8)" % (rows, nR, H, S, blocks))
+    if bits.dim() not in (2, 3) or int(bits.shape[0]) != B or int(math.prod(bits.shape[1:])) != planes * nR or \
+            (bits.dim() == 3 and tuple(bits.shape[1:]) != (planes, nR)):
+        raise ValueError("bits of shape %s is not the shadow of %d envs of a (%d, %d) window" % (tuple(bits.shape), B, rows, nR))
+    dev = _lib.resolve_device(bits.device)
+    if not bits.is_contiguous() or bits.device != dev:
+        bits = bits.to(dev).contiguous()
+
+    def prep(t):
+        if t.dtype is not torch.float32:
+            t = t.float()
+        if not t.is_contiguous() or t.device != dev:
+            t = t.to(dev).contiguous()
+        return t
+    x = prep(x.detach())
+    args = [prep(t) for t in (G, g, M, q0, v, w2, b2)]
+    if torch.is_grad_enabled() and any(t.requires_grad for t in args):
+        return _CriticValue.apply(x, bits, *args, blocks, rows)
+    args = [t.detach() for t in args]
+    value, z, p, xbar, q = _critic_buffers(B, S, nR, H, blocks, dev)
+    _critic_into(x, bits, *args, blocks, rows, value, z, p, xbar, q)
+    return value
+
+
 def decoder_step_supported(Ks, Kd, Hd):
     """whether tap_decoder_step has a kernel for this shape: Hd 64, 128 or 256 and 1 <= Ks + Kd <= Hd + 16"""
     Ks, Kd, Hd = int(Ks), int(Kd), int(Hd)

@@ -365,6 +365,132 @@ class Pointer(nn.Module):
         return logits, h_new.unsqueeze(0)
 
 
+class _Conv1x1(nn.Module):
+    """The reference's Encoder (model.py:9-18): its only layer is ``conv``, a Conv1d(input_size, hidden_size, 1)"""
+
+    def __init__(self, input_size, hidden_size):
+        super(_Conv1x1, self).__init__()
+        self.conv = nn.Conv1d(input_size, int(hidden_size), kernel_size=1)
+
+    def forward(self, input):
+        return self.conv(input)
+
+
+class _CriticAttention(nn.Module):
+    """The reference's criticAttention (trainer.py:18-42) as a parameter holder: ``v`` (1, 1, H) and ``W`` (1, H, 3 H),
+    columns [static | dynamic | decoder]; StateCritic.forward does its arithmetic."""
+
+    def __init__(self, hidden_size):
+        super(_CriticAttention, self).__init__()
+        self.v = nn.Parameter(torch.zeros((1, 1, hidden_size), requires_grad=True))
+        self.W = nn.Parameter(torch.zeros((1, hidden_size, 3 * hidden_size), requires_grad=True))
+
+
+class CriticFold(object):
+    """What ``StateCritic.fold`` returns: G (3 H, S), g (3 H,), M (H, rows), v, w2 (H,), b2 (1,) -- ``rollout.critic_value``'s
+    parameters -- and Wq (H, H), the attention's columns for the decoder (q0 = rnn_out . Wq^T)."""
+    __slots__ = ("G", "g", "M", "v", "w2", "b2", "Wq")
+
+
+class StateCritic(nn.Module):
+    """The reference trainer's critic ``realCritic`` (trainer.py:44-94; its criticAttention, trainer.py:18-42) with a second
+    input form.  The constructor is the reference's and so are its 16 state-dict keys -- ``static_encoder.conv.*``,
+    ``dynamic_encoder.conv.*``, ``decoder.conv.*``, ``gru.*_l0``, ``attention.v``, ``attention.W``, ``fc.0.*``, ``fc.2.*`` --:
+    a reference ``critic.pt`` loads with ``strict=True``.
+
+    ``forward(static, dynamic, decoder_input=None, last_hh=None)`` -> (B, 1), as the reference returns.  A floating
+    ``dynamic`` (B, rows, nR) runs the reference's arithmetic in torch, any dtype and device: the oracle path.  An int64
+    ``dynamic`` is the bit shadow (``EpisodeStepper.dynamic_bits`` taken before step 0, or ``pack.dynamic_bits``): the
+    encoders are folded into the attention's W and fc.0 (``fold()``) and ``rollout.critic_value`` computes the estimate in
+    ONE launch from ``static`` and the shadow -- no static_hidden, no dynamic_hidden, no concatenation.
+    ``decoder_input=None`` is the trainer's zero ``x0`` (trainer.py:213): the GRU step then runs for ONE row and serves the
+    whole batch.  ``drop_hh`` touches only ``last_hh``, which the estimate does not depend on, so the device path is valid
+    in training mode too.  The torch path takes over for ``num_layers > 1``, ``n_process_blocks`` outside 1..8, tensors
+    off the GPU and shapes without a kernel (``rollout.critic_value_supported``); on a shadow it gets dynamic_hidden from
+    ``rollout.encode_dynamic_bits`` on the GPU and from the unpacked bits elsewhere.
+
+    ``fold()`` -> CriticFold, differentiable; under ``no_grad`` it can be built once and handed to ``forward(..., fold=f)``
+    for many batches."""
+
+    def __init__(self, static_size, dynamic_size, hidden_size, num_layers=1, n_process_blocks=3, dropout=0.2):
+        super(StateCritic, self).__init__()
+        self.static_encoder = _Conv1x1(static_size, hidden_size)
+        self.dynamic_encoder = _Conv1x1(dynamic_size, hidden_size)
+        self.decoder = _Conv1x1(static_size, hidden_size)
+        self.gru = nn.GRU(hidden_size, hidden_size, num_layers, batch_first=True)
+        self.attention = _CriticAttention(hidden_size)
+        self.n_process_blocks = n_process_blocks
+        self.fc = nn.Sequential(nn.Linear(hidden_size, hidden_size), nn.ReLU(), nn.Linear(hidden_size, 1))
+        self.num_layers = num_layers
+        self.drop_hh = nn.Dropout(p=dropout)
+        self.static_size, self.dynamic_size, self.hidden_size = int(static_size), int(dynamic_size), int(hidden_size)
+
+    def fold(self):
+        H = self.hidden_size
+        W = self.attention.W[0]
+        Was, Wad, Waq = W[:, :H], W[:, H:2 * H], W[:, 2 * H:]
+        Es, bs = self.static_encoder.conv.weight[:, :, 0], self.static_encoder.conv.bias
+        Ed, bd = self.dynamic_encoder.conv.weight[:, :, 0], self.dynamic_encoder.conv.bias
+        F1, f1 = self.fc[0].weight, self.fc[0].bias
+        f = CriticFold()
+        f.G = torch.cat((Was.matmul(Es), Waq.matmul(Es), F1.matmul(Es)), 0)
+        f.g = torch.cat((Was.matmul(bs) + Wad.matmul(bd), Waq.matmul(bs), F1.matmul(bs) + f1), 0)
+        f.M = Wad.matmul(Ed)
+        f.v, f.w2, f.b2, f.Wq = self.attention.v[0, 0], self.fc[2].weight[0], self.fc[2].bias, Waq
+        return f
+
+    def _rnn_out(self, static, decoder_input, last_hh):
+        """trainer.py:78-84: the decoder's encoder and the GRU step -> rnn_out (B, H), or (1, H) for the zero x0"""
+        if decoder_input is None:
+            w = self.decoder.conv.weight
+            decoder_input = torch.zeros(1 if last_hh is None else static.shape[0], self.static_size, 1, dtype=w.dtype, device=w.device)
+        rnn_out, last_hh = self.gru(self.decoder(decoder_input).transpose(2, 1), last_hh)
+        if self.num_layers == 1:
+            last_hh = self.drop_hh(last_hh)         # (with more layers the GRU has applied it); the estimate does not read it
+        return rnn_out.squeeze(1)
+
+    def _unpack(self, bits, nR):
+        rows = self.dynamic_size
+        w = bits.reshape(bits.shape[0], 2 if rows > 64 else 1, nR)
+        r = torch.arange(rows, device=bits.device)
+        return (w[:, r // 64, :] >> (r % 64).view(1, rows, 1)) & 1
+
+    def forward(self, static, dynamic, decoder_input=None, last_hh=None, fold=None):
+        from .rollout import critic_value, critic_value_supported, encode_dynamic_bits
+        B, S, nR = static.shape
+        H, n = self.hidden_size, self.n_process_blocks
+        rnn_out = self._rnn_out(static, decoder_input, last_hh)
+        shadow = dynamic.dtype is torch.int64
+        if not shadow and not dynamic.is_floating_point():
+            raise TypeError("StateCritic takes the int64 shadow or the floating `dynamic`, got %s" % (dynamic.dtype,))
+        if shadow and self.num_layers == 1 and static.is_cuda and dynamic.is_cuda and self.attention.W.is_cuda and \
+                critic_value_supported(self.dynamic_size, nR, H, S, n):
+            f = self.fold() if fold is None else fold
+            q0 = rnn_out.matmul(f.Wq.t())
+            return critic_value(static, dynamic, f.G, f.g, f.M, q0, f.v, f.w2, f.b2, n, rows=self.dynamic_size).unsqueeze(1)
+        conv = self.dynamic_encoder.conv
+        if shadow:
+            if dynamic.is_cuda and _lib.lib().tap_bits_words(self.dynamic_size, int(nR)) > 0:
+                dynamic_hidden = encode_dynamic_bits(dynamic, conv.weight, conv.bias, rows=self.dynamic_size).to(conv.weight.dtype)
+            else:
+                dynamic_hidden = self.dynamic_encoder(self._unpack(dynamic, int(nR)).to(conv.weight.dtype))
+        else:
+            dynamic_hidden = self.dynamic_encoder(dynamic)
+        static_hidden = self.static_encoder(static)
+        if rnn_out.shape[0] != B:
+            rnn_out = rnn_out.expand(B, -1)
+        v, W = self.attention.v.expand(B, 1, H), self.attention.W.expand(B, H, -1)
+        for _ in range(n):
+            # criticAttention.forward (trainer.py:29-42)
+            hidden = torch.cat((static_hidden, dynamic_hidden, rnn_out.unsqueeze(2).expand_as(static_hidden)), 1)
+            prob = torch.softmax(torch.bmm(v, torch.tanh(torch.bmm(W, hidden))), dim=2)
+            rnn_out = prob.bmm(static_hidden.permute(0, 2, 1)).squeeze(1)
+        return self.fc(rnn_out)
+
+
+realCritic = StateCritic
+
+
 class StepFold(object):
     """What ``Pointer.fold_episode`` returns: the per-episode tensors of ``Pointer.forward_step`` (M, k, P, c, Wq, va, vp, the
     GRU's w_ih / w_hh / b_ih / b_hh) and, for the torch path, the encoders and how the decoder's two are combined;
