@@ -828,6 +828,49 @@ int tap_decoder_step_hm(tap_ctx *ctx, const float *xs, int Ks, const float *hm, 
                         const float *b3, const float *P, const float *c, const float *w_hh, const float *b_hh,
                         const float *wq, float *h_out, float *q_out, float *gates_out, float *enc_out, void *stream);
 
+/* tap_decoder_step with the pointer's two dropouts (model.py:112-115: drop_rnn on the GRU's output, drop_hh on last_hh)
+ * inside the launch, for training.  Both are element-wise masks on h'; the random source is a counter-based generator, so
+ * the masks are the same bytes on every call, need no host value, change on every replay of a captured graph and can be
+ * recomputed anywhere (rollout.dropout_keep_words is the torch form, tests/step_dropout_model.py the numpy one).
+ *   Generator: Philox4x32-10, multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85, ten rounds.
+ *   For env b of the call, hidden row j:  counter = (env_offset + b, j, step, episode mod 2^32),  key = (seed mod 2^32,
+ *   seed >> 32), with (seed, episode) = state[0], state[1] -- an int64[2] ON THE DEVICE, read by the launch.  Output word 0
+ *   decides drop_rnn, word 1 drop_hh; words 2 and 3 are unused.
+ *   Keep iff word >= thr, thr = min(2^32 - 1, round(p 2^32)) computed by the caller, one per mask.  A kept element is
+ *   h' s with s = float32(1 / (1 - p)), a dropped one +0.0f.  thr = 0, s = 1 keeps everything: the bytes of tap_decoder_step.
+ *   An env's masks depend on (seed, episode, step, env_offset + b, j) and on nothing else.
+ * h_out (B, Hd) = drop_hh(h'); q_out = wq . drop_rnn(h') in tap_decoder_step's order; gates_out (B, 4, Hd) or NULL as
+ * tap_decoder_step writes it (r, z, n, gh_n of the step before any mask); rnn_out (B, Hd) = drop_rnn(h') or NULL -- the
+ * backward's dwq needs it; keep_out (B, 2, Hd / 64) int64: plane 0 drop_rnn, plane 1 drop_hh, bit j mod 64 of word j / 64
+ * set iff row j is kept (one wavefront ballot per word, stored by one lane with an ordinary vector store).  Everything
+ * else -- geometry, sum orders, shapes, the order of the checks -- is tap_decoder_step's; a null state or keep_out ->
+ * TAP_E_INVALID with the other null buffers, and both must be 8-byte aligned.  Launch record key (29, 0, TE, Hd / 64, H, 2,
+ * 0): a dropout launch never records variant 0. */
+int tap_decoder_step_dropout(tap_ctx *ctx, const float *xs, int Ks, const float *xd, int Kd, const float *h, int B, int Hd,
+                             const float *P, const float *c, const float *w_hh, const float *b_hh, const float *wq,
+                             const int64_t *state, uint32_t step, uint32_t env_offset, uint32_t thr_rnn, uint32_t thr_hh,
+                             float s_rnn, float s_hh, float *h_out, float *q_out, float *gates_out, float *rnn_out,
+                             int64_t *keep_out, void *stream);
+
+/* tap_decoder_step_hm with the same two masks at the same place (tap_decoder_step_dropout has the definition); the encoder
+ * stage is untouched.  Launch record key (30, C, Np, Hd / 64, H, 2, 0). */
+int tap_decoder_step_hm_dropout(tap_ctx *ctx, const float *xs, int Ks, const float *hm, int C, int W, int L, const float *h,
+                                int B, int Hd, int m, const float *w1, const float *b1, const float *w2, const float *b2,
+                                const float *w3, const float *b3, const float *P, const float *c, const float *w_hh,
+                                const float *b_hh, const float *wq, const int64_t *state, uint32_t step, uint32_t env_offset,
+                                uint32_t thr_rnn, uint32_t thr_hh, float s_rnn, float s_hh, float *h_out, float *q_out,
+                                float *gates_out, float *enc_out, float *rnn_out, int64_t *keep_out, void *stream);
+
+/* tap_decoder_step_backward for a step that ran with dropout, one element-wise launch, no atomics.  last_hh and rnn_out
+ * both hang on h', so with g_h (B, Hd) the gradient at the returned last_hh, g_r (B, Hd) = g_q . wq (the caller's matmul)
+ * and keep (B, 2, Hd / 64) as the forward wrote it:
+ *   g = keep_hh s_hh g_h + keep_rnn s_rnn g_r        (each product and the sum rounded; a dropped element adds +0.0f)
+ * and then tap_decoder_step_backward's formulas and outputs from g.  Checks as there; g_r and keep are required, keep
+ * 8-byte aligned.  Launch record key (29, 0, TE, Hd / 64, H, 3, 0). */
+int tap_decoder_step_dropout_backward(tap_ctx *ctx, int B, int Hd, const float *gates, const float *h, const float *g_h,
+                                      const float *g_r, const int64_t *keep, float s_rnn, float s_hh, float *dgi_out,
+                                      float *dghn_out, float *dh_carry_out, void *stream);
+
 /* ---- the step object of a decoding loop ----------------------------------------------------- */
 /* DRL.forward's loop (model.py:342-496) runs its policy network between the environment steps, so the loop is
  * issued from the host, step by step, and what the host pays per step counts.  A tap_stepper is

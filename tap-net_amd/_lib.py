@@ -73,6 +73,7 @@ _lock = threading.RLock()
 _ctxs = {}
 
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
+_u32, _f = C.c_uint32, C.c_float
 _PROTOS = {
     "tap_abi_version": (_i, []),
     "tap_status_string": (C.c_char_p, [_i]),
@@ -108,6 +109,9 @@ _PROTOS = {
     "tap_decoder_step": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tap_decoder_step_backward": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tap_decoder_step_hm": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _i] + [_vp] * 16),
+    "tap_decoder_step_dropout": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i] + [_vp] * 6 + [_u32] * 4 + [_f, _f] + [_vp] * 6),
+    "tap_decoder_step_hm_dropout": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _i] + [_vp] * 12 + [_u32] * 4 + [_f, _f] + [_vp] * 7),
+    "tap_decoder_step_dropout_backward": (_i, [_vp, _i, _i] + [_vp] * 5 + [_f, _f] + [_vp] * 4),
     "tap_env_feature": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp]),
     "tap_env_ratio": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp, _vp, _vp]),
     "tap_env_export": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp, _vp, _vp, _vp]),

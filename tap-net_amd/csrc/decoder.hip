@@ -22,6 +22,13 @@
 // depend on which other envs share its launch.
 //
 // Backward: element-wise only (k_decoder_step_bw), from the saved gates; the sums over the batch are the caller's GEMMs.
+//
+// Dropout form (training; tapenv.h: tap_decoder_step_dropout): the pointer's drop_hh and drop_rnn are two element-wise masks
+// on h', applied where h' leaves the registers -- the value stored to h_out and the value written to the h' tile that q
+// reads.  A lane draws its own (env, row) pair of keep bits from Philox4x32-10 (tap_decoder.h), keyed on a (seed, episode)
+// pair read from device memory; a wavefront's 64 rows of an env are one ballot = one keep word.  The kernel is a template on
+// its argument struct: the plain instantiation's gfx950 listing is instruction for instruction what it was before the
+// dropout form existed.
 #include "tap_decoder.h"
 
 namespace {
@@ -40,8 +47,16 @@ inline size_t dec_lds_bytes(int Hd)
     return ((size_t)DEC_WROWS * DEC_WS + (size_t)DEC_TE * DEC_KC + 2 * (size_t)DEC_TE * Hd) * sizeof(float);   // 61 KB at Hd = 256
 }
 
-__global__ void __launch_bounds__(TAP_BLOCK) k_decoder_step(DecArgs a)
+struct DecArgsDrop : DecArgs {
+    DecDropArgs d;
+};
+
+// A = DecArgs: the plain step; A = DecArgsDrop: the dropout form (tapenv.h: tap_decoder_step_dropout), the two masks applied
+// where h' leaves the registers -- nothing else of the launch differs, and the plain instantiation has no trace of it
+template <typename A>
+__global__ void __launch_bounds__(TAP_BLOCK) k_decoder_step(A a)
 {
+    constexpr bool DROP = std::is_same<A, DecArgsDrop>::value;
     extern __shared__ float4 dec_lds4[];                                   // (float4: the 16-byte reads need the base aligned)
     float *lw = reinterpret_cast<float *>(dec_lds4), *xa = lw + DEC_WROWS * DEC_WS, *hl = xa + DEC_TE * DEC_KC;
     const int tid = threadIdx.x, lane = tid & 63, wave = TAP_WAVE_INDEX();
@@ -49,6 +64,13 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_decoder_step(DecArgs a)
     float *hn = hl + DEC_TE * Hd;
     const int e0 = (int)blockIdx.x * DEC_TE, ew = wave * DEC_E;            // the tile's first env; the wavefront's first env in the tile
     const bool have_h = a.h != nullptr;
+    unsigned seed_lo = 0, seed_hi = 0, episode = 0;
+    if constexpr (DROP) {
+        const unsigned long long seed = (unsigned long long)a.d.state[0];
+        seed_lo = (unsigned)seed;
+        seed_hi = (unsigned)(seed >> 32);
+        episode = (unsigned)(unsigned long long)a.d.state[1];
+    }
 
     // the tile's h rows (zeros for a null h and for the envs past the batch); the first block's barriers publish them
 #pragma unroll 4
@@ -94,9 +116,25 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_decoder_step(DecArgs a)
             const float r = dec_sigmoid(gi[0][e] + gh[0][e]), z = dec_sigmoid(gi[1][e] + gh[1][e]);
             const float n = tanhf(gi[2][e] + r * gh[2][e]);
             const float hv = (1.f - z) * n + z * hl[(ew + e) * Hd + j];
-            hn[(ew + e) * Hd + j] = hv;
+            float h_rnn = hv, h_hh = hv;
+            if constexpr (DROP) {
+                bool keep_rnn, keep_hh;
+                dec_keep(a.d, seed_lo, seed_hi, episode, b, j, keep_rnn, keep_hh);
+                h_rnn = keep_rnn ? hv * a.d.s_rnn : 0.f;
+                h_hh = keep_hh ? hv * a.d.s_hh : 0.f;
+                const unsigned long long w_rnn = __ballot(keep_rnn), w_hh = __ballot(keep_hh);   // the wavefront's 64 rows of env b
+                if (b < B) {
+                    if (lane == 0) {
+                        unsigned long long *kw = a.d.keep + (size_t)b * 2 * (Hd / 64) + jc;
+                        kw[0] = w_rnn;
+                        kw[Hd / 64] = w_hh;
+                    }
+                    if (a.d.rnn_out) a.d.rnn_out[(size_t)b * Hd + j] = h_rnn;
+                }
+            }
+            hn[(ew + e) * Hd + j] = h_rnn;
             if (b < B) {
-                a.h_out[(size_t)b * Hd + j] = hv;
+                a.h_out[(size_t)b * Hd + j] = h_hh;
                 if (a.gates_out) {
                     float *go = a.gates_out + (size_t)b * 4 * Hd + j;
                     go[0] = r;
@@ -146,7 +184,79 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_decoder_step_bw(const float *gate
     carry[i] = g * z;
 }
 
+// the same from a step that ran with dropout: last_hh = drop_hh(h') and rnn_out = drop_rnn(h') both hang on h', so the
+// gradient arriving at h' is g = keep_hh s_hh g_h + keep_rnn s_rnn g_r (g_r = g_q . wq, the caller's matmul), each product
+// and the sum rounded; a dropped element contributes an exact zero
+__global__ void __launch_bounds__(TAP_BLOCK) k_decoder_step_bw_drop(const float *gates, const float *h, const float *g_h, const float *g_r,
+                                                                    const unsigned long long *keep, float s_rnn, float s_hh, float *dgi,
+                                                                    float *dghn, float *carry, size_t total, int Hd)
+{
+    const size_t i = (size_t)blockIdx.x * TAP_BLOCK + threadIdx.x;
+    if (i >= total) return;
+    const size_t b = i / (size_t)Hd;
+    const int j = (int)(i - b * (size_t)Hd), nw = Hd >> 6;
+    const unsigned long long *kw = keep + b * 2 * (size_t)nw + (j >> 6);
+    const bool keep_rnn = (kw[0] >> (j & 63)) & 1, keep_hh = (kw[nw] >> (j & 63)) & 1;
+    const float *gp = gates + b * 4 * (size_t)Hd + j;
+    const float r = gp[0], z = gp[Hd], n = gp[2 * Hd], ghn = gp[3 * Hd];
+    const float g = (keep_hh ? s_hh * g_h[i] : 0.f) + (keep_rnn ? s_rnn * g_r[i] : 0.f), hp = h ? h[i] : 0.f;
+    const float dan = g * (1.f - z) * (1.f - n * n);
+    float *dp = dgi + b * 3 * (size_t)Hd + j;
+    dp[0] = dan * ghn * (r * (1.f - r));
+    dp[Hd] = g * (hp - n) * (z * (1.f - z));
+    dp[2 * Hd] = dan;
+    dghn[i] = dan * r;
+    carry[i] = g * z;
+}
+
 } // namespace
+
+extern "C" int tap_decoder_step_dropout(tap_ctx *ctx, const float *xs, int Ks, const float *xd, int Kd, const float *h, int B, int Hd,
+                                        const float *P, const float *c, const float *w_hh, const float *b_hh, const float *wq,
+                                        const int64_t *state, uint32_t step, uint32_t env_offset, uint32_t thr_rnn, uint32_t thr_hh,
+                                        float s_rnn, float s_hh, float *h_out, float *q_out, float *gates_out, float *rnn_out,
+                                        int64_t *keep_out, void *stream)
+{
+    if (B < 0 || Ks < 0 || Kd < 0 || Hd < 1) return tap_fail(ctx, TAP_E_INVALID, "decoder step (dropout): B %d, Ks %d, Kd %d, Hd %d", B, Ks, Kd, Hd);
+    if (B == 0) return TAP_OK; // an empty batch has no buffers to check
+    if ((Ks > 0 && !xs) || (Kd > 0 && !xd) || !P || !c || !w_hh || !b_hh || !wq || !h_out || !q_out || dec_drop_null(state, keep_out))
+        return tap_fail(ctx, TAP_E_INVALID, "decoder step (dropout): null buffer");
+    if (!dec_hd_ok(Hd) || Ks + Kd < 1 || Ks + Kd > Hd + 16)
+        return tap_fail(ctx, TAP_E_UNSUPPORTED, "decoder step (dropout): Ks %d, Kd %d, Hd %d (needs Hd 64, 128 or 256 and 1 <= Ks + Kd <= Hd + 16)", Ks, Kd,
+                        Hd);
+    const void *f32[] = {xs, xd, h, P, c, w_hh, b_hh, wq, h_out, q_out, gates_out, rnn_out};
+    bool bad = dec_drop_misaligned(state, keep_out);
+    for (const void *p : f32) bad = bad || dec_misaligned(p);
+    if (bad) return tap_fail(ctx, TAP_E_INVALID, "decoder step (dropout): every float buffer must be 4-byte aligned, state and keep_out 8-byte");
+    const DecArgsDrop a = {{xs, xd, h, P, c, w_hh, b_hh, wq, h_out, q_out, gates_out, B, Hd, Ks, Kd},
+                           {(const long long *)state, (unsigned long long *)keep_out, rnn_out, step, env_offset, thr_rnn, thr_hh, s_rnn, s_hh}};
+    const unsigned blocks = (unsigned)((B + DEC_TE - 1) / DEC_TE);
+    hipLaunchKernelGGL(k_decoder_step<DecArgsDrop>, dim3(blocks), dim3(TAP_BLOCK), dec_lds_bytes(Hd), (hipStream_t)stream, a);
+    TAP_LAUNCH_CHECK(ctx, "k_decoder_step<dropout>");
+    tap_variant_hit(ctx, TAP_HIT_DECODER, 0, DEC_TE, TapVariant{Hd / 64, h ? 1 : 0, 2}, 0);
+    return TAP_OK;
+}
+
+extern "C" int tap_decoder_step_dropout_backward(tap_ctx *ctx, int B, int Hd, const float *gates, const float *h, const float *g_h,
+                                                 const float *g_r, const int64_t *keep, float s_rnn, float s_hh, float *dgi_out,
+                                                 float *dghn_out, float *dh_carry_out, void *stream)
+{
+    if (B < 0 || Hd < 1) return tap_fail(ctx, TAP_E_INVALID, "decoder step backward (dropout): B %d, Hd %d", B, Hd);
+    if (B == 0) return TAP_OK; // (an empty batch leaves the outputs as they are)
+    if (!gates || !g_h || !g_r || !keep || !dgi_out || !dghn_out || !dh_carry_out)
+        return tap_fail(ctx, TAP_E_INVALID, "decoder step backward (dropout): null buffer");
+    if (!dec_hd_ok(Hd)) return tap_fail(ctx, TAP_E_UNSUPPORTED, "decoder step backward (dropout): Hd %d (needs 64, 128 or 256)", Hd);
+    const void *f32[] = {gates, h, g_h, g_r, dgi_out, dghn_out, dh_carry_out};
+    bool bad = ((uintptr_t)keep & 7) != 0;
+    for (const void *p : f32) bad = bad || dec_misaligned(p);
+    if (bad) return tap_fail(ctx, TAP_E_INVALID, "decoder step backward (dropout): every float buffer must be 4-byte aligned, keep 8-byte");
+    const size_t total = (size_t)B * Hd;
+    hipLaunchKernelGGL(k_decoder_step_bw_drop, dim3((unsigned)((total + TAP_BLOCK - 1) / TAP_BLOCK)), dim3(TAP_BLOCK), 0, (hipStream_t)stream,
+                       gates, h, g_h, g_r, (const unsigned long long *)keep, s_rnn, s_hh, dgi_out, dghn_out, dh_carry_out, total, Hd);
+    TAP_LAUNCH_CHECK(ctx, "k_decoder_step_bw_drop");
+    tap_variant_hit(ctx, TAP_HIT_DECODER, 0, DEC_TE, TapVariant{Hd / 64, h ? 1 : 0, 3}, 0);
+    return TAP_OK;
+}
 
 extern "C" int tap_decoder_step(tap_ctx *ctx, const float *xs, int Ks, const float *xd, int Kd, const float *h, int B, int Hd,
                                 const float *P, const float *c, const float *w_hh, const float *b_hh, const float *wq, float *h_out,
@@ -164,7 +274,7 @@ extern "C" int tap_decoder_step(tap_ctx *ctx, const float *xs, int Ks, const flo
     if (bad) return tap_fail(ctx, TAP_E_INVALID, "decoder step: every buffer must be 4-byte aligned");
     const DecArgs a = {xs, xd, h, P, c, w_hh, b_hh, wq, h_out, q_out, gates_out, B, Hd, Ks, Kd};
     const unsigned blocks = (unsigned)((B + DEC_TE - 1) / DEC_TE);
-    hipLaunchKernelGGL(k_decoder_step, dim3(blocks), dim3(TAP_BLOCK), dec_lds_bytes(Hd), (hipStream_t)stream, a);
+    hipLaunchKernelGGL(k_decoder_step<DecArgs>, dim3(blocks), dim3(TAP_BLOCK), dec_lds_bytes(Hd), (hipStream_t)stream, a);
     TAP_LAUNCH_CHECK(ctx, "k_decoder_step");
     tap_variant_hit(ctx, TAP_HIT_DECODER, 0, DEC_TE, TapVariant{Hd / 64, h ? 1 : 0, 0}, 0);
     return TAP_OK;

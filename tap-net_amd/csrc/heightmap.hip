@@ -21,6 +21,8 @@
 // Every sum is ONE chain of fmaf in ascending term order, the encoder's three from their biases; no atomics, no
 // cross-lane sums, nothing depends on the batch or the tile.  Backward: none here -- tap_decoder_step_backward from the
 // saved gates, and the encoder's gradients are the caller's (rollout.decoder_step_heightmap recomputes a1 / a2 in torch).
+// Dropout form (tapenv.h: tap_decoder_step_hm_dropout): decoder.hip's two masks at the same place, the encoder untouched;
+// the kernel is a template on its argument struct and the plain instantiation's listing is unchanged.
 #include "tap_decoder.h"
 
 namespace {
@@ -100,8 +102,16 @@ __device__ __forceinline__ void hm_conv3(const HmArgs &a, float *lw, const float
     }
 }
 
-__global__ void __launch_bounds__(TAP_BLOCK) k_decoder_step_hm(HmArgs a)
+struct HmArgsDrop : HmArgs {
+    DecDropArgs d;
+};
+
+// A = HmArgs: the plain step; A = HmArgsDrop: the dropout form (tapenv.h: tap_decoder_step_hm_dropout), decoder.hip's two
+// masks at the same place -- nothing else of the launch differs, and the plain instantiation has no trace of it
+template <typename A>
+__global__ void __launch_bounds__(TAP_BLOCK) k_decoder_step_hm(A a)
 {
+    constexpr bool DROP = std::is_same<A, HmArgsDrop>::value;
     extern __shared__ float4 hm_lds4[];                                    // (float4: the 16-byte reads need the base aligned)
     const int tid = threadIdx.x, lane = tid & 63, wave = TAP_WAVE_INDEX();
     const int B = a.B, Hd = a.Hd, Ks = a.Ks, m = a.m, Np = a.Np, K = a.Ks + a.m;
@@ -111,6 +121,13 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_decoder_step_hm(HmArgs a)
     float *a1 = r1, *enc = r1, *a2 = r2, *hl = r2, *hn = r2 + DEC_TE * Hd;
     const int e0 = (int)blockIdx.x * DEC_TE, ew = wave * DEC_E;            // the tile's first env; the wavefront's first env in the tile
     const bool have_h = a.h != nullptr;
+    unsigned seed_lo = 0, seed_hi = 0, episode = 0;
+    if constexpr (DROP) {
+        const unsigned long long seed = (unsigned long long)a.d.state[0];
+        seed_lo = (unsigned)seed;
+        seed_hi = (unsigned)(seed >> 32);
+        episode = (unsigned)(unsigned long long)a.d.state[1];
+    }
 
     // ---- the encoder stage --------------------------------------------------------------------------------------------
     // a1[e][p][o] = leaky(b1[o] + sum_c w1[o][c] hm[b][c][4i][4j]), p = i nl + j (zeros for the envs past the batch)
@@ -206,9 +223,25 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_decoder_step_hm(HmArgs a)
             const float r = dec_sigmoid(gi[0][e] + gh[0][e]), z = dec_sigmoid(gi[1][e] + gh[1][e]);
             const float n = tanhf(gi[2][e] + r * gh[2][e]);
             const float hv = (1.f - z) * n + z * hl[(ew + e) * Hd + j];
-            hn[(ew + e) * Hd + j] = hv;
+            float h_rnn = hv, h_hh = hv;
+            if constexpr (DROP) {
+                bool keep_rnn, keep_hh;
+                dec_keep(a.d, seed_lo, seed_hi, episode, b, j, keep_rnn, keep_hh);
+                h_rnn = keep_rnn ? hv * a.d.s_rnn : 0.f;
+                h_hh = keep_hh ? hv * a.d.s_hh : 0.f;
+                const unsigned long long w_rnn = __ballot(keep_rnn), w_hh = __ballot(keep_hh);   // the wavefront's 64 rows of env b
+                if (b < B) {
+                    if (lane == 0) {
+                        unsigned long long *kw = a.d.keep + (size_t)b * 2 * (Hd / 64) + jc;
+                        kw[0] = w_rnn;
+                        kw[Hd / 64] = w_hh;
+                    }
+                    if (a.d.rnn_out) a.d.rnn_out[(size_t)b * Hd + j] = h_rnn;
+                }
+            }
+            hn[(ew + e) * Hd + j] = h_rnn;
             if (b < B) {
-                a.h_out[(size_t)b * Hd + j] = hv;
+                a.h_out[(size_t)b * Hd + j] = h_hh;
                 if (a.gates_out) {
                     float *go = a.gates_out + (size_t)b * 4 * Hd + j;
                     go[0] = r;
@@ -265,9 +298,47 @@ extern "C" int tap_decoder_step_hm(tap_ctx *ctx, const float *xs, int Ks, const 
                         Np, Hd);
     const HmArgs a = {xs, hm, h, w1, b1, w2, b2, w3, b3, P, c, w_hh, b_hh, wq, h_out, q_out, gates_out, enc_out, B, Hd, Ks, m, C, W, L, nl, Np};
     const unsigned blocks = (unsigned)((B + DEC_TE - 1) / DEC_TE);
-    TAP_HIP_CHECK(ctx, tap_allow_lds(k_decoder_step_hm, lds));
-    hipLaunchKernelGGL(k_decoder_step_hm, dim3(blocks), dim3(TAP_BLOCK), lds, (hipStream_t)stream, a);
+    TAP_HIP_CHECK(ctx, tap_allow_lds(k_decoder_step_hm<HmArgs>, lds));
+    hipLaunchKernelGGL(k_decoder_step_hm<HmArgs>, dim3(blocks), dim3(TAP_BLOCK), lds, (hipStream_t)stream, a);
     TAP_LAUNCH_CHECK(ctx, "k_decoder_step_hm");
     tap_variant_hit(ctx, TAP_HIT_HEIGHTMAP, C, Np, TapVariant{Hd / 64, h ? 1 : 0, 0}, 0);
+    return TAP_OK;
+}
+
+extern "C" int tap_decoder_step_hm_dropout(tap_ctx *ctx, const float *xs, int Ks, const float *hm, int C, int W, int L, const float *h, int B,
+                                           int Hd, int m, const float *w1, const float *b1, const float *w2, const float *b2,
+                                           const float *w3, const float *b3, const float *P, const float *c, const float *w_hh,
+                                           const float *b_hh, const float *wq, const int64_t *state, uint32_t step, uint32_t env_offset,
+                                           uint32_t thr_rnn, uint32_t thr_hh, float s_rnn, float s_hh, float *h_out, float *q_out,
+                                           float *gates_out, float *enc_out, float *rnn_out, int64_t *keep_out, void *stream)
+{
+    if (B < 0 || Ks < 0 || C < 1 || W < 1 || L < 1 || Hd < 1 || m < 1)
+        return tap_fail(ctx, TAP_E_INVALID, "decoder step (height-map, dropout): B %d, Ks %d, C %d, W %d, L %d, Hd %d, m %d", B, Ks, C, W, L, Hd, m);
+    if (B == 0) return TAP_OK; // an empty batch has no buffers to check
+    if ((Ks > 0 && !xs) || !hm || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !P || !c || !w_hh || !b_hh || !wq || !h_out || !q_out ||
+        dec_drop_null(state, keep_out))
+        return tap_fail(ctx, TAP_E_INVALID, "decoder step (height-map, dropout): null buffer");
+    if (!dec_hd_ok(Hd) || (m != Hd && 2 * m != Hd) || (C != 1 && C != 2 && C != 4) || W > HM_MAX_SIDE || L > HM_MAX_SIDE || Ks > 16 ||
+        Ks + m > Hd + 16)
+        return tap_fail(ctx, TAP_E_UNSUPPORTED,
+                        "decoder step (height-map, dropout): Ks %d, C %d, W %d, L %d, m %d, Hd %d (needs Hd 64, 128 or 256, m = Hd / 2 or Hd, "
+                        "C 1, 2 or 4, W and L <= 12, Ks <= 16 and Ks + m <= Hd + 16)", Ks, C, W, L, m, Hd);
+    const void *f32[] = {xs, hm, h, w1, b1, w2, b2, w3, b3, P, c, w_hh, b_hh, wq, h_out, q_out, gates_out, enc_out, rnn_out};
+    bool bad = dec_drop_misaligned(state, keep_out);
+    for (const void *p : f32) bad = bad || dec_misaligned(p);
+    if (bad)
+        return tap_fail(ctx, TAP_E_INVALID, "decoder step (height-map, dropout): every float buffer must be 4-byte aligned, state and keep_out 8-byte");
+    const int nw = (W + 3) / 4, nl = (L + 3) / 4, Np = nw * nl;
+    const size_t lds = hm_lds_bytes(m, Np, Hd);
+    if (lds > tap_lds_limit(ctx))
+        return tap_fail(ctx, TAP_E_UNSUPPORTED, "decoder step (height-map, dropout): %zu bytes of LDS for m %d, Np %d, Hd %d do not fit a workgroup",
+                        lds, m, Np, Hd);
+    const HmArgsDrop a = {{xs, hm, h, w1, b1, w2, b2, w3, b3, P, c, w_hh, b_hh, wq, h_out, q_out, gates_out, enc_out, B, Hd, Ks, m, C, W, L, nl, Np},
+                          {(const long long *)state, (unsigned long long *)keep_out, rnn_out, step, env_offset, thr_rnn, thr_hh, s_rnn, s_hh}};
+    const unsigned blocks = (unsigned)((B + DEC_TE - 1) / DEC_TE);
+    TAP_HIP_CHECK(ctx, tap_allow_lds(k_decoder_step_hm<HmArgsDrop>, lds));
+    hipLaunchKernelGGL(k_decoder_step_hm<HmArgsDrop>, dim3(blocks), dim3(TAP_BLOCK), lds, (hipStream_t)stream, a);
+    TAP_LAUNCH_CHECK(ctx, "k_decoder_step_hm<dropout>");
+    tap_variant_hit(ctx, TAP_HIT_HEIGHTMAP, C, Np, TapVariant{Hd / 64, h ? 1 : 0, 2}, 0);
     return TAP_OK;
 }

@@ -5,7 +5,9 @@ The reference interleaves its pointer network with a per-env Python loop and two
 copies per step (model.py:407-465).  Here a step is two kernel launches on the current stream
 (precedence update, placement) and nothing leaves the device until the caller asks.
 """
+import collections
 import math
+import struct
 
 import torch
 
@@ -591,6 +593,185 @@ def _decoder_backward_into(gates, h, g, dgi, dghn, carry):
                                                     _lib.ptr(dghn), _lib.ptr(carry), _lib.stream_of(dev)), c_)
 
 
+# ---- dropout inside the decoder step's launch (tapenv.h: tap_decoder_step_dropout has the definition) -------------------
+_PHILOX_M = (0xD2511F53, 0xCD9E8D57)
+_PHILOX_W = (0x9E3779B9, 0xBB67AE85)
+_M32 = 0xFFFFFFFF
+
+StepDropoutRecord = collections.namedtuple("StepDropoutRecord", "state step p_rnn p_hh env_offset")
+StepDropoutRecord.__doc__ = """what a dropout step takes: ``state`` the int64[2] (seed, episode) tensor, ``step`` the decoding step
+(a Python int), the two probabilities and the index of the call's first env in the whole batch (``tools.StepDropout.take_step``)"""
+
+
+def dropout_threshold(p):
+    """keep iff word >= min(2^32 - 1, round(p 2^32))"""
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError("a dropout probability lies in [0, 1], got %r" % (p,))
+    return min(_M32, int(math.floor(p * 4294967296.0 + 0.5)))
+
+
+def dropout_scale(p):
+    """what a kept element is multiplied by: float32(1 / (1 - p)), as a Python float"""
+    return struct.unpack("f", struct.pack("f", 1.0 / (1.0 - float(p))))[0]
+
+
+def _mulhilo32(m, c):
+    """the 64-bit product of the constant m < 2^32 and an int64 tensor of values < 2^32 -> (high, low) 32-bit halves, in
+    int64 arithmetic that never passes 2^49"""
+    lo16 = m * (c & 0xFFFF)
+    t = m * (c >> 16) + (lo16 >> 16)
+    return t >> 16, ((t & 0xFFFF) << 16) | (lo16 & 0xFFFF)
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 in torch integer ops: ``counter`` four and ``key`` two int64 tensors (or ints) of values < 2^32, which
+    broadcast -> the four output words, int64 tensors of values < 2^32"""
+    c0, c1, c2, c3 = counter
+    k0, k1 = key
+    for _ in range(10):
+        hi0, lo0 = _mulhilo32(_PHILOX_M[0], c0)
+        hi1, lo1 = _mulhilo32(_PHILOX_M[1], c2)
+        c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+        k0, k1 = (k0 + _PHILOX_W[0]) & _M32, (k1 + _PHILOX_W[1]) & _M32
+    return c0, c1, c2, c3
+
+
+def dropout_keep_words(state, step, B, Hd, p_rnn, p_hh, env_offset=0):
+    """The two dropout masks of a decoding step, packed as the kernels write them: (B, 2, Hd / 64) int64 on ``state``'s
+    device, plane 0 drop_rnn, plane 1 drop_hh, bit j mod 64 of word j / 64 set iff hidden row j is kept.  ``state`` is the
+    int64[2] (seed, episode).  For env b and row j the Philox4x32-10 counter is (env_offset + b, j, step, episode mod 2^32)
+    and the key (seed mod 2^32, seed >> 32); output word 0 decides drop_rnn and word 1 drop_hh: keep iff word >=
+    ``dropout_threshold(p)``.  Torch integer ops only -- it runs on the CPU, and on the GPU it reads no value on the host,
+    so it can be captured in a graph with the ``state`` update in front of it."""
+    B, Hd = int(B), int(Hd)
+    if Hd < 64 or Hd % 64:
+        raise ValueError("the packed masks need Hd to be a multiple of 64, got %d" % Hd)
+    if state.dtype is not torch.int64 or tuple(state.shape) != (2,):
+        raise ValueError("state must be an int64[2] (seed, episode) tensor, got %s %s" % (state.dtype, tuple(state.shape)))
+    dev = state.device
+    seed, episode = state[0], state[1]
+    env = ((torch.arange(B, dtype=torch.int64, device=dev) + int(env_offset)) & _M32).view(B, 1)
+    row = torch.arange(Hd, dtype=torch.int64, device=dev).view(1, Hd)
+    zero = torch.zeros(B, Hd, dtype=torch.int64, device=dev)
+    w = philox4x32_10((env + zero, row + zero, zero + (int(step) & _M32), zero + (episode & _M32)), (seed & _M32, (seed >> 32) & _M32))
+    keep = torch.stack((w[0] >= dropout_threshold(p_rnn), w[1] >= dropout_threshold(p_hh)), dim=1)        # (B, 2, Hd)
+    bit = torch.arange(64, dtype=torch.int64, device=dev)
+    return (keep.view(B, 2, Hd // 64, 64).to(torch.int64) << bit).sum(-1)
+
+
+def dropout_keep_mask(words):
+    """packed keep words (B, 2, Hd / 64) -> bool (B, 2, Hd)"""
+    bit = torch.arange(64, dtype=torch.int64, device=words.device)
+    return ((words.unsqueeze(-1) >> bit) & 1).bool().view(int(words.shape[0]), 2, -1)
+
+
+def _dropout_record(dropout):
+    """-> a checked StepDropoutRecord from the record or a plain (state, step, p_rnn, p_hh[, env_offset]) tuple"""
+    d = StepDropoutRecord(*dropout) if len(dropout) == 5 else StepDropoutRecord(*dropout, 0)
+    if not torch.is_tensor(d.state) or d.state.dtype is not torch.int64 or tuple(d.state.shape) != (2,) or not d.state.is_contiguous():
+        raise ValueError("dropout state must be a contiguous int64[2] (seed, episode) tensor")
+    for p in (d.p_rnn, d.p_hh):
+        if not 0.0 <= float(p) < 1.0:
+            raise ValueError("the dropout launch takes 0 <= p < 1, got %r (p = 1 stays on the torch path)" % (p,))
+    if int(d.step) < 0 or int(d.env_offset) < 0:
+        raise ValueError("dropout step and env_offset must not be negative, got %r and %r" % (d.step, d.env_offset))
+    if not d.state.is_cuda:
+        raise ValueError("dropout state lives on %s: the launch reads it on the device (tools.StepDropout(seed, device))" % (d.state.device,))
+    return d
+
+
+def _dropout_state_on(drop, dev):
+    """the launch dereferences ``state``: it must live on the launch's own device.  It is refused, not copied -- a copy would
+    cut a captured graph off from the tensor that ``next_episode()`` advances"""
+    if drop.state.device != dev:
+        raise ValueError("dropout state lives on %s, the step's tensors on %s: the launch reads the state on its own device"
+                         % (drop.state.device, dev))
+    return drop
+
+
+def _drop_scalars(d):
+    """the launch arguments of a record: step, env_offset, the two thresholds, the two scales"""
+    return (int(d.step) & _M32, int(d.env_offset) & _M32, dropout_threshold(d.p_rnn), dropout_threshold(d.p_hh),
+            dropout_scale(d.p_rnn), dropout_scale(d.p_hh))
+
+
+def _decoder_dropout_into(xs, xd, h, P, c, w_hh, b_hh, wq, drop, h_out, q_out, gates, rnn_out, keep):
+    """tap_decoder_step_dropout on prepared buffers (as _decoder_into; ``drop`` a StepDropoutRecord whose state lives on the
+    device, rnn_out (B, Hd) or None, keep (B, 2, Hd / 64) int64): one launch on the current stream, nothing allocated"""
+    dev = P.device
+    _dropout_state_on(drop, dev)
+    c_ = _lib.ctx(dev)
+    B, Hd = int(h_out.shape[0]), int(h_out.shape[1])
+    Ks = 0 if xs is None else int(xs.shape[1])
+    Kd = 0 if xd is None else int(xd.shape[1])
+    p = _lib.ptr
+    _lib.check(_lib.lib().tap_decoder_step_dropout(c_, p(xs), Ks, p(xd), Kd, p(h), B, Hd, p(P), p(c), p(w_hh), p(b_hh), p(wq),
+                                                   p(drop.state), *_drop_scalars(drop), p(h_out), p(q_out), p(gates), p(rnn_out),
+                                                   p(keep), _lib.stream_of(dev)), c_)
+
+
+def _decoder_dropout_backward_into(gates, h, g_h, g_r, keep, s_rnn, s_hh, dgi, dghn, carry):
+    """tap_decoder_step_dropout_backward on prepared buffers: one launch on the current stream, nothing allocated"""
+    dev = gates.device
+    c_ = _lib.ctx(dev)
+    B, Hd = int(g_h.shape[0]), int(g_h.shape[1])
+    p = _lib.ptr
+    _lib.check(_lib.lib().tap_decoder_step_dropout_backward(c_, B, Hd, p(gates), p(h), p(g_h), p(g_r), p(keep), s_rnn, s_hh, p(dgi),
+                                                            p(dghn), p(carry), _lib.stream_of(dev)), c_)
+
+
+def _dropout_backward_launch(gates, h, g_h, g_q, wq, keep, scales):
+    """the element-wise part of a dropout step's backward -> g_q (float32), dgi, dgh, carry"""
+    B, Hd = int(gates.shape[0]), int(gates.shape[2])
+    dev = gates.device
+    g_q = _as_f32(g_q, dev)
+    dgi = torch.empty(B, 3 * Hd, dtype=torch.float32, device=dev)
+    dghn = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+    carry = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+    _decoder_dropout_backward_into(gates, h, _as_f32(g_h, dev), g_q.matmul(wq), keep, scales[0], scales[1], dgi, dghn, carry)
+    return g_q, dgi, torch.cat((dgi[:, :2 * Hd], dghn), dim=1), carry
+
+
+class _DecoderStepDropout(torch.autograd.Function):
+    """decoder_step(dropout=...) under autograd: forward = the dropout launch with gates, rnn_out = drop_rnn(h') and the keep
+    words kept; backward = tap_decoder_step_dropout_backward (element-wise: the two masks join g_h and g_q . wq at h') and
+    _DecoderStep's matmuls, with dwq = g_q^T . rnn_out.  The state tensor is NOT kept -- the masks are, so advancing the
+    episode cannot change a pending backward.  Inputs by reference, as _DecoderStep."""
+
+    @staticmethod
+    def forward(ctx, xs, xd, h, P, c, w_hh, b_hh, wq, drop):
+        B = int((xs if xs is not None else xd).shape[0])
+        Hd, dev = int(wq.shape[0]), P.device
+        h_new = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+        q = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+        gates = torch.empty(B, 4, Hd, dtype=torch.float32, device=dev)
+        rnn_out = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+        keep = torch.empty(B, 2, Hd // 64, dtype=torch.int64, device=dev)
+        _decoder_dropout_into(xs, xd, h, P, c, w_hh, b_hh, wq, drop, h_new, q, gates, rnn_out, keep)
+        ctx.save_for_backward(xs, xd, h, gates, rnn_out, keep, P, w_hh, wq)
+        ctx.scales = (dropout_scale(drop.p_rnn), dropout_scale(drop.p_hh))
+        return h_new, q
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_h, g_q):
+        xs, xd, h, gates, rnn_out, keep, P, w_hh, wq = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        g_q, dgi, dgh, carry = _dropout_backward_launch(gates, h, g_h, g_q, wq, keep, ctx.scales)
+        Ks = 0 if xs is None else int(xs.shape[1])
+        x = xd if xs is None else xs if xd is None else torch.cat((xs, xd), dim=1)
+        dxs = dgi.matmul(P[:, :Ks]) if xs is not None and need[0] else None
+        dxd = dgi.matmul(P[:, Ks:]) if xd is not None and need[1] else None
+        dh = carry + dgh.matmul(w_hh) if h is not None and need[2] else None
+        dP = dgi.t().matmul(x) if need[3] else None
+        dc = dgi.sum(0) if need[4] else None
+        dw_hh = (torch.zeros_like(w_hh) if h is None else dgh.t().matmul(h)) if need[5] else None
+        db_hh = dgh.sum(0) if need[6] else None
+        dwq = g_q.t().matmul(rnn_out) if need[7] else None
+        return dxs, dxd, dh, dP, dc, dw_hh, db_hh, dwq, None
+
+
 class _DecoderStep(torch.autograd.Function):
     """decoder_step under autograd: forward = the one launch with the gates kept, backward = tap_decoder_step_backward
     (element-wise) and the sums over the batch as matmuls.  What a step keeps: xs, xd and h BY REFERENCE (a stepper hands
@@ -635,6 +816,19 @@ class _DecoderStep(torch.autograd.Function):
         return dxs, dxd, dh, dP, dc, dw_hh, db_hh, dwq
 
 
+def decoder_step_dropout(xs, xd, h, P, c, w_hh, b_hh, wq, dropout):
+    """``decoder_step`` with the pointer's two dropouts (model.py:112-115) inside the same launch (tapenv.h:
+    tap_decoder_step_dropout) -> (drop_hh(h'), wq . drop_rnn(h')).  ``dropout`` = (state, step, p_rnn, p_hh, env_offset) -- a
+    ``StepDropoutRecord``, what ``tools.StepDropout.take_step`` hands out: the masks are ``dropout_keep_words`` for that
+    record, a kept element is scaled by float32(1 / (1 - p)), a dropped one is +0.0; 0 <= p < 1.  ``state`` is read on the
+    device: no host value, capturable, new masks on every replay that advances it.  Under autograd the backward is again
+    one element-wise launch (tap_decoder_step_dropout_backward) plus ``decoder_step``'s matmuls; per step it keeps, beside
+    ``gates``, drop_rnn(h') and the packed keep words (64 bytes per env at Hd = 256) -- not ``state``, so a later
+    ``next_episode()`` cannot change a pending backward.  Everything else as ``decoder_step``, whose signature stays the
+    reference-facing one."""
+    return _decoder_step(xs, xd, h, P, c, w_hh, b_hh, wq, dropout)
+
+
 def decoder_step(xs, xd, h, P, c, w_hh, b_hh, wq):
     """The decoder side of a decoding step (tapenv.h: tap_decoder_step; model.py:347-354, the GRU step of 108-115 and the
     decoder's columns of the attention) in ONE launch -> (h_new (B, Hd), q (B, Hd)) float32: the decoder's 1x1 encoders
@@ -648,7 +842,12 @@ def decoder_step(xs, xd, h, P, c, w_hh, b_hh, wq):
     input requiring grad the call runs through a ``torch.autograd.Function``: the backward is one element-wise launch
     (tap_decoder_step_backward) and torch matmuls for the sums over the batch; per step it keeps ``gates`` (B, 4, Hd) and
     h', and ``xs`` / ``xd`` / ``h`` by reference, so the caller must not overwrite them before ``backward()`` (a stepper's
-    grad-mode attributes are private copies).  A shape without a kernel (``decoder_step_supported``) raises ValueError."""
+    grad-mode attributes are private copies).  A shape without a kernel (``decoder_step_supported``) raises ValueError.
+    ``decoder_step_dropout`` is the training form with the pointer's dropouts inside the launch."""
+    return _decoder_step(xs, xd, h, P, c, w_hh, b_hh, wq, None)
+
+
+def _decoder_step(xs, xd, h, P, c, w_hh, b_hh, wq, dropout):
     if P.dim() != 2 or int(P.shape[0]) % 3 or not P.is_floating_point():
         raise ValueError("P must be a floating (3 Hd, Ks + Kd) tensor, got %s %s" % (P.dtype, tuple(P.shape)))
     Hd = int(P.shape[0]) // 3
@@ -670,7 +869,10 @@ def decoder_step(xs, xd, h, P, c, w_hh, b_hh, wq):
             raise ValueError("%s must be a floating %s tensor, got %s %s" % (name, shape, v.dtype, tuple(v.shape)))
     if not decoder_step_supported(Ks, Kd, Hd):
         raise ValueError("no decoder-step kernel for Ks %d, Kd %d, Hd %d (Hd 64 / 128 / 256, 1 <= Ks + Kd <= Hd + 16)" % (Ks, Kd, Hd))
+    drop = None if dropout is None else _dropout_record(dropout)
     dev = _lib.resolve_device(P.device)
+    if drop is not None:
+        _dropout_state_on(drop, dev)
 
     def prep(t):
         if t is None:
@@ -682,10 +884,14 @@ def decoder_step(xs, xd, h, P, c, w_hh, b_hh, wq):
         return t
     args = [prep(v) for v in (xs, xd, h, P, c, w_hh, b_hh, wq)]
     if torch.is_grad_enabled() and any(v is not None and v.requires_grad for v in args):
-        return _DecoderStep.apply(*args)
+        return _DecoderStep.apply(*args) if drop is None else _DecoderStepDropout.apply(*args, drop)
     h_new = torch.empty(B, Hd, dtype=torch.float32, device=dev)
     q = torch.empty(B, Hd, dtype=torch.float32, device=dev)
-    _decoder_into(*(None if v is None else v.detach() for v in args), h_new, q, None)
+    if drop is None:
+        _decoder_into(*(None if v is None else v.detach() for v in args), h_new, q, None)
+    else:
+        keep = torch.empty(B, 2, Hd // 64, dtype=torch.int64, device=dev)
+        _decoder_dropout_into(*(None if v is None else v.detach() for v in args), drop, h_new, q, None, None, keep)
     return h_new, q
 
 
@@ -755,29 +961,99 @@ class _DecoderStepHeightmap(torch.autograd.Function):
         dw_hh = (torch.zeros_like(w_hh) if h is None else dgh.t().matmul(h)) if need[11] else None
         db_hh = dgh.sum(0) if need[12] else None
         dwq = g_q.t().matmul(h_new) if need[13] else None
-        dhm = dw1 = db1 = dw2 = db2 = dw3 = db3 = None
-        if need[1] or any(need[3:9]):
-            d_enc = dgi.matmul(P[:, Ks:])                             # (B, m)
-            cells = hm[:, :, ::4, ::4]                                # (B, C, nw, nl)
-            C, nw, nl = (int(v) for v in cells.shape[1:])
-            Np, C1, C2 = nw * nl, int(w1.shape[0]), int(w2.shape[0])
-            cells = cells.reshape(B, C, Np).transpose(1, 2)           # (B, Np, C)
-            z1 = cells.matmul(w1.t()) + b1
-            a1 = z1 * _leaky_slope(z1)                                # (B, Np, C1)
-            z2 = a1.matmul(w2.t()) + b2
-            a2 = z2 * _leaky_slope(z2)                                # (B, Np, C2); conv3 reads it as t = c2 Np + p
-            dw3 = d_enc.t().matmul(a2.transpose(1, 2).reshape(B, C2 * Np)) if need[7] else None
-            db3 = d_enc.sum(0) if need[8] else None
-            dz2 = d_enc.matmul(w3).view(B, C2, Np).transpose(1, 2) * _leaky_slope(z2)
-            dw2 = dz2.reshape(B * Np, C2).t().matmul(a1.reshape(B * Np, C1)) if need[5] else None
-            db2 = dz2.sum((0, 1)) if need[6] else None
-            dz1 = dz2.matmul(w2) * _leaky_slope(z1)
-            dw1 = dz1.reshape(B * Np, C1).t().matmul(cells.reshape(B * Np, C)) if need[3] else None
-            db1 = dz1.sum((0, 1)) if need[4] else None
-            if need[1]:
-                dhm = torch.zeros_like(hm)
-                dhm[:, :, ::4, ::4] = dz1.matmul(w1).transpose(1, 2).reshape(B, C, nw, nl)
+        dhm, dw1, db1, dw2, db2, dw3, db3 = _heightmap_encoder_backward(need, dgi, P, Ks, hm, w1, b1, w2, b2, w3)
         return dxs, dhm, dh, dw1, db1, dw2, db2, dw3, db3, dP, dc, dw_hh, db_hh, dwq
+
+
+def _heightmap_encoder_backward(need, dgi, P, Ks, hm, w1, b1, w2, b2, w3):
+    """the encoder's half of a height-map step's backward, from dgi (B, 3 Hd): d_enc = dgi . P[:, Ks:], then the two hidden
+    layers recomputed in torch on the gathered cells -> dhm, dw1, db1, dw2, db2, dw3, db3 (None where ``need``, the
+    Function's needs_input_grad, does not ask)"""
+    dhm = dw1 = db1 = dw2 = db2 = dw3 = db3 = None
+    if need[1] or any(need[3:9]):
+        B = int(hm.shape[0])
+        d_enc = dgi.matmul(P[:, Ks:])                             # (B, m)
+        cells = hm[:, :, ::4, ::4]                                # (B, C, nw, nl)
+        C, nw, nl = (int(v) for v in cells.shape[1:])
+        Np, C1, C2 = nw * nl, int(w1.shape[0]), int(w2.shape[0])
+        cells = cells.reshape(B, C, Np).transpose(1, 2)           # (B, Np, C)
+        z1 = cells.matmul(w1.t()) + b1
+        a1 = z1 * _leaky_slope(z1)                                # (B, Np, C1)
+        z2 = a1.matmul(w2.t()) + b2
+        a2 = z2 * _leaky_slope(z2)                                # (B, Np, C2); conv3 reads it as t = c2 Np + p
+        dw3 = d_enc.t().matmul(a2.transpose(1, 2).reshape(B, C2 * Np)) if need[7] else None
+        db3 = d_enc.sum(0) if need[8] else None
+        dz2 = d_enc.matmul(w3).view(B, C2, Np).transpose(1, 2) * _leaky_slope(z2)
+        dw2 = dz2.reshape(B * Np, C2).t().matmul(a1.reshape(B * Np, C1)) if need[5] else None
+        db2 = dz2.sum((0, 1)) if need[6] else None
+        dz1 = dz2.matmul(w2) * _leaky_slope(z1)
+        dw1 = dz1.reshape(B * Np, C1).t().matmul(cells.reshape(B * Np, C)) if need[3] else None
+        db1 = dz1.sum((0, 1)) if need[4] else None
+        if need[1]:
+            dhm = torch.zeros_like(hm)
+            dhm[:, :, ::4, ::4] = dz1.matmul(w1).transpose(1, 2).reshape(B, C, nw, nl)
+    return dhm, dw1, db1, dw2, db2, dw3, db3
+
+
+def _decoder_hm_dropout_into(xs, hm, h, enc_w, P, c, w_hh, b_hh, wq, drop, h_out, q_out, gates, enc_out, rnn_out, keep):
+    """tap_decoder_step_hm_dropout on prepared buffers (as _decoder_hm_into and _decoder_dropout_into): one launch on the
+    current stream, nothing allocated"""
+    dev = P.device
+    _dropout_state_on(drop, dev)
+    c_ = _lib.ctx(dev)
+    B, Hd = int(h_out.shape[0]), int(h_out.shape[1])
+    Ks = 0 if xs is None else int(xs.shape[1])
+    C, W, L = (int(v) for v in hm.shape[1:])
+    p = _lib.ptr
+    _lib.check(_lib.lib().tap_decoder_step_hm_dropout(c_, p(xs), Ks, p(hm), C, W, L, p(h), B, Hd, int(enc_w[4].shape[0]),
+                                                      *(p(w) for w in enc_w), p(P), p(c), p(w_hh), p(b_hh), p(wq), p(drop.state),
+                                                      *_drop_scalars(drop), p(h_out), p(q_out), p(gates), p(enc_out), p(rnn_out),
+                                                      p(keep), _lib.stream_of(dev)), c_)
+
+
+class _DecoderStepHeightmapDropout(torch.autograd.Function):
+    """decoder_step_heightmap(dropout=...) under autograd: _DecoderStepHeightmap with _DecoderStepDropout's changes -- the
+    dropout launch forward, rnn_out and the keep words kept, the dropout form of the element-wise backward launch, dwq from
+    rnn_out.  The encoder's backward is unchanged: it receives dgi as before."""
+
+    @staticmethod
+    def forward(ctx, xs, hm, h, w1, b1, w2, b2, w3, b3, P, c, w_hh, b_hh, wq, drop):
+        B, Hd, dev = int(hm.shape[0]), int(wq.shape[0]), P.device
+        h_new = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+        q = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+        gates = torch.empty(B, 4, Hd, dtype=torch.float32, device=dev)
+        enc = torch.empty(B, int(w3.shape[0]), dtype=torch.float32, device=dev)
+        rnn_out = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+        keep = torch.empty(B, 2, Hd // 64, dtype=torch.int64, device=dev)
+        _decoder_hm_dropout_into(xs, hm, h, (w1, b1, w2, b2, w3, b3), P, c, w_hh, b_hh, wq, drop, h_new, q, gates, enc, rnn_out, keep)
+        ctx.save_for_backward(xs, hm, h, gates, enc, rnn_out, keep, w1, b1, w2, b2, w3, P, w_hh, wq)
+        ctx.scales = (dropout_scale(drop.p_rnn), dropout_scale(drop.p_hh))
+        return h_new, q
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_h, g_q):
+        xs, hm, h, gates, enc, rnn_out, keep, w1, b1, w2, b2, w3, P, w_hh, wq = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        g_q, dgi, dgh, carry = _dropout_backward_launch(gates, h, g_h, g_q, wq, keep, ctx.scales)
+        Ks = 0 if xs is None else int(xs.shape[1])
+        x = enc if xs is None else torch.cat((xs, enc), dim=1)
+        dxs = dgi.matmul(P[:, :Ks]) if xs is not None and need[0] else None
+        dh = carry + dgh.matmul(w_hh) if h is not None and need[2] else None
+        dP = dgi.t().matmul(x) if need[9] else None
+        dc = dgi.sum(0) if need[10] else None
+        dw_hh = (torch.zeros_like(w_hh) if h is None else dgh.t().matmul(h)) if need[11] else None
+        db_hh = dgh.sum(0) if need[12] else None
+        dwq = g_q.t().matmul(rnn_out) if need[13] else None
+        dhm, dw1, db1, dw2, db2, dw3, db3 = _heightmap_encoder_backward(need, dgi, P, Ks, hm, w1, b1, w2, b2, w3)
+        return dxs, dhm, dh, dw1, db1, dw2, db2, dw3, db3, dP, dc, dw_hh, db_hh, dwq, None
+
+
+def decoder_step_heightmap_dropout(xs, hm, h, encoder, P, c, w_hh, b_hh, wq, dropout):
+    """``decoder_step_heightmap`` with the pointer's two dropouts inside the same launch (tapenv.h:
+    tap_decoder_step_hm_dropout) -> (drop_hh(h'), wq . drop_rnn(h')); ``dropout`` and what a step keeps as
+    ``decoder_step_dropout``.  The encoder stage and its backward are untouched: the backward receives dgi as before."""
+    return _decoder_step_heightmap(xs, hm, h, encoder, P, c, w_hh, b_hh, wq, dropout)
 
 
 def decoder_step_heightmap(xs, hm, h, encoder, P, c, w_hh, b_hh, wq):
@@ -793,7 +1069,11 @@ def decoder_step_heightmap(xs, hm, h, encoder, P, c, w_hh, b_hh, wq):
     tap_decoder_step_backward and ``decoder_step``'s matmuls, and gets the encoder's six parameter gradients -- and ``hm``'s,
     scattered back to the cells (4i, 4j) -- from d_enc by recomputing the two hidden layers in torch; per step it keeps
     ``gates``, h' and enc, and the inputs by reference.  A shape without a kernel
-    (``decoder_step_heightmap_supported``) raises ValueError."""
+    (``decoder_step_heightmap_supported``) raises ValueError.  ``decoder_step_heightmap_dropout`` is the training form."""
+    return _decoder_step_heightmap(xs, hm, h, encoder, P, c, w_hh, b_hh, wq, None)
+
+
+def _decoder_step_heightmap(xs, hm, h, encoder, P, c, w_hh, b_hh, wq, dropout):
     if P.dim() != 2 or int(P.shape[0]) % 3 or not P.is_floating_point():
         raise ValueError("P must be a floating (3 Hd, Ks + m) tensor, got %s %s" % (P.dtype, tuple(P.shape)))
     Hd = int(P.shape[0]) // 3
@@ -824,7 +1104,10 @@ def decoder_step_heightmap(xs, hm, h, encoder, P, c, w_hh, b_hh, wq):
     if not decoder_step_heightmap_supported(Ks, C, W, L, m, Hd):
         raise ValueError("no height-map decoder-step kernel for Ks %d, C %d, W %d, L %d, m %d, Hd %d (Hd 64 / 128 / 256, m = Hd / 2 or Hd, "
                          "C 1 / 2 / 4, W and L <= 12, Ks <= 16, Ks + m <= Hd + 16)" % (Ks, C, W, L, m, Hd))
+    drop = None if dropout is None else _dropout_record(dropout)
     dev = _lib.resolve_device(P.device)
+    if drop is not None:
+        _dropout_state_on(drop, dev)
 
     def prep(t):
         if t is None:
@@ -838,11 +1121,15 @@ def decoder_step_heightmap(xs, hm, h, encoder, P, c, w_hh, b_hh, wq):
              convs[2].weight.reshape(m, (m // 2) * nw * nl), convs[2].bias)
     args = [prep(v) for v in (xs, hm, h) + enc_w + (P, c, w_hh, b_hh, wq)]
     if torch.is_grad_enabled() and any(v is not None and v.requires_grad for v in args):
-        return _DecoderStepHeightmap.apply(*args)
+        return _DecoderStepHeightmap.apply(*args) if drop is None else _DecoderStepHeightmapDropout.apply(*args, drop)
     h_new = torch.empty(B, Hd, dtype=torch.float32, device=dev)
     q = torch.empty(B, Hd, dtype=torch.float32, device=dev)
     d = [None if v is None else v.detach() for v in args]
-    _decoder_hm_into(d[0], d[1], d[2], tuple(d[3:9]), *d[9:], h_new, q, None, None)
+    if drop is None:
+        _decoder_hm_into(d[0], d[1], d[2], tuple(d[3:9]), *d[9:], h_new, q, None, None)
+    else:
+        keep = torch.empty(B, 2, Hd // 64, dtype=torch.int64, device=dev)
+        _decoder_hm_dropout_into(d[0], d[1], d[2], tuple(d[3:9]), *d[9:], drop, h_new, q, None, None, None, keep)
     return h_new, q
 
 

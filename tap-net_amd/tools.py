@@ -166,7 +166,11 @@ class Pointer(nn.Module):
     the decoder's 1x1 encoders folded into the GRU's input weights, and everything else of a step that depends on the
     parameters alone (M, k, Wq).  ``forward_step(proj, bits, fold, decoder_static, decoder_dynamic, last_hh)`` -> (logits,
     last_hh) is then TWO launches: ``rollout.decoder_step`` (input product, GRU cell and q; with a ``HeightmapEncoder`` as the
-    dynamic decoder ``rollout.decoder_step_heightmap``, which runs that encoder too) and ``rollout.pointer_scores``."""
+    dynamic decoder ``rollout.decoder_step_heightmap``, which runs that encoder too) and ``rollout.pointer_scores``.
+
+    ``forward_step_dropout(..., last_hh, dropout)`` and ``forward_bits_dropout(..., last_hh, dropout)`` are the training
+    forms: ``dropout`` is a ``StepDropout``, whose counter-based masks replace torch's generator -- inside the first launch
+    where there is one, through ``rollout.dropout_keep_words`` on the torch path."""
 
     def __init__(self, encoder_hidden_size, decoder_hidden_size, decoder_input_type, input_type, num_layers=1, dropout=0.2):
         super(Pointer, self).__init__()
@@ -183,16 +187,47 @@ class Pointer(nn.Module):
         self.drop_rnn = nn.Dropout(p=dropout)
         self.drop_hh = nn.Dropout(p=dropout)
 
-    def _gru_step(self, decoder_hidden, last_hh):
-        """model.py:108-115: the GRU step and the two dropouts -> rnn_out (B, Hd), last_hh"""
+    def _gru_step(self, decoder_hidden, last_hh, keep=None):
+        """model.py:108-115: the GRU step and the two dropouts -> rnn_out (B, Hd), last_hh.  ``keep``: packed keep words
+        (B, 2, Hd / 64) int64 (``rollout.dropout_keep_words``) -- those masks are applied instead of ``drop_rnn`` / ``drop_hh``:
+        a kept element is x s with s = float32(1 / (1 - p)), a dropped one 0, in the dtype of x.  With one layer torch's
+        generator is not touched; with more, ``nn.GRU``'s own inter-layer dropout still draws from it, and plane 1 is unused
+        (``drop_hh`` is not applied there, as without ``keep``)."""
         rnn_out, last_hh = self.gru(decoder_hidden.transpose(2, 1), last_hh)
-        rnn_out = self.drop_rnn(rnn_out.squeeze(1))
+        rnn_out = rnn_out.squeeze(1)
+        if keep is None:
+            rnn_out = self.drop_rnn(rnn_out)
+            if self.num_layers == 1:
+                last_hh = self.drop_hh(last_hh)     # with more layers the GRU has applied it
+            return rnn_out, last_hh
+        from .rollout import dropout_keep_mask, dropout_scale
+
+        def masked(x, kept, p):
+            return torch.zeros_like(x) if p >= 1 else torch.where(kept, x * dropout_scale(p), torch.zeros_like(x))
+        mask = dropout_keep_mask(keep.to(rnn_out.device))
+        rnn_out = masked(rnn_out, mask[:, 0], self.drop_rnn.p)
         if self.num_layers == 1:
-            last_hh = self.drop_hh(last_hh)         # with more layers the GRU has applied it
+            last_hh = masked(last_hh, mask[:, 1].unsqueeze(0), self.drop_hh.p)
         return rnn_out, last_hh
 
+    def _step_dropout(self, dropout):
+        """-> the record of the next step of a ``StepDropout`` (or the record itself, when ``forward_step`` has taken it) in
+        training mode, else None: in ``eval()`` the keyword is ignored and the step counter stays where it is"""
+        if dropout is None or not self.training:
+            return None
+        return dropout.take_step(self.drop_rnn.p, self.drop_hh.p) if hasattr(dropout, "take_step") else dropout
+
+    def _keep_words(self, rec, B):
+        """the torch path's masks for a record: the same words the dropout launch would write"""
+        from .rollout import dropout_keep_words
+        return None if rec is None else dropout_keep_words(rec.state, rec.step, B, self.decoder_hidden_size, rec.p_rnn, rec.p_hh,
+                                                           rec.env_offset)
+
     def forward(self, static_hidden, dynamic_hidden, decoder_hidden, last_hh):
-        rnn_out, last_hh = self._gru_step(decoder_hidden, last_hh)
+        return self._forward(static_hidden, dynamic_hidden, decoder_hidden, last_hh)
+
+    def _forward(self, static_hidden, dynamic_hidden, decoder_hidden, last_hh, keep=None):
+        rnn_out, last_hh = self._gru_step(decoder_hidden, last_hh, keep)
         B, nR = static_hidden.size(0), static_hidden.shape[-1]
         encoder_hidden = torch.cat((static_hidden, dynamic_hidden), 1)
         # Attention.forward (model.py:55-74)
@@ -224,16 +259,26 @@ class Pointer(nn.Module):
         return proj
 
     def forward_bits(self, proj, bits, dynamic_encoder, decoder_hidden, last_hh):
+        return self._forward_bits(proj, bits, dynamic_encoder, decoder_hidden, last_hh, None)
+
+    def forward_bits_dropout(self, proj, bits, dynamic_encoder, decoder_hidden, last_hh, dropout):
+        """``forward_bits`` with a ``StepDropout`` as the random source: in training mode the GRU step takes the masks of its
+        next record (``rollout.dropout_keep_words``) instead of torch's generator -- the masks ``forward_step_dropout``'s
+        launch applies for the same (state, step).  In ``eval()`` it is ``forward_bits`` and the step counter stays."""
+        return self._forward_bits(proj, bits, dynamic_encoder, decoder_hidden, last_hh, dropout)
+
+    def _forward_bits(self, proj, bits, dynamic_encoder, decoder_hidden, last_hh, dropout):
         from .rollout import pointer_scores, pointer_scores_supported
         conv = dynamic_encoder.conv
         rows, nR, Hd = int(conv.weight.shape[1]), int(proj.shape[2]), self.decoder_hidden_size
+        keep = self._keep_words(self._step_dropout(dropout), int(decoder_hidden.shape[0]))
         if not pointer_scores_supported(rows, nR, Hd):
             static_hidden = getattr(proj, "static_hidden", None)
             if static_hidden is None:
                 raise ValueError("no pointer kernel for rows %d, nR %d, Hd %d, and proj does not come from project_static: "
                                  "call forward(static_hidden, dynamic_encoder(bits), ...)" % (rows, nR, Hd))
-            return self.forward(static_hidden, dynamic_encoder(bits), decoder_hidden, last_hh)
-        rnn_out, last_hh = self._gru_step(decoder_hidden, last_hh)
+            return self._forward(static_hidden, dynamic_encoder(bits), decoder_hidden, last_hh, keep)
+        rnn_out, last_hh = self._gru_step(decoder_hidden, last_hh, keep)
         _, Wd, Wq = self.folded_weights()
         M = Wd.matmul(conv.weight[:, :, 0])
         k = Wd.matmul(conv.bias) if conv.bias is not None else torch.zeros_like(Wd[:, 0])
@@ -335,13 +380,35 @@ class Pointer(nn.Module):
         launch is ``rollout.decoder_step_heightmap`` -- the encoder runs inside it -- and ``decoder_dynamic`` is the stepper's 4-D
         (B, C, W, L) feature, which the torch path hands to the encoder as it is.  The torch path -- ``_gru_step`` on the unfolded decoder_hidden, then what
         ``forward_bits`` does: today's result -- runs instead when dropout would be active (training with p > 0), with more
-        than one GRU layer, with a GRU without bias, off the GPU, or on a shape without a kernel for either launch."""
-        from .rollout import (decoder_step, decoder_step_heightmap, decoder_step_heightmap_supported, decoder_step_supported,
-                              pointer_scores, pointer_scores_supported)
+        than one GRU layer, with a GRU without bias, off the GPU, or on a shape without a kernel for either launch.
+        ``forward_step_dropout`` keeps a training step with dropout on the two launches."""
+        return self._forward_step(proj, bits, fold, decoder_static, decoder_dynamic, last_hh, None)
+
+    def forward_step_dropout(self, proj, bits, fold, decoder_static, decoder_dynamic, last_hh, dropout):
+        """``forward_step`` for training with dropout: ``dropout`` is a ``StepDropout``.  In training mode the step takes its
+        next record; ``drop_rnn.p`` / ``drop_hh.p`` are read at the call, and the two masks run INSIDE the first launch
+        (``rollout.decoder_step_dropout`` / ``decoder_step_heightmap_dropout``): last_hh = drop_hh(h'), q from drop_rnn(h').
+        Wherever the torch path is still taken -- off the GPU, several GRU layers, a GRU without bias, a shape without a kernel,
+        p = 1 -- it applies ``rollout.dropout_keep_words`` for the same record, so both paths are the same function of the same
+        masks, and with one GRU layer torch's generator is never touched.  With ``num_layers > 1`` only ``drop_rnn`` takes the
+        record's mask: ``nn.GRU`` applies its own dropout between the layers and to nothing after the last, from torch's
+        generator, and ``drop_hh`` is not applied, as in ``forward``.  A ``StepDropout`` whose state is not on the device of
+        ``bits`` raises ValueError.  In ``eval()`` it is ``forward_step`` and the step counter stays."""
+        return self._forward_step(proj, bits, fold, decoder_static, decoder_dynamic, last_hh, dropout)
+
+    def _forward_step(self, proj, bits, fold, decoder_static, decoder_dynamic, last_hh, dropout):
+        from .rollout import (decoder_step_heightmap_supported, decoder_step_supported, pointer_scores, pointer_scores_supported,
+                              _decoder_step, _decoder_step_heightmap)
         Hd, nR = self.decoder_hidden_size, int(proj.shape[2])
         Ks = 0 if decoder_static is None or fold.static_decoder is None else int(decoder_static[0].numel())
         Kd = 0 if decoder_dynamic is None or (fold.dynamic_decoder is None and not fold.identity_dynamic) else int(decoder_dynamic[0].numel())
-        dropping = self.training and (self.drop_rnn.p > 0 or self.drop_hh.p > 0)
+        rec = self._step_dropout(dropout)
+        if rec is not None and bits.is_cuda and rec.state.device != bits.device:
+            # the launch would dereference the state on its own device; a copy would cut a captured graph off from it
+            raise ValueError("the StepDropout's state lives on %s, the step's tensors on %s: build it with StepDropout(seed, %r)"
+                             % (rec.state.device, bits.device, str(bits.device)))
+        # without a record active dropout is torch's own and stays on the torch path; with one only p = 1 does
+        dropping = self.training and ((self.drop_rnn.p > 0 or self.drop_hh.p > 0) if rec is None else max(rec.p_rnn, rec.p_hh) >= 1)
         hm = fold.heightmap
         if hm is not None:
             m = int(hm.conv3.weight.shape[0])
@@ -354,13 +421,13 @@ class Pointer(nn.Module):
         if dropping or self.num_layers != 1 or not self.gru.bias or not bits.is_cuda or not launch or \
                 not pointer_scores_supported(fold.rows, nR, Hd):
             decoder_hidden = self._decoder_hidden(fold, decoder_static, decoder_dynamic)
-            return self.forward_bits(proj, bits, fold.dynamic_encoder, decoder_hidden, last_hh)
+            return self._forward_bits(proj, bits, fold.dynamic_encoder, decoder_hidden, last_hh, rec)
         if hm is not None:
-            h_new, q = decoder_step_heightmap(decoder_static if Ks else None, decoder_dynamic, None if last_hh is None else last_hh[0],
-                                              hm, fold.P, fold.c, fold.w_hh, fold.b_hh, fold.Wq)
+            h_new, q = _decoder_step_heightmap(decoder_static if Ks else None, decoder_dynamic, None if last_hh is None else last_hh[0],
+                                               hm, fold.P, fold.c, fold.w_hh, fold.b_hh, fold.Wq, rec)
         else:
-            h_new, q = decoder_step(decoder_static if Ks else None, decoder_dynamic if Kd else None,
-                                    None if last_hh is None else last_hh[0], fold.P, fold.c, fold.w_hh, fold.b_hh, fold.Wq)
+            h_new, q = _decoder_step(decoder_static if Ks else None, decoder_dynamic if Kd else None,
+                                     None if last_hh is None else last_hh[0], fold.P, fold.c, fold.w_hh, fold.b_hh, fold.Wq, rec)
         logits = pointer_scores(proj, bits, fold.M, fold.k, q, fold.va, fold.vp, rows=fold.rows)
         return logits, h_new.unsqueeze(0)
 
@@ -497,6 +564,37 @@ class StepFold(object):
     ``heightmap`` is the dynamic decoder when it is a ``HeightmapEncoder`` (it runs inside the step's launch), else None."""
     __slots__ = ("dynamic_encoder", "rows", "M", "k", "P", "c", "Wq", "va", "vp", "w_ih", "w_hh", "b_ih", "b_hh",
                  "static_decoder", "dynamic_decoder", "combine", "identity_dynamic", "heightmap")
+
+
+class StepDropout(object):
+    """The random source of the pointer's two dropouts when they run inside the decoder step's launch
+    (``Pointer.forward_step_dropout``; tapenv.h: tap_decoder_step_dropout has the definition): a counter-based generator keyed
+    on (seed, episode, step, env, hidden row), so a step's masks are the same bytes wherever they are computed.  ``state`` is
+    an int64[2] (seed, episode) ON ``device`` -- the launches read it there --, ``step`` a Python counter that becomes a
+    launch argument.  ``env_offset``: the index of this batch's first env in the whole batch, so the shards of a
+    data-parallel run draw disjoint masks from one seed (rank r of equal shards of B envs: ``env_offset = r * B``).
+
+    ``next_episode()`` adds one to the episode as a torch op and resets ``step``: captured at the head of an episode's
+    graph, it makes every replay draw new masks.  ``take_step(p_rnn, p_hh)`` -> the ``rollout.StepDropoutRecord`` of the
+    next step, and advances ``step``."""
+
+    def __init__(self, seed, device, env_offset=0):
+        seed, env_offset = int(seed), int(env_offset)
+        if not 0 <= seed < 1 << 63 or env_offset < 0:
+            raise ValueError("seed must lie in [0, 2^63) and env_offset must not be negative, got %d and %d" % (seed, env_offset))
+        self.state = torch.tensor([seed, 0], dtype=torch.int64, device=device)
+        self.env_offset = env_offset
+        self.step = 0
+
+    def next_episode(self):
+        self.state[1] += 1
+        self.step = 0
+
+    def take_step(self, p_rnn=0.0, p_hh=0.0):
+        from .rollout import StepDropoutRecord
+        rec = StepDropoutRecord(self.state, self.step, float(p_rnn), float(p_hh), self.env_offset)
+        self.step += 1
+        return rec
 
 
 class _EngineRow(object):
