@@ -126,6 +126,7 @@ const char *tap_last_error(const tap_ctx *ctx);
  *      k_encode_bits_bw_partial + _reduce         (27, 0, 0, PLANES, BIAS, 1, 0) BIAS 1 = dbias wanted (one count per call)
  *   28 k_pointer_scores<HPL>                      (28, 0, HPL, PLANES, CHUNKS, 0, 0) CHUNKS = Hd / (64 HPL) hidden chunks per segment
  *      k_pointer_scores_bw<HPL> + _bw_reduce      (28, 0, HPL, PLANES, CHUNKS, 1, 0) (one count per call)
+ *      k_pointer_scores<HPL, SS> / _bw<HPL, SS>   (28, 0, HPL, PLANES, CHUNKS, 0 | 1, S) the static-rows form, S = 1 .. 8 static rows (SS = S for 2, 3, 4, else 0)
  *   29 k_decoder_step                             (29, 0, TE, CHUNKS, H, 0, 0) TE = 16 envs per workgroup, CHUNKS = Hd / 64, H 1 = h given
  *      k_decoder_step_bw                          (29, 0, TE, CHUNKS, H, 1, 0)
  *   30 k_decoder_step_hm                          (30, C, NP, CHUNKS, H, 0, 0)   C height-map planes, NP = ceil(W / 4) ceil(L / 4) positions read
@@ -697,6 +698,46 @@ int tap_pointer_scores_backward(tap_ctx *ctx, const float *proj, const unsigned 
                                 float *dva_out, float *dvp_out, void *scratch, size_t scratch_bytes, void *stream);
 /* bytes of scratch the backward needs for this shape (0 for a shape the entry refuses) */
 size_t tap_pointer_scores_backward_scratch(int B, int nR, int rows, int Hd);
+
+/* tap_pointer_scores with the static term of U computed from the S rows of `static` that the static encoder sees, in
+ * place of proj: static_hidden = Es . xs + bs is a 1x1 convolution, so with G = Ws . Es (3 Hd, S) and g = Ws . bs (3 Hd,),
+ * prepared by the caller in differentiable host code from the parameters alone, per env b, column c and hidden row x in
+ * fp32:
+ *   P[x, c]   = g[x], then fmaf(G[x, i], xs[b, i, c], .) for i = 0 .. S - 1 (ascending, as tap_critic_value orders it)
+ *   U[x, c]   = P[x, c] + (k[x] + the M[x, r] of the rows r set in column c, ascending, plane 0 before plane 1)
+ *   s, attn, t, logits: tap_pointer_scores' lines on this U
+ * -- tap_pointer_scores' contract with proj := P, every order of summation and the assignment of columns to wavefronts
+ * included: given a proj that equals P bit for bit both entries write the same bytes.  No proj, no static_hidden: an
+ * episode keeps xs (B S nR floats) where it kept 3 Hd nR floats per env.
+ *   xs (B, S, nR) f32 contiguous; G (3 Hd, S) row-major; g (3 Hd,) -- k and g stay separate arguments; the rest as
+ *   tap_pointer_scores takes it.
+ * k_pointer_scores<HPL, SS> (pointer.hip), tap_pointer_scores' kernel with another source for the static term: SS = S
+ * for S = 2, 3, 4 (a lane's HPL S values of G in registers), SS = 0 for S = 1 and 5 .. 8 (an LDS copy [i][hidden] of the
+ * chunk's G).  xs[b, :, c] is wave-uniform.  One launch, no allocation, no host read, capturable in a hipGraph.
+ * Launch record key (28, 0, HPL, PLANES, CHUNKS, 0, S).
+ * Shapes: tap_pointer_scores' and 1 <= S <= 8.  Checks, in tap_pointer_scores' order: B < 0 or nR / rows / Hd / S < 1 ->
+ * TAP_E_INVALID; B == 0 -> TAP_OK; a null buffer -> TAP_E_INVALID; a shape outside the list or S > 8 ->
+ * TAP_E_UNSUPPORTED; a misaligned buffer (bits 8 bytes, floats 4) -> TAP_E_INVALID. */
+int tap_pointer_scores_static(tap_ctx *ctx, const float *xs, const unsigned long long *bits, int B, int nR, int rows, int Hd,
+                              int S, const float *G, const float *g, const float *M, const float *k, const float *q,
+                              const float *va, const float *vp, float *logits_out, float *attn_out, float *t_out, void *stream);
+
+/* The backward of tap_pointer_scores_static: tap_pointer_scores_backward with P recomputed from xs, G and g.  Writes
+ * dU_out (B, 3 Hd, nR), dq_out (B, Hd), dva_out, dvp_out (Hd,) as that entry does; from dU the caller gets dM and the bias
+ * sum (tap_encode_bits_backward with H = 3 Hd: the sum is dk and dg alike) and dG[x, i] = sum over (b, c) of dU[b, x, c]
+ * xs[b, i, c].  xs carries no gradient.  Given a proj that equals P bit for bit, dU and dq are tap_pointer_scores_backward's
+ * bytes; dva / dvp are sums of one partial per workgroup and may differ in the last bits where the LDS copy of G (SS = 0)
+ * leaves room for fewer envs per workgroup.  scratch: at least tap_pointer_scores_static_backward_scratch(B, nR, rows, Hd,
+ * S) bytes.  The forward's checks in the forward's order (every buffer required), then the scratch, then the alignment
+ * (dU_out 16 bytes); B == 0 -> TAP_OK with nothing written.
+ * Launch record key (28, 0, HPL, PLANES, CHUNKS, 1, S), one count per call. */
+int tap_pointer_scores_static_backward(tap_ctx *ctx, const float *xs, const unsigned long long *bits, int B, int nR, int rows,
+                                       int Hd, int S, const float *G, const float *g, const float *M, const float *k,
+                                       const float *q, const float *va, const float *vp, const float *attn, const float *t,
+                                       const float *grad, float *dU_out, float *dq_out, float *dva_out, float *dvp_out,
+                                       void *scratch, size_t scratch_bytes, void *stream);
+/* bytes of scratch the backward needs for this shape (0 for a shape the entry refuses) */
+size_t tap_pointer_scores_static_backward_scratch(int B, int nR, int rows, int Hd, int S);
 
 /* The state critic's value estimate in ONE launch from the critic's static input and the bit shadow (critic.hip): the
  * reference's realCritic (trainer.py:18-94) after its GRU step.  With Es, bs / Ed, bd the static / dynamic encoder's

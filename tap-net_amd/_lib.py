@@ -29,7 +29,7 @@ TAP_HIT_EPISODE_MACS2_WAVE, TAP_HIT_EPISODE_MACS3_WAVE = 23, 24
 TAP_HIT_TRIAL = 25                                             # trial.hip: k_trial_scores
 TAP_HIT_POLICY_PICK = 26                                       # policy.hip: k_policy_pick / _wide / _backward
 TAP_HIT_ENCODE_BITS = 27                                       # encode.hip: k_encode_bits<HPL> / _bw_partial + _bw_reduce
-TAP_HIT_POINTER = 28                                           # pointer.hip: k_pointer_scores<HPL> / _bw<HPL> + _bw_reduce
+TAP_HIT_POINTER = 28                                           # pointer.hip: k_pointer_scores<HPL[, SS]> / _bw + _bw_reduce (last field: S of the static-rows form, 0 = proj)
 TAP_HIT_DECODER = 29                                           # decoder.hip: k_decoder_step / k_decoder_step_bw
 TAP_HIT_HEIGHTMAP = 30                                         # heightmap.hip: k_decoder_step_hm
 TAP_HIT_CRITIC = 31                                            # critic.hip: k_critic_value<HPL> / _bw<HPL> + _bw_reduce
@@ -103,6 +103,9 @@ _PROTOS = {
     "tap_pointer_scores_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                          _vp, _sz, _vp]),
     "tap_pointer_scores_backward_scratch": (_sz, [_i, _i, _i, _i]),
+    "tap_pointer_scores_static": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i] + [_vp] * 10 + [_vp]),
+    "tap_pointer_scores_static_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i] + [_vp] * 15 + [_sz, _vp]),
+    "tap_pointer_scores_static_backward_scratch": (_sz, [_i, _i, _i, _i, _i]),
     "tap_critic_value": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i] + [_vp] * 9),
     "tap_critic_value_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i] + [_vp] * 11 + [_sz, _vp]),
     "tap_critic_value_backward_scratch": (_sz, [_i, _i, _i, _i, _i, _i]),

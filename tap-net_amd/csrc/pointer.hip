@@ -26,6 +26,15 @@
 // takes as g, which then gives dM and dk -- through an LDS tile [hidden row][column] per env and pass of columns, stored
 // as float4s like k_encode_bits' output; dva / dvp as one partial per workgroup in the caller's scratch, added in
 // workgroup order by a second launch.
+//
+// The static-rows form (tapenv.h: tap_pointer_scores_static) is the same kernels with another source for the static term
+// of U: static_hidden is a 1x1 convolution of the S = 1..8 rows xs of `static`, so proj[b, x, c] = g[x] + G[x, :] . xs[b, :, c]
+// with G = Ws Es (3 Hd, S) and g = Ws bs -- S multiply-adds per element in place of a load (critic.hip computes its U this
+// way).  PtrSeg's SS parameter chooses: PTR_PROJ loads proj; SS = 2, 3, 4 keeps a lane's HPL SS values of G in registers;
+// SS = 0 takes any S <= 8 from an LDS copy [i][hidden] of the chunk's G.  xs[b, :, c] is wave-uniform and is loaded
+// PTR_AHEAD columns ahead, where the proj form loads proj.  Everything after the static term -- the bit loop, the phases,
+// every order of summation, the dU tile, the reduce -- is the proj form's code, so a proj that equals P bit for bit gives
+// the same bytes.
 #include <algorithm>
 
 #include "tap_common.h"
@@ -43,14 +52,19 @@ struct PtrGeom {
     int ct;                    // backward: columns per pass of the dU tile, min(nR, 4096 / hck)
     size_t lds;                // bytes of dynamic LDS
 };
-inline size_t ptr_lds_floats(int nR, int rows, int Hd, int hck, int epb, int ct)
+constexpr int PTR_PROJ = -1;                 // PtrSeg's SS: the static term of U is loaded from proj
+constexpr int PTR_SMAX = 8;                  // static rows of the static-rows form, as in critic.hip
+inline int ptr_static_ss(int S) { return S >= 2 && S <= 4 ? S : 0; }      // the instantiation that takes S static rows
+inline size_t ptr_lds_floats(int nR, int rows, int Hd, int hck, int epb, int ct, int gcopy = 0)
 {
     // the folded weights of a chunk, s / attn / logits (or dattn / ds), the wavefronts' partials, t (or dt); the backward
-    // adds (ct > 0) the dva / dvp partials and the dU tile of a pass
+    // adds (ct > 0) the dva / dvp partials and the dU tile of a pass; the static-rows form with SS = 0 its copy of a
+    // chunk's G (gcopy = S hck)
     return (size_t)rows * (hck + 1) + (size_t)epb * nR + (size_t)PTR_NW * epb * hck + (size_t)epb * Hd +
-           (ct ? (size_t)PTR_NW * hck + (size_t)hck * (ct + 1) : 0);
+           (ct ? (size_t)PTR_NW * hck + (size_t)hck * (ct + 1) : 0) + (size_t)gcopy;
 }
-inline PtrGeom ptr_geom(int B, int nR, int rows, int Hd, bool backward)
+// S = 0: the proj form; S >= 1: the static-rows form with S static rows
+inline PtrGeom ptr_geom(int B, int nR, int rows, int Hd, bool backward, int S = 0)
 {
     PtrGeom g;
     g.planes = rows > 64 ? 2 : 1;
@@ -58,10 +72,11 @@ inline PtrGeom ptr_geom(int B, int nR, int rows, int Hd, bool backward)
     g.hck = 64 * g.hpl;
     g.nch = Hd / g.hck;
     g.ct = backward ? std::min(nR, 4096 / g.hck) : 0;
+    const int gcopy = S > 0 && ptr_static_ss(S) == 0 ? S * g.hck : 0;      // at most 4 KB
     g.epb = std::max(1, B / 1024);                                         // about four workgroups per CU before a second env
-    while (g.epb > 1 && ptr_lds_floats(nR, rows, Hd, g.hck, g.epb, g.ct) * sizeof(float) > PTR_LDS_BUDGET) g.epb >>= 1;
+    while (g.epb > 1 && ptr_lds_floats(nR, rows, Hd, g.hck, g.epb, g.ct, gcopy) * sizeof(float) > PTR_LDS_BUDGET) g.epb >>= 1;
     g.blocks = (B + g.epb - 1) / g.epb;
-    g.lds = ptr_lds_floats(nR, rows, Hd, g.hck, g.epb, g.ct) * sizeof(float);   // at most 60 KB: a lone env needs under 56 KB
+    g.lds = ptr_lds_floats(nR, rows, Hd, g.hck, g.epb, g.ct, gcopy) * sizeof(float); // at most 60 KB: a lone env needs under 56 KB (+ gcopy: under 59 KB)
     return g;
 }
 
@@ -74,6 +89,12 @@ struct PtrArgs {
     const float *g;                 // backward: (B, nR)
     float *dU, *dq, *part;          // backward: (B, 3 Hd, nR), (B, Hd), (blocks, 2, Hd)
     int B, nR, rows, Hd, planes, epb, ct;
+};
+// the static-rows form: proj is null; P = gs + Gs . xs takes its place
+struct PtrArgsStatic : PtrArgs {
+    const float *xs;                // (B, S, nR)
+    const float *Gs, *gs;           // (3 Hd, S), (3 Hd,)
+    int S;
 };
 
 __device__ __forceinline__ float ptr_wave_sum(float v)
@@ -89,13 +110,76 @@ __device__ __forceinline__ float ptr_wave_max(float v)
     return v;
 }
 
-// what a phase keeps of its segment's chunk: the LDS copy of the folded weights and the lane's k
+// the static term of U in the static-rows form: what a phase keeps of its chunk's G and g, a column's xs, and
+// P[x0 + lane + 64 i, c] = g, then fmaf(G[., s], xs[b, s, c], .) for s ascending (tap_critic_value's order)
+template <int HPL, int SS>
+struct PtrStat {
+    static constexpr int HCK = 64 * HPL, NX = SS > 0 ? SS : PTR_SMAX;
+    struct Xs { float x[NX]; };
+    const float *xs, *G, *g;
+    float *lg;                      // SS == 0: lg[s * HCK + hl] = G[x0 + hl][s]
+    int S;
+    float gg[HPL], gw[HPL][SS > 0 ? SS : 1];
+
+    __device__ __forceinline__ void init(const PtrArgsStatic &a, float *lds_g) { xs = a.xs; G = a.Gs; g = a.gs; S = a.S; lg = lds_g; }
+    // between the caller's barriers, like PtrSeg::fill
+    __device__ __forceinline__ void fill(int x0, int tid, int lane)
+    {
+#pragma unroll
+        for (int i = 0; i < HPL; ++i) gg[i] = g[x0 + i * 64 + lane];
+        if constexpr (SS > 0) {
+#pragma unroll
+            for (int i = 0; i < HPL; ++i)
+#pragma unroll
+                for (int s = 0; s < SS; ++s) gw[i][s] = G[(size_t)(x0 + i * 64 + lane) * SS + s];
+        } else {
+            for (int i = tid; i < HCK * S; i += TAP_BLOCK) {
+                const int hl = i / S, s = i - hl * S;
+                lg[s * HCK + hl] = G[(size_t)x0 * S + i];
+            }
+        }
+    }
+    __device__ __forceinline__ void load(int b, int nR, int c, Xs &x) const
+    {
+        const float *xp = xs + (size_t)b * S * nR + c;
+#pragma unroll
+        for (int s = 0; s < NX; ++s) x.x[s] = (SS > 0 || s < S) ? xp[(size_t)s * nR] : 0.f;
+    }
+    __device__ __forceinline__ void term(int lane, float (&u)[HPL], const Xs &x) const
+    {
+#pragma unroll
+        for (int i = 0; i < HPL; ++i) {
+            float p = gg[i];
+            if constexpr (SS > 0) {
+#pragma unroll
+                for (int s = 0; s < SS; ++s) p = fmaf(gw[i][s], x.x[s], p);
+            } else {
+#pragma unroll
+                for (int s = 0; s < PTR_SMAX; ++s)
+                    if (s < S) p = fmaf(lg[s * HCK + i * 64 + lane], x.x[s], p);   // wave-uniform
+            }
+            u[i] = p;
+        }
+    }
+};
 template <int HPL>
+struct PtrStat<HPL, PTR_PROJ> {     // the proj form keeps nothing
+    struct Xs {};
+    __device__ __forceinline__ void init(const PtrArgs &, float *) {}
+    __device__ __forceinline__ void fill(int, int, int) {}
+    __device__ __forceinline__ void term(int, float (&)[HPL], const Xs &) const {}
+};
+
+// what a phase keeps of its segment's chunk: the LDS copy of the folded weights and the lane's k (and, in the static-rows
+// form, st)
+template <int HPL, int SS = PTR_PROJ>
 struct PtrSeg {
     static constexpr int HCK = 64 * HPL, S = HCK + 1;
+    using Xs = typename PtrStat<HPL, SS>::Xs;
     const float *lw;
     float kk[HPL];
     unsigned long long m0, m1;
+    PtrStat<HPL, SS> st;
 
     // M[x0 + hl][r] -> lw[r * S + hl]: global reads in memory order, LDS writes at the odd stride S.  The caller's barriers
     // stand before (the previous chunk has been consumed) and after.
@@ -112,20 +196,25 @@ struct PtrSeg {
         // bits at positions >= rows are ignored: masked off each plane's word
         m0 = rows >= 64 ? ~0ull : (1ull << rows) - 1;
         m1 = rows >= 128 ? ~0ull : rows > 64 ? (1ull << (rows - 64)) - 1 : 0ull;
+        st.fill(x0, tid, lane);
     }
 
     // U[x0 + lane + 64 i, c] of env b = proj + (k + the M columns of the set rows, ascending), in two halves: load()
-    // issues the loads of the column's shadow word(s) and proj values, finish() runs the scalar loop over the set bits
-    // and adds its sum to proj
+    // issues the loads of the column's shadow word(s) and proj values (static-rows form: the column's xs, and st.term()
+    // makes P of them in proj's place), finish() runs the scalar loop over the set bits and adds its sum to proj
     __device__ __forceinline__ void load(const PtrArgs &a, int b, int seg, int ch, int c, int lane, float (&u)[HPL],
-                                         unsigned long long (&w)[2]) const
+                                         unsigned long long (&w)[2], Xs &x) const
     {
         const unsigned long long *wp = a.bits + (size_t)b * (a.planes * a.nR);
         w[0] = wp[c];
         w[1] = a.planes == 2 ? wp[a.nR + c] : 0ull;
-        const float *pp = a.proj + (((size_t)b * 3 + seg) * a.nR + c) * a.Hd + ch * HCK + lane;
+        if constexpr (SS == PTR_PROJ) {
+            const float *pp = a.proj + (((size_t)b * 3 + seg) * a.nR + c) * a.Hd + ch * HCK + lane;
 #pragma unroll
-        for (int i = 0; i < HPL; ++i) u[i] = pp[i * 64];
+            for (int i = 0; i < HPL; ++i) u[i] = pp[i * 64];
+        } else {
+            st.load(b, a.nR, c, x);
+        }
     }
     __device__ __forceinline__ void finish(int lane, float (&u)[HPL], const unsigned long long (&w)[2]) const
     {
@@ -159,12 +248,14 @@ struct PtrSeg {
         for (int c0 = cbeg + wave; c0 < cend; c0 += PTR_NW * PTR_AHEAD) {
             float u[PTR_AHEAD][HPL];
             unsigned long long w[PTR_AHEAD][2];
+            Xs xv[PTR_AHEAD];
 #pragma unroll
-            for (int j = 0; j < PTR_AHEAD; ++j) load(a, b, seg, ch, min(c0 + j * PTR_NW, cend - 1), lane, u[j], w[j]);
+            for (int j = 0; j < PTR_AHEAD; ++j) load(a, b, seg, ch, min(c0 + j * PTR_NW, cend - 1), lane, u[j], w[j], xv[j]);
 #pragma unroll
             for (int j = 0; j < PTR_AHEAD; ++j) {
                 const int c = c0 + j * PTR_NW;
                 if (c < cend) {                                            // wave-uniform
+                    st.term(lane, u[j], xv[j]);
                     finish(lane, u[j], w[j]);
                     use(c, u[j]);
                 }
@@ -182,8 +273,9 @@ __device__ __forceinline__ float ptr_add_waves(const float *tp, int E, int HCK, 
     return v;
 }
 
-template <int HPL>
-__global__ void __launch_bounds__(TAP_BLOCK) k_pointer_scores(PtrArgs a)
+// both forms: A is PtrArgs (SS = PTR_PROJ, the proj form) or PtrArgsStatic (SS = 0, 2, 3, 4)
+template <int HPL, int SS = PTR_PROJ, class A = PtrArgs>
+__global__ void __launch_bounds__(TAP_BLOCK) k_pointer_scores(A a)
 {
     constexpr int HCK = 64 * HPL, S = HCK + 1;
     extern __shared__ float ptr_lds[];
@@ -191,7 +283,8 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_pointer_scores(PtrArgs a)
     const int nR = a.nR, Hd = a.Hd, E = a.epb, nch = Hd / HCK;
     float *lw = ptr_lds, *sl = lw + a.rows * S, *tp = sl + E * nR, *tl = tp + PTR_NW * E * HCK;
     const int e0 = (int)blockIdx.x * E, ne = min(E, a.B - e0);
-    PtrSeg<HPL> sg;
+    PtrSeg<HPL, SS> sg;
+    sg.st.init(a, tl + E * Hd);
 
     // phase 1, segment 0: s[c] = sum_j va[j] tanh(U[j, c] + q[j]) -> sl[e][c]
     for (int ch = 0; ch < nch; ++ch) {
@@ -299,8 +392,8 @@ __device__ __forceinline__ void ptr_store_tile(const float *tile, int TS, int nc
     __syncthreads();
 }
 
-template <int HPL>
-__global__ void __launch_bounds__(TAP_BLOCK) k_pointer_scores_bw(PtrArgs a)
+template <int HPL, int SS = PTR_PROJ, class A = PtrArgs>
+__global__ void __launch_bounds__(TAP_BLOCK) k_pointer_scores_bw(A a)
 {
     constexpr int HCK = 64 * HPL, S = HCK + 1;
     extern __shared__ float ptr_lds[];
@@ -311,7 +404,8 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_pointer_scores_bw(PtrArgs a)
     const int CT = a.ct, TS = CT + 1;                                      // columns per pass of the dU tile
     const int e0 = (int)blockIdx.x * E, ne = min(E, a.B - e0);
     float *part = a.part + (size_t)blockIdx.x * 2 * Hd;                    // this workgroup's dva (Hd), then dvp (Hd)
-    PtrSeg<HPL> sg;
+    PtrSeg<HPL, SS> sg;
+    sg.st.init(a, tile + HCK * TS);
 
     // phase 1, segment 1: G = U + t; dvp += g tanh(G); dG = g vp (1 - tanh^2) = dU[Hd + j]; dt[j] = sum_c dG[j, c]
     for (int ch = 0; ch < nch; ++ch) {
@@ -462,6 +556,48 @@ int ptr_check_shape(tap_ctx *ctx, const char *what, int nR, int rows, int Hd)
 }
 inline bool ptr_misaligned(const void *p, unsigned to) { return ((uintptr_t)p & (to - 1)) != 0; }
 
+// the static-rows form's launch: the instantiation (HPL, SS) of the forward or the backward
+template <int HPL, int SS>
+void ptr_launch_static_ss(bool backward, const PtrGeom &geo, hipStream_t st, const PtrArgsStatic &a)
+{
+    if (backward) hipLaunchKernelGGL((k_pointer_scores_bw<HPL, SS, PtrArgsStatic>), dim3((unsigned)geo.blocks), dim3(TAP_BLOCK), geo.lds, st, a);
+    else hipLaunchKernelGGL((k_pointer_scores<HPL, SS, PtrArgsStatic>), dim3((unsigned)geo.blocks), dim3(TAP_BLOCK), geo.lds, st, a);
+}
+template <int HPL>
+void ptr_launch_static_hpl(bool backward, const PtrGeom &geo, hipStream_t st, const PtrArgsStatic &a)
+{
+    switch (ptr_static_ss(a.S)) {
+    case 2: ptr_launch_static_ss<HPL, 2>(backward, geo, st, a); break;
+    case 3: ptr_launch_static_ss<HPL, 3>(backward, geo, st, a); break;
+    case 4: ptr_launch_static_ss<HPL, 4>(backward, geo, st, a); break;
+    default: ptr_launch_static_ss<HPL, 0>(backward, geo, st, a); break;
+    }
+}
+void ptr_launch_static(bool backward, const PtrGeom &geo, hipStream_t st, const PtrArgsStatic &a)
+{
+    if (geo.hpl == 1) ptr_launch_static_hpl<1>(backward, geo, st, a);
+    else ptr_launch_static_hpl<2>(backward, geo, st, a);
+}
+int ptr_check_dims_static(tap_ctx *ctx, const char *what, int B, int nR, int rows, int Hd, int S)
+{
+    if (B < 0 || nR < 1 || rows < 1 || Hd < 1 || S < 1)
+        return tap_fail(ctx, TAP_E_INVALID, "%s: B %d, nR %d, rows %d, Hd %d, S %d", what, B, nR, rows, Hd, S);
+    return TAP_OK;
+}
+int ptr_check_shape_static(tap_ctx *ctx, const char *what, int nR, int rows, int Hd, int S)
+{
+    if (!ptr_shape_ok(nR, rows, Hd) || S > PTR_SMAX)
+        return tap_fail(ctx, TAP_E_UNSUPPORTED, "%s: rows %d, nR %d, Hd %d, S %d (needs a bit shadow: rows <= 128, nR %% 4 == 0, nR <= 256; Hd 64, 128 or 256; S <= 8)",
+                        what, rows, nR, Hd, S);
+    return TAP_OK;
+}
+// the launch record of the static-rows form: the proj form's fields with S in the last one
+void ptr_hit_static(tap_ctx *ctx, const PtrGeom &geo, int backward, int S)
+{
+    const int32_t key[7] = {TAP_HIT_POINTER, 0, geo.hpl, geo.planes, geo.nch, backward, S};
+    tap_variant_hit_key(ctx, key);
+}
+
 } // namespace
 
 extern "C" int tap_pointer_scores(tap_ctx *ctx, const float *proj, const unsigned long long *bits, int B, int nR, int rows, int Hd,
@@ -524,5 +660,70 @@ extern "C" int tap_pointer_scores_backward(tap_ctx *ctx, const float *proj, cons
                        static_cast<const float *>(scratch), geo.blocks, Hd, dva_out, dvp_out);
     TAP_LAUNCH_CHECK(ctx, "k_pointer_scores_bw_reduce");
     tap_variant_hit(ctx, TAP_HIT_POINTER, 0, geo.hpl, TapVariant{geo.planes, geo.nch, 1}, 0);
+    return TAP_OK;
+}
+
+extern "C" int tap_pointer_scores_static(tap_ctx *ctx, const float *xs, const unsigned long long *bits, int B, int nR, int rows, int Hd,
+                                         int S, const float *G, const float *g, const float *M, const float *k, const float *q,
+                                         const float *va, const float *vp, float *logits_out, float *attn_out, float *t_out,
+                                         void *stream)
+{
+    int rc = ptr_check_dims_static(ctx, "pointer scores static", B, nR, rows, Hd, S);
+    if (rc != TAP_OK) return rc;
+    if (B == 0) return TAP_OK; // an empty batch has no buffers to check
+    if (!xs || !bits || !G || !g || !M || !k || !q || !va || !vp || !logits_out || !attn_out || !t_out)
+        return tap_fail(ctx, TAP_E_INVALID, "pointer scores static: null buffer");
+    if ((rc = ptr_check_shape_static(ctx, "pointer scores static", nR, rows, Hd, S)) != TAP_OK) return rc;
+    const void *f32[] = {xs, G, g, M, k, q, va, vp, logits_out, attn_out, t_out};
+    bool bad = ptr_misaligned(bits, 8);
+    for (const void *p : f32) bad = bad || ptr_misaligned(p, 4);
+    if (bad) return tap_fail(ctx, TAP_E_INVALID, "pointer scores static: bits must be 8-byte and the float buffers 4-byte aligned");
+    const PtrGeom geo = ptr_geom(B, nR, rows, Hd, false, S);
+    const PtrArgsStatic a = {{nullptr, bits, M, k, q, va, vp, logits_out, attn_out, t_out, nullptr, nullptr, nullptr, nullptr,
+                              B, nR, rows, Hd, geo.planes, geo.epb, 0},
+                             xs, G, g, S};
+    ptr_launch_static(false, geo, (hipStream_t)stream, a);
+    TAP_LAUNCH_CHECK(ctx, "k_pointer_scores (static rows)");
+    ptr_hit_static(ctx, geo, 0, S);
+    return TAP_OK;
+}
+
+extern "C" size_t tap_pointer_scores_static_backward_scratch(int B, int nR, int rows, int Hd, int S)
+{
+    if (B < 1 || nR < 1 || rows < 1 || Hd < 1 || S < 1 || S > PTR_SMAX || !ptr_shape_ok(nR, rows, Hd)) return 0;
+    return (size_t)ptr_geom(B, nR, rows, Hd, true, S).blocks * 2 * (size_t)Hd * sizeof(float);
+}
+
+extern "C" int tap_pointer_scores_static_backward(tap_ctx *ctx, const float *xs, const unsigned long long *bits, int B, int nR, int rows,
+                                                  int Hd, int S, const float *G, const float *g, const float *M, const float *k,
+                                                  const float *q, const float *va, const float *vp, const float *attn, const float *t,
+                                                  const float *grad, float *dU_out, float *dq_out, float *dva_out, float *dvp_out,
+                                                  void *scratch, size_t scratch_bytes, void *stream)
+{
+    int rc = ptr_check_dims_static(ctx, "pointer scores static backward", B, nR, rows, Hd, S);
+    if (rc != TAP_OK) return rc;
+    if (B == 0) return TAP_OK; // (an empty batch leaves the outputs as they are)
+    if (!xs || !bits || !G || !g || !M || !k || !q || !va || !vp || !attn || !t || !grad || !dU_out || !dq_out || !dva_out || !dvp_out)
+        return tap_fail(ctx, TAP_E_INVALID, "pointer scores static backward: null buffer");
+    if ((rc = ptr_check_shape_static(ctx, "pointer scores static backward", nR, rows, Hd, S)) != TAP_OK) return rc;
+    const size_t need = tap_pointer_scores_static_backward_scratch(B, nR, rows, Hd, S);
+    if (!scratch || scratch_bytes < need)
+        return tap_fail(ctx, TAP_E_INVALID, "pointer scores static backward: scratch of %zu bytes, %zu needed", scratch ? scratch_bytes : (size_t)0, need);
+    const void *f32[] = {xs, G, g, M, k, q, va, vp, attn, t, grad, dU_out, dq_out, dva_out, dvp_out, scratch};
+    bool bad = ptr_misaligned(bits, 8) || ptr_misaligned(dU_out, 16);      // dU leaves as float4s
+    for (const void *p : f32) bad = bad || ptr_misaligned(p, 4);
+    if (bad)
+        return tap_fail(ctx, TAP_E_INVALID, "pointer scores static backward: bits must be 8-byte, dU 16-byte and the other float buffers 4-byte aligned");
+    const PtrGeom geo = ptr_geom(B, nR, rows, Hd, true, S);
+    const PtrArgsStatic a = {{nullptr, bits, M, k, q, va, vp, nullptr, const_cast<float *>(attn), const_cast<float *>(t), grad, dU_out,
+                              dq_out, static_cast<float *>(scratch), B, nR, rows, Hd, geo.planes, geo.epb, geo.ct},
+                             xs, G, g, S};
+    hipStream_t st = (hipStream_t)stream;
+    ptr_launch_static(true, geo, st, a);
+    TAP_LAUNCH_CHECK(ctx, "k_pointer_scores_bw (static rows)");
+    hipLaunchKernelGGL(k_pointer_scores_bw_reduce, dim3((unsigned)((2 * Hd + TAP_BLOCK - 1) / TAP_BLOCK)), dim3(TAP_BLOCK), 0, st,
+                       static_cast<const float *>(scratch), geo.blocks, Hd, dva_out, dvp_out);
+    TAP_LAUNCH_CHECK(ctx, "k_pointer_scores_bw_reduce");
+    ptr_hit_static(ctx, geo, 1, S);
     return TAP_OK;
 }

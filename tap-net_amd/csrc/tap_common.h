@@ -53,17 +53,21 @@ struct tap_ctx {
 };
 
 // counts one launch of an instantiation (host only: a launch captured into a hipGraph counts once, at capture)
-inline void tap_variant_hit(tap_ctx *ctx, int kind, int D, int G, const TapVariant &v, int wt)
+inline void tap_variant_hit_key(tap_ctx *ctx, const int32_t (&key)[7])
 {
     if (!ctx) return;
-    const int32_t key[7] = {kind, D, G, v.nc, v.mode, v.extra, wt ? 1 : 0};
-    static_assert((int)TAP_SV_KINDS <= (int)TAP_HIT_EPISODE, "launch-record kinds overlap");
     std::lock_guard<std::mutex> g(ctx->hit_lock);
     for (int i = 0; i < ctx->nhits; ++i)
         if (memcmp(ctx->hits[i].key, key, sizeof(key)) == 0) { ctx->hits[i].count += 1; return; }
     if (ctx->nhits == TAP_VARIANT_HIT_SLOTS) { ctx->hits_full = true; return; }
     memcpy(ctx->hits[ctx->nhits].key, key, sizeof(key));
     ctx->hits[ctx->nhits++].count = 1;
+}
+inline void tap_variant_hit(tap_ctx *ctx, int kind, int D, int G, const TapVariant &v, int wt)
+{
+    static_assert((int)TAP_SV_KINDS <= (int)TAP_HIT_EPISODE, "launch-record kinds overlap");
+    const int32_t key[7] = {kind, D, G, v.nc, v.mode, v.extra, wt ? 1 : 0};
+    tap_variant_hit_key(ctx, key);
 }
 
 // LDS budget of one workgroup: what the device reports (hipDeviceAttributeMaxSharedMemoryPerBlock; 160 KiB on

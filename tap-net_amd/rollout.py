@@ -426,6 +426,130 @@ def pointer_scores(proj, bits, M, k, q, va, vp, rows=None):
     return logits
 
 
+def pointer_scores_static_supported(rows, nR, Hd, S):
+    """whether tap_pointer_scores_static has a kernel for this shape: ``pointer_scores_supported`` and 1 <= S <= 8 static rows"""
+    return 1 <= int(S) <= 8 and pointer_scores_supported(rows, nR, Hd)
+
+
+def _scores_static_into(xs, bits, G, g, M, k, q, va, vp, rows, logits, attn, t):
+    """tap_pointer_scores_static on prepared buffers: one launch on the current stream, nothing allocated"""
+    dev = xs.device
+    c = _lib.ctx(dev)
+    B, S, nR = (int(v) for v in xs.shape)
+    Hd = int(q.shape[1])
+    _lib.check(_lib.lib().tap_pointer_scores_static(c, _lib.ptr(xs), _lib.ptr(bits), B, nR, rows, Hd, S, _lib.ptr(G), _lib.ptr(g),
+                                                    _lib.ptr(M), _lib.ptr(k), _lib.ptr(q), _lib.ptr(va), _lib.ptr(vp),
+                                                    _lib.ptr(logits), _lib.ptr(attn), _lib.ptr(t), _lib.stream_of(dev)), c)
+
+
+class _PointerScoresStatic(torch.autograd.Function):
+    """pointer_scores_static under autograd: forward = the one launch, backward = tap_pointer_scores_static_backward (dU,
+    dq, dva, dvp), tap_encode_bits_backward on dU (dM and the bias sum, which is dk and dg alike) and dG = sum_b dU[b] xs[b]^T
+    as ``_CriticValue.backward`` computes its dG.  What a step keeps beside its parameters: a CLONE of the shadow, attn (B, nR),
+    t and q (B, Hd), and ``xs`` by reference; dU is a temporary of the backward and is returned to nobody."""
+
+    @staticmethod
+    def forward(ctx, xs, bits, G, g, M, k, q, va, vp, rows):
+        B, S, nR = (int(v) for v in xs.shape)
+        Hd, dev = int(q.shape[1]), xs.device
+        logits = torch.empty(B, nR, dtype=torch.float32, device=dev)
+        attn = torch.empty(B, nR, dtype=torch.float32, device=dev)
+        t = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+        _scores_static_into(xs, bits, G, g, M, k, q, va, vp, rows, logits, attn, t)
+        ctx.save_for_backward(xs, bits.clone(), G, g, M, k, q, va, vp, attn, t)
+        ctx.rows = rows
+        return logits
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        xs, bits, G, g, M, k, q, va, vp, attn, t = ctx.saved_tensors
+        B, S, nR = (int(v) for v in xs.shape)
+        Hd, rows, dev = int(q.shape[1]), ctx.rows, xs.device
+        L, c = _lib.lib(), _lib.ctx(dev)
+        f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        dva, dvp, dM, dk, dq = f(Hd), f(Hd), f(3 * Hd, rows), f(3 * Hd), f(B, Hd)
+        if B == 0:
+            for z in (dva, dvp, dM, dk):
+                z.zero_()
+            return None, None, torch.zeros_like(G), dk, dM, dk.clone(), dq, dva, dvp, None
+        grad = _as_f32(grad, dev)
+        dU = f(B, 3 * Hd, nR)
+        need = int(L.tap_pointer_scores_static_backward_scratch(B, nR, rows, Hd, S))
+        need2 = int(L.tap_encode_bits_backward_scratch(B, nR, rows, 3 * Hd))
+        scratch = f(max(need, need2, 16) // 4)
+        st = _lib.stream_of(dev)
+        _lib.check(L.tap_pointer_scores_static_backward(c, _lib.ptr(xs), _lib.ptr(bits), B, nR, rows, Hd, S, _lib.ptr(G), _lib.ptr(g),
+                                                        _lib.ptr(M), _lib.ptr(k), _lib.ptr(q), _lib.ptr(va), _lib.ptr(vp),
+                                                        _lib.ptr(attn), _lib.ptr(t), _lib.ptr(grad), _lib.ptr(dU), _lib.ptr(dq),
+                                                        _lib.ptr(dva), _lib.ptr(dvp), _lib.ptr(scratch), need, st), c)
+        # dM[x, r] = sum over (b, c) of dU[b, x, c] bit[b, r, c], dk[x] = dg[x] = sum of dU: the encoder's backward with H = 3 Hd
+        _lib.check(L.tap_encode_bits_backward(c, _lib.ptr(bits), _lib.ptr(dU), B, nR, rows, 3 * Hd, _lib.ptr(dM), _lib.ptr(dk),
+                                              _lib.ptr(scratch), need2, st), c)
+        # dG = sum_b dU[b] xs[b]^T: one batched product that reads dU once, then the batch sum of (B, 3 Hd, S)
+        dG = torch.bmm(dU, xs.transpose(1, 2)).sum(0)
+        return None, None, dG, dk, dM, dk.clone(), dq, dva, dvp, None
+
+
+def pointer_scores_static(xs, bits, G, g, M, k, q, va, vp, rows=None):
+    """``pointer_scores`` without ``proj`` (tapenv.h: tap_pointer_scores_static): the static term of U is computed inside the
+    launch from the S = 1 .. 8 rows of ``static`` that the static encoder sees -> logits (B, nR) float32.
+    ``xs`` (B, S, nR) that slice of ``static``; ``G`` (3 Hd, S) and ``g`` (3 Hd,) the static encoder folded into the two W
+    (``tools.Pointer.fold_static`` builds them); the rest as ``pointer_scores`` takes it.  Per env and column, in fp32:
+    P = g, then fmaf(G[:, i], xs[i], .) for i ascending; U = P + (k + the M columns of the set rows, ascending); s, attn, t and
+    the logits as in ``pointer_scores`` -- with a ``proj`` that equals P bit for bit, the same bytes.  Floating inputs of
+    another dtype, layout or device are converted through ``.float()``.  With grad enabled and any parameter requiring grad
+    the call runs through a ``torch.autograd.Function`` whose backward is tap_pointer_scores_static_backward +
+    tap_encode_bits_backward and one batched product for dG (deterministic: no atomics); per step it keeps a clone of
+    ``bits``, ``attn`` (B, nR), ``t`` and ``q`` (B, Hd), and ``xs`` by reference.  ``xs`` and ``bits`` get no gradient.  A
+    shape without a kernel (``pointer_scores_static_supported``) raises ValueError."""
+    if bits.dtype is not torch.int64:
+        raise TypeError("bits must be the int64 shadow (pack.dynamic_bits), got %s" % (bits.dtype,))
+    if xs.dim() != 3 or not xs.is_floating_point():
+        raise ValueError("xs must be a floating (B, S, nR) tensor, got %s %s" % (xs.dtype, tuple(xs.shape)))
+    B, S, nR = (int(v) for v in xs.shape)
+    if not 1 <= S <= 8:
+        raise ValueError("xs has %d static rows; the kernel takes 1 .. 8" % S)
+    if M.dim() != 2 or int(M.shape[0]) % 3 or not M.is_floating_point():
+        raise ValueError("M must be a floating (3 Hd, rows) tensor, got %s %s" % (M.dtype, tuple(M.shape)))
+    Hd = int(M.shape[0]) // 3
+    rows = int(M.shape[1]) if rows is None else int(rows)
+    if rows != int(M.shape[1]):
+        raise ValueError("M has %d rows' columns, rows is %d" % (int(M.shape[1]), rows))
+    for name, v, shape in (("G", G, (3 * Hd, S)), ("g", g, (3 * Hd,)), ("k", k, (3 * Hd,)), ("q", q, (B, Hd)), ("va", va, (Hd,)),
+                           ("vp", vp, (Hd,))):
+        if tuple(v.shape) != shape or not v.is_floating_point():
+            raise ValueError("%s must be a floating %s tensor, got %s %s" % (name, shape, v.dtype, tuple(v.shape)))
+    planes = 2 if rows > 64 else 1
+    if bits.dim() not in (2, 3) or int(bits.shape[0]) != B or int(math.prod(bits.shape[1:])) != planes * nR or \
+            (bits.dim() == 3 and tuple(bits.shape[1:]) != (planes, nR)):
+        raise ValueError("xs of shape %s and bits of shape %s are not (B, S, nR) and the shadow of B envs of a (%d, nR) window"
+                         % (tuple(xs.shape), tuple(bits.shape), rows))
+    if rows < 1 or nR < 1 or not pointer_scores_static_supported(rows, nR, Hd, S):
+        raise ValueError("no pointer kernel for rows %d, nR %d, Hd %d, S %d (rows <= 128, nR %% 4 == 0, nR <= 256, Hd 64 / 128 / 256, "
+                         "S <= 8)" % (rows, nR, Hd, S))
+    dev = _lib.resolve_device(bits.device)
+    if not bits.is_contiguous() or bits.device != dev:
+        bits = bits.to(dev).contiguous()
+
+    def prep(t):
+        if t.dtype is not torch.float32:
+            t = t.float()
+        if not t.is_contiguous() or t.device != dev:
+            t = t.to(dev).contiguous()
+        return t
+    xs = prep(xs.detach())
+    args = [prep(v) for v in (G, g, M, k, q, va, vp)]
+    if torch.is_grad_enabled() and any(v.requires_grad for v in args):
+        return _PointerScoresStatic.apply(xs, bits, *args, rows)
+    args = [v.detach() for v in args]
+    logits = torch.empty(B, nR, dtype=torch.float32, device=dev)
+    attn = torch.empty(B, nR, dtype=torch.float32, device=dev)
+    t = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+    _scores_static_into(xs, bits, *args, rows, logits, attn, t)
+    return logits
+
+
 def critic_value_supported(rows, nR, H, S, blocks):
     """whether tap_critic_value has a kernel for this shape: a window with a shadow, H 64, 128 or 256, 1 <= S <= 8 static
     rows and 1 <= blocks <= 8 process blocks"""

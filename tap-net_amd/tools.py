@@ -170,7 +170,15 @@ class Pointer(nn.Module):
 
     ``forward_step_dropout(..., last_hh, dropout)`` and ``forward_bits_dropout(..., last_hh, dropout)`` are the training
     forms: ``dropout`` is a ``StepDropout``, whose counter-based masks replace torch's generator -- inside the first launch
-    where there is one, through ``rollout.dropout_keep_words`` on the torch path."""
+    where there is one, through ``rollout.dropout_keep_words`` on the torch path.
+
+    ``fold_static(static_encoder, static_input)`` -> ``StaticFold``, once per episode, differentiable in the encoder's and the
+    two W's parameters: the static encoder folded into the two W (G, g) beside the rows ``xs`` of ``static`` it sees.  The
+    record is accepted wherever ``proj`` is -- ``forward_bits``, ``forward_step`` and both ``_dropout`` forms --; the pointer
+    launch is then ``rollout.pointer_scores_static``, which computes the static term from ``xs`` inside the launch: an episode
+    has no static_hidden and no ``proj``.  The dispatch is on the type: a tensor goes the way described above.  With the
+    record the torch path is ``forward`` on ``static_encoder(xs)``, in the dtype it is given, and is taken off the GPU, on a
+    shape without a kernel and, in ``forward_step``, under the conditions listed there."""
 
     def __init__(self, encoder_hidden_size, decoder_hidden_size, decoder_input_type, input_type, num_layers=1, dropout=0.2):
         super(Pointer, self).__init__()
@@ -258,6 +266,42 @@ class Pointer(nn.Module):
         proj.static_hidden = static_hidden
         return proj
 
+    def fold_static(self, static_encoder, static_input):
+        """-> the ``StaticFold`` that stands where ``proj`` stands, once per episode: static_hidden = Es . xs + bs is a 1x1
+        convolution of the S rows ``static_input`` (B, S, nR) of ``static`` that the encoder sees (the reference's
+        ``static[:, 1:, :]``), so proj = g + G . xs with G = Ws . Es (3 Hd, S) and g = Ws . bs (3 Hd,), Ws from
+        ``folded_weights``.  G and g are differentiable in the encoder's and the two W's parameters; ``xs`` is kept detached
+        and contiguous.  ``static_encoder``: anything with a kernel-size-1 ``.conv``, or an ``nn.Conv1d`` itself."""
+        conv = getattr(static_encoder, "conv", static_encoder)
+        w = conv.weight
+        if w.dim() != 3 or int(w.shape[2]) != 1:
+            raise ValueError("the static encoder must be a kernel-size-1 convolution, got a weight of shape %s" % (tuple(w.shape),))
+        if static_input.dim() != 3 or int(static_input.shape[1]) != int(w.shape[1]) or not static_input.is_floating_point():
+            raise ValueError("static_input must be a floating (B, %d, nR) tensor, got %s %s"
+                             % (int(w.shape[1]), static_input.dtype, tuple(static_input.shape)))
+        Ws = self.folded_weights()[0]
+        sf = StaticFold()
+        sf.static_encoder = static_encoder
+        sf.xs = static_input.detach().contiguous()
+        sf.G = Ws.matmul(w[:, :, 0].to(Ws.dtype))
+        sf.g = Ws.matmul(conv.bias.to(Ws.dtype)) if conv.bias is not None else torch.zeros_like(Ws[:, 0])
+        sf.S, sf.nR = int(static_input.shape[1]), int(static_input.shape[2])
+        return sf
+
+    def _forward_static_torch(self, sf, bits, dynamic_encoder, decoder_hidden, last_hh, keep):
+        """the torch path of a step whose static side is a ``StaticFold``: ``forward`` on ``static_encoder(xs)`` and the
+        dynamic encoder's output.  A shadow off the GPU is unpacked to the 0/1 ``dynamic``; anything else goes to the encoder
+        as it is"""
+        conv = dynamic_encoder.conv
+        if bits.dtype is torch.int64 and not bits.is_cuda:
+            rows = int(conv.weight.shape[1])
+            w = bits.reshape(bits.shape[0], 2 if rows > 64 else 1, sf.nR)
+            r = torch.arange(rows, device=bits.device)
+            dynamic_hidden = dynamic_encoder(((w[:, r // 64, :] >> (r % 64).view(1, rows, 1)) & 1).to(conv.weight.dtype))
+        else:
+            dynamic_hidden = dynamic_encoder(bits)
+        return self._forward(sf.static_encoder(sf.xs), dynamic_hidden, decoder_hidden, last_hh, keep)
+
     def forward_bits(self, proj, bits, dynamic_encoder, decoder_hidden, last_hh):
         return self._forward_bits(proj, bits, dynamic_encoder, decoder_hidden, last_hh, None)
 
@@ -267,11 +311,21 @@ class Pointer(nn.Module):
         launch applies for the same (state, step).  In ``eval()`` it is ``forward_bits`` and the step counter stays."""
         return self._forward_bits(proj, bits, dynamic_encoder, decoder_hidden, last_hh, dropout)
 
-    def _forward_bits(self, proj, bits, dynamic_encoder, decoder_hidden, last_hh, dropout):
-        from .rollout import pointer_scores, pointer_scores_supported
+    def _forward_bits(self, proj, bits, dynamic_encoder, decoder_hidden, last_hh, dropout, torch_only=False):
+        from .rollout import pointer_scores, pointer_scores_static, pointer_scores_static_supported, pointer_scores_supported
         conv = dynamic_encoder.conv
-        rows, nR, Hd = int(conv.weight.shape[1]), int(proj.shape[2]), self.decoder_hidden_size
+        static = isinstance(proj, StaticFold)
+        rows, nR, Hd = int(conv.weight.shape[1]), proj.nR if static else int(proj.shape[2]), self.decoder_hidden_size
         keep = self._keep_words(self._step_dropout(dropout), int(decoder_hidden.shape[0]))
+        if static:
+            if torch_only or not bits.is_cuda or bits.dtype is not torch.int64 or not pointer_scores_static_supported(rows, nR, Hd, proj.S):
+                return self._forward_static_torch(proj, bits, dynamic_encoder, decoder_hidden, last_hh, keep)
+            rnn_out, last_hh = self._gru_step(decoder_hidden, last_hh, keep)
+            _, Wd, Wq = self.folded_weights()
+            M = Wd.matmul(conv.weight[:, :, 0])
+            k = Wd.matmul(conv.bias) if conv.bias is not None else torch.zeros_like(Wd[:, 0])
+            q = rnn_out.matmul(Wq.t())
+            return pointer_scores_static(proj.xs, bits, proj.G, proj.g, M, k, q, self.encoder_attn.v[0, 0], self.v[0, 0], rows=rows), last_hh
         if not pointer_scores_supported(rows, nR, Hd):
             static_hidden = getattr(proj, "static_hidden", None)
             if static_hidden is None:
@@ -397,9 +451,10 @@ class Pointer(nn.Module):
         return self._forward_step(proj, bits, fold, decoder_static, decoder_dynamic, last_hh, dropout)
 
     def _forward_step(self, proj, bits, fold, decoder_static, decoder_dynamic, last_hh, dropout):
-        from .rollout import (decoder_step_heightmap_supported, decoder_step_supported, pointer_scores, pointer_scores_supported,
-                              _decoder_step, _decoder_step_heightmap)
-        Hd, nR = self.decoder_hidden_size, int(proj.shape[2])
+        from .rollout import (decoder_step_heightmap_supported, decoder_step_supported, pointer_scores, pointer_scores_static,
+                              pointer_scores_static_supported, pointer_scores_supported, _decoder_step, _decoder_step_heightmap)
+        static = isinstance(proj, StaticFold)
+        Hd, nR = self.decoder_hidden_size, proj.nR if static else int(proj.shape[2])
         Ks = 0 if decoder_static is None or fold.static_decoder is None else int(decoder_static[0].numel())
         Kd = 0 if decoder_dynamic is None or (fold.dynamic_decoder is None and not fold.identity_dynamic) else int(decoder_dynamic[0].numel())
         rec = self._step_dropout(dropout)
@@ -418,17 +473,21 @@ class Pointer(nn.Module):
                 decoder_step_heightmap_supported(Ks, *decoder_dynamic.shape[1:], m, Hd)
         else:
             launch = Ks + Kd == int(fold.P.shape[1]) and decoder_step_supported(Ks, Kd, Hd)
-        if dropping or self.num_layers != 1 or not self.gru.bias or not bits.is_cuda or not launch or \
-                not pointer_scores_supported(fold.rows, nR, Hd):
+        kernel = pointer_scores_static_supported(fold.rows, nR, Hd, proj.S) and bits.dtype is torch.int64 if static else \
+            pointer_scores_supported(fold.rows, nR, Hd)
+        if dropping or self.num_layers != 1 or not self.gru.bias or not bits.is_cuda or not launch or not kernel:
             decoder_hidden = self._decoder_hidden(fold, decoder_static, decoder_dynamic)
-            return self._forward_bits(proj, bits, fold.dynamic_encoder, decoder_hidden, last_hh, rec)
+            return self._forward_bits(proj, bits, fold.dynamic_encoder, decoder_hidden, last_hh, rec, torch_only=static)
         if hm is not None:
             h_new, q = _decoder_step_heightmap(decoder_static if Ks else None, decoder_dynamic, None if last_hh is None else last_hh[0],
                                                hm, fold.P, fold.c, fold.w_hh, fold.b_hh, fold.Wq, rec)
         else:
             h_new, q = _decoder_step(decoder_static if Ks else None, decoder_dynamic if Kd else None,
                                      None if last_hh is None else last_hh[0], fold.P, fold.c, fold.w_hh, fold.b_hh, fold.Wq, rec)
-        logits = pointer_scores(proj, bits, fold.M, fold.k, q, fold.va, fold.vp, rows=fold.rows)
+        if static:
+            logits = pointer_scores_static(proj.xs, bits, proj.G, proj.g, fold.M, fold.k, q, fold.va, fold.vp, rows=fold.rows)
+        else:
+            logits = pointer_scores(proj, bits, fold.M, fold.k, q, fold.va, fold.vp, rows=fold.rows)
         return logits, h_new.unsqueeze(0)
 
 
@@ -564,6 +623,13 @@ class StepFold(object):
     ``heightmap`` is the dynamic decoder when it is a ``HeightmapEncoder`` (it runs inside the step's launch), else None."""
     __slots__ = ("dynamic_encoder", "rows", "M", "k", "P", "c", "Wq", "va", "vp", "w_ih", "w_hh", "b_ih", "b_hh",
                  "static_decoder", "dynamic_decoder", "combine", "identity_dynamic", "heightmap")
+
+
+class StaticFold(object):
+    """What ``Pointer.fold_static`` returns and every step takes in ``proj``'s place: ``xs`` (B, S, nR) the rows of ``static``
+    that the static encoder sees, detached and contiguous; ``G`` (3 Hd, S) and ``g`` (3 Hd,) the encoder folded into the two W
+    (``rollout.pointer_scores_static``'s parameters); ``static_encoder`` for the torch path; ``nR`` and ``S``."""
+    __slots__ = ("xs", "G", "g", "static_encoder", "nR", "S")
 
 
 class StepDropout(object):
