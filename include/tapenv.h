@@ -646,6 +646,13 @@ int tap_encode_bits_backward(tap_ctx *ctx, const unsigned long long *bits, const
                              float *dweight, float *dbias /* or NULL */, void *scratch, size_t scratch_bytes, void *stream);
 /* bytes of scratch the backward needs for this shape (0 for a shape the entry refuses) */
 size_t tap_encode_bits_backward_scratch(int B, int nR, int rows, int H);
+/* The launch geometry of tap_encode_bits (backward = 0) or tap_encode_bits_backward (backward != 0) for this shape, from
+ * the function the launcher itself calls: host only, no context, no GPU code, like tap_bits_words.  Forward: out =
+ * (consecutive envs per workgroup, grid x = runs of envs, grid y = hidden chunks, bytes of dynamic LDS).  Backward: out =
+ * (envs per slice, slices, hidden chunks, hidden rows per chunk); the scratch above is slices * H * (rows + 1) floats.
+ * TAP_OK; a null out -> TAP_E_INVALID; B, nR, rows or H < 1 -> TAP_E_INVALID and a shape the entries refuse ->
+ * TAP_E_UNSUPPORTED, both with out = zeros (as the scratch query answers 0). */
+int tap_encode_bits_geometry(int B, int nR, int rows, int H, int backward, int32_t out[4]);
 
 /* ---- the pointer network on the bit shadow: glimpse and logits in one launch -------------------- */
 
@@ -738,6 +745,14 @@ int tap_pointer_scores_static_backward(tap_ctx *ctx, const float *xs, const unsi
                                        void *scratch, size_t scratch_bytes, void *stream);
 /* bytes of scratch the backward needs for this shape (0 for a shape the entry refuses) */
 size_t tap_pointer_scores_static_backward_scratch(int B, int nR, int rows, int Hd, int S);
+/* The launch geometry of the four pointer entries for this shape, from the function the launchers themselves call: host
+ * only, no context, no GPU code, like tap_bits_words.  S = 0: tap_pointer_scores / _backward; S = 1 .. 8: the static-rows
+ * form; backward != 0: the backward.  out = (consecutive envs per workgroup -- max(1, B / 1024), halved while the dynamic
+ * LDS exceeds 60 KB --, workgroups = ceil(B / envs per workgroup), bytes of dynamic LDS, columns per pass of the backward's
+ * dU tile (0 forward)); the backward's scratch is workgroups * 2 * Hd floats.  TAP_OK; a null out -> TAP_E_INVALID; B, nR,
+ * rows or Hd < 1 or S < 0 -> TAP_E_INVALID and a shape the entries refuse -> TAP_E_UNSUPPORTED, both with out = zeros (as
+ * the scratch queries answer 0). */
+int tap_pointer_scores_geometry(int B, int nR, int rows, int Hd, int S, int backward, int32_t out[4]);
 
 /* The state critic's value estimate in ONE launch from the critic's static input and the bit shadow (critic.hip): the
  * reference's realCritic (trainer.py:18-94) after its GRU step.  With Es, bs / Ed, bd the static / dynamic encoder's

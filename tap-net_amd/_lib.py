@@ -99,6 +99,7 @@ _PROTOS = {
     "tap_encode_bits": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "tap_encode_bits_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "tap_encode_bits_backward_scratch": (_sz, [_i, _i, _i, _i]),
+    "tap_encode_bits_geometry": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int32)]),
     "tap_pointer_scores": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tap_pointer_scores_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                          _vp, _sz, _vp]),
@@ -106,6 +107,7 @@ _PROTOS = {
     "tap_pointer_scores_static": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i] + [_vp] * 10 + [_vp]),
     "tap_pointer_scores_static_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i] + [_vp] * 15 + [_sz, _vp]),
     "tap_pointer_scores_static_backward_scratch": (_sz, [_i, _i, _i, _i, _i]),
+    "tap_pointer_scores_geometry": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32)]),
     "tap_critic_value": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i] + [_vp] * 9),
     "tap_critic_value_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i] + [_vp] * 11 + [_sz, _vp]),
     "tap_critic_value_backward_scratch": (_sz, [_i, _i, _i, _i, _i, _i]),
@@ -243,6 +245,26 @@ def variant_keys(device):
 def variant_hits_reset(device):
     c = ctx(device)
     check(lib().tap_variant_hits_reset(c), c)
+
+
+def pointer_scores_geometry(B, nR, rows, Hd, S=0, backward=False):
+    """tap_pointer_scores_geometry (host only, no context) -> (envs per workgroup, workgroups, bytes of dynamic LDS, columns
+    per pass of the dU tile); S = 0 the proj form.  Raises TapError for a shape the entries refuse."""
+    out = (C.c_int32 * 4)()
+    st = lib().tap_pointer_scores_geometry(int(B), int(nR), int(rows), int(Hd), int(S), 1 if backward else 0, out)
+    if st != TAP_OK:
+        raise TapError(st, "no pointer geometry for B %d, nR %d, rows %d, Hd %d, S %d" % (B, nR, rows, Hd, S))
+    return tuple(out)
+
+
+def encode_bits_geometry(B, nR, rows, H, backward=False):
+    """tap_encode_bits_geometry (host only, no context) -> forward (envs per workgroup, grid x, grid y, bytes of dynamic LDS),
+    backward (envs per slice, slices, hidden chunks, hidden rows per chunk).  Raises TapError for a shape the entries refuse."""
+    out = (C.c_int32 * 4)()
+    st = lib().tap_encode_bits_geometry(int(B), int(nR), int(rows), int(H), 1 if backward else 0, out)
+    if st != TAP_OK:
+        raise TapError(st, "no encoder geometry for B %d, nR %d, rows %d, H %d" % (B, nR, rows, H))
+    return tuple(out)
 
 
 def check(status, context):

@@ -48,6 +48,27 @@ struct EncArgs {
 // weights of a chunk + the output tile of a pass, in floats
 inline size_t enc_lds_floats(int rows, int hck, int CT) { return (size_t)rows * (hck + 1) + (size_t)hck * (CT + 1); }
 
+// the forward's launch: what tap_encode_bits launches with and tap_encode_bits_geometry reports
+struct EncGeom {
+    int planes, hpl, hck; // shadow planes; hidden rows per lane, per chunk
+    int CT, epb;          // columns per pass; consecutive envs per workgroup
+    int gx, gy;           // the grid: runs of envs, hidden chunks
+    size_t lds;           // bytes of dynamic LDS
+};
+inline EncGeom enc_geom(int B, int nR, int rows, int H)
+{
+    EncGeom g;
+    g.planes = rows > 64 ? 2 : 1;
+    g.hpl = (g.planes == 1 && H > 64) ? 2 : 1;
+    g.hck = 64 * g.hpl;
+    g.CT = std::min(nR, 4096 / g.hck);
+    g.epb = std::max(1, B / 1024);                                         // about four workgroups per CU before a second env
+    g.gx = (B + g.epb - 1) / g.epb;
+    g.gy = (H + g.hck - 1) / g.hck;
+    g.lds = enc_lds_floats(rows, g.hck, g.CT) * sizeof(float);            // at most 49 920 bytes
+    return g;
+}
+
 template <int HPL>
 __global__ void __launch_bounds__(TAP_BLOCK) k_encode_bits(EncArgs a)
 {
@@ -246,17 +267,37 @@ extern "C" int tap_encode_bits(tap_ctx *ctx, const unsigned long long *bits, int
     // the words are loaded one by one; out leaves as float4s
     if (enc_misaligned(bits, 8) || enc_misaligned(out, 16))
         return tap_fail(ctx, TAP_E_INVALID, "encode bits: bits must be 8-byte and out 16-byte aligned");
-    const int planes = rows > 64 ? 2 : 1, hpl = (planes == 1 && H > 64) ? 2 : 1, hck = 64 * hpl;
-    EncArgs a = {bits, weight, bias, out, B, nR, rows, H, planes, 0, 0};
-    a.CT = std::min(nR, 4096 / hck);
-    a.epb = std::max(1, B / 1024);                                         // about four workgroups per CU before a second env
-    const dim3 grid((unsigned)((B + a.epb - 1) / a.epb), (unsigned)((H + hck - 1) / hck));
-    const size_t lds = enc_lds_floats(rows, hck, a.CT) * sizeof(float);   // at most 49 920 bytes
+    const EncGeom geo = enc_geom(B, nR, rows, H);
+    const EncArgs a = {bits, weight, bias, out, B, nR, rows, H, geo.planes, geo.CT, geo.epb};
+    const dim3 grid((unsigned)geo.gx, (unsigned)geo.gy);
     hipStream_t st = (hipStream_t)stream;
-    if (hpl == 1) hipLaunchKernelGGL((k_encode_bits<1>), grid, dim3(TAP_BLOCK), lds, st, a);
-    else hipLaunchKernelGGL((k_encode_bits<2>), grid, dim3(TAP_BLOCK), lds, st, a);
+    if (geo.hpl == 1) hipLaunchKernelGGL((k_encode_bits<1>), grid, dim3(TAP_BLOCK), geo.lds, st, a);
+    else hipLaunchKernelGGL((k_encode_bits<2>), grid, dim3(TAP_BLOCK), geo.lds, st, a);
     TAP_LAUNCH_CHECK(ctx, "k_encode_bits");
-    tap_variant_hit(ctx, TAP_HIT_ENCODE_BITS, 0, hpl, TapVariant{planes, bias ? 1 : 0, 0}, 0);
+    tap_variant_hit(ctx, TAP_HIT_ENCODE_BITS, 0, geo.hpl, TapVariant{geo.planes, bias ? 1 : 0, 0}, 0);
+    return TAP_OK;
+}
+
+// host only: what enc_geom / enc_bw_geom give the launchers, for tests that must know which geometry a batch runs with
+extern "C" int tap_encode_bits_geometry(int B, int nR, int rows, int H, int backward, int32_t out[4])
+{
+    if (!out) return TAP_E_INVALID;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (B < 1 || nR < 1 || rows < 1 || H < 1) return TAP_E_INVALID;
+    if (tap_bits_words(rows, nR) <= 0 || H > 1024) return TAP_E_UNSUPPORTED;
+    if (backward) {
+        const EncBwGeom g = enc_bw_geom(B, nR, rows, H);
+        out[0] = g.per;
+        out[1] = g.slices;
+        out[2] = g.chunks;
+        out[3] = g.hc;
+    } else {
+        const EncGeom g = enc_geom(B, nR, rows, H);
+        out[0] = g.epb;
+        out[1] = g.gx;
+        out[2] = g.gy;
+        out[3] = (int32_t)g.lds;
+    }
     return TAP_OK;
 }
 

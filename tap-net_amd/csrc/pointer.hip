@@ -663,6 +663,21 @@ extern "C" int tap_pointer_scores_backward(tap_ctx *ctx, const float *proj, cons
     return TAP_OK;
 }
 
+// host only: what ptr_geom gives the four launchers, for tests that must know which geometry a batch runs with
+extern "C" int tap_pointer_scores_geometry(int B, int nR, int rows, int Hd, int S, int backward, int32_t out[4])
+{
+    if (!out) return TAP_E_INVALID;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (B < 1 || nR < 1 || rows < 1 || Hd < 1 || S < 0) return TAP_E_INVALID;
+    if (!ptr_shape_ok(nR, rows, Hd) || S > PTR_SMAX) return TAP_E_UNSUPPORTED;
+    const PtrGeom geo = ptr_geom(B, nR, rows, Hd, backward != 0, S);
+    out[0] = geo.epb;
+    out[1] = geo.blocks;
+    out[2] = (int32_t)geo.lds;
+    out[3] = geo.ct;
+    return TAP_OK;
+}
+
 extern "C" int tap_pointer_scores_static(tap_ctx *ctx, const float *xs, const unsigned long long *bits, int B, int nR, int rows, int Hd,
                                          int S, const float *G, const float *g, const float *M, const float *k, const float *q,
                                          const float *va, const float *vp, float *logits_out, float *attn_out, float *t_out,
