@@ -22,7 +22,8 @@
 // cross-lane sums, nothing depends on the batch or the tile.  Backward: none here -- tap_decoder_step_backward from the
 // saved gates, and the encoder's gradients are the caller's (rollout.decoder_step_heightmap recomputes a1 / a2 in torch).
 // Dropout form (tapenv.h: tap_decoder_step_hm_dropout): decoder.hip's two masks at the same place, the encoder untouched;
-// the kernel is a template on its argument struct and the plain instantiation's listing is unchanged.
+// the kernel is a template on its argument struct, and the seed read, the h tile, the cell and q are tap_decoder.h's pieces,
+// the same code k_decoder_step runs.  The two products in front of the cell are written out here (decoder.hip says why).
 #include "tap_decoder.h"
 
 namespace {
@@ -30,12 +31,12 @@ namespace {
 constexpr int TAP_HIT_HEIGHTMAP = 30;       // launch record (tapenv.h: tap_variant_hits), after decoder.hip's 29
 constexpr int HM_MAX_SIDE = 12;             // W, L <= 12: Np <= 9
 
-struct HmArgs {
-    const float *xs, *hm, *h;               // (B, Ks), (B, C, W, L), (B, Hd) or null
+struct HmArgs : DecCellArgs {
+    const float *xs, *hm;                   // (B, Ks), (B, C, W, L)
     const float *w1, *b1, *w2, *b2, *w3, *b3;   // (C1, C), (C1,), (C2, C1), (C2,), (m, C2 Np), (m,)
-    const float *P, *c, *w_hh, *b_hh, *wq;  // (3 Hd, Ks + m), (3 Hd,), (3 Hd, Hd), (3 Hd,), (Hd, Hd)
-    float *h_out, *q_out, *gates_out, *enc_out;   // (B, Hd), (B, Hd), (B, 4, Hd) or null, (B, m) or null
-    int B, Hd, Ks, m, C, W, L, nl, Np;
+    const float *P;                         // (3 Hd, Ks + m)
+    float *enc_out;                         // (B, m) or null
+    int Ks, m, C, W, L, nl, Np;
 };
 
 inline size_t hm_r1_floats(int m, int Np) { return (size_t)DEC_TE * (size_t)std::max(Np * (m / 4), m); }
@@ -46,7 +47,8 @@ inline size_t hm_lds_bytes(int m, int Np, int Hd)
 }
 
 // dec_fill_weights for 64 NG consecutive rows of a matrix of `rows` rows, which need not be a multiple of 64: the rows
-// past it are zeros
+// past it are zeros.  A fill of its own: dec_fill_weights with the row bound as one more argument costs every step kernel
+// 200 to 280 instructions and k_decoder_step three VGPRs
 template <int NG>
 __device__ __forceinline__ void hm_fill_rows(float *lw, const float *W, int ld, int rows, int row0, int k0, int kn, int tid)
 {
@@ -111,8 +113,7 @@ struct HmArgsDrop : HmArgs {
 template <typename A>
 __global__ void __launch_bounds__(TAP_BLOCK) k_decoder_step_hm(A a)
 {
-    constexpr bool DROP = std::is_same<A, HmArgsDrop>::value;
-    extern __shared__ float4 hm_lds4[];                                    // (float4: the 16-byte reads need the base aligned)
+    extern __shared__ float4 hm_lds4[];                                   // (float4: the 16-byte reads need the base aligned)
     const int tid = threadIdx.x, lane = tid & 63, wave = TAP_WAVE_INDEX();
     const int B = a.B, Hd = a.Hd, Ks = a.Ks, m = a.m, Np = a.Np, K = a.Ks + a.m;
     const int C1 = m >> 2, C2 = m >> 1, A1 = Np * C1, T = C2 * Np;         // a1 and a2 floats per env
@@ -121,13 +122,7 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_decoder_step_hm(A a)
     float *a1 = r1, *enc = r1, *a2 = r2, *hl = r2, *hn = r2 + DEC_TE * Hd;
     const int e0 = (int)blockIdx.x * DEC_TE, ew = wave * DEC_E;            // the tile's first env; the wavefront's first env in the tile
     const bool have_h = a.h != nullptr;
-    unsigned seed_lo = 0, seed_hi = 0, episode = 0;
-    if constexpr (DROP) {
-        const unsigned long long seed = (unsigned long long)a.d.state[0];
-        seed_lo = (unsigned)seed;
-        seed_hi = (unsigned)(seed >> 32);
-        episode = (unsigned)(unsigned long long)a.d.state[1];
-    }
+    const DecSeed seed = dec_seed(a);
 
     // ---- the encoder stage --------------------------------------------------------------------------------------------
     // a1[e][p][o] = leaky(b1[o] + sum_c w1[o][c] hm[b][c][4i][4j]), p = i nl + j (zeros for the envs past the batch)
@@ -175,13 +170,8 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_decoder_step_hm(A a)
     __syncthreads();                                                      // a2 has been consumed: h and h' take its place
 
     // ---- the step, as k_decoder_step runs it --------------------------------------------------------------------------
-    // the tile's h rows (zeros for a null h and for the envs past the batch) and its static values, zero-padded to a
-    // block; the first block's barriers publish them
-#pragma unroll 4
-    for (int i = tid; i < DEC_TE * Hd; i += TAP_BLOCK) {
-        const int e = i / Hd, k = i - e * Hd;
-        hl[i] = (have_h && e0 + e < B) ? a.h[(size_t)(e0 + e) * Hd + k] : 0.f;
-    }
+    // the tile's h rows and its static values, zero-padded to a block; the first block's barriers publish them
+    dec_load_h(a, hl, e0, tid);
 #pragma unroll
     for (int it = 0; it < DEC_TE * DEC_KC / TAP_BLOCK; ++it) {
         const int i = it * TAP_BLOCK + tid, e = i / DEC_KC, kk = i - e * DEC_KC, b = e0 + e;
@@ -217,57 +207,50 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_decoder_step_hm(A a)
                 __syncthreads();
                 dec_mac<3>(lw, hl + ew * Hd + k0, Hd, DEC_KC / 4, lane, gh);
             }
-#pragma unroll
-        for (int e = 0; e < DEC_E; ++e) {
-            const int b = e0 + ew + e;
-            const float r = dec_sigmoid(gi[0][e] + gh[0][e]), z = dec_sigmoid(gi[1][e] + gh[1][e]);
-            const float n = tanhf(gi[2][e] + r * gh[2][e]);
-            const float hv = (1.f - z) * n + z * hl[(ew + e) * Hd + j];
-            float h_rnn = hv, h_hh = hv;
-            if constexpr (DROP) {
-                bool keep_rnn, keep_hh;
-                dec_keep(a.d, seed_lo, seed_hi, episode, b, j, keep_rnn, keep_hh);
-                h_rnn = keep_rnn ? hv * a.d.s_rnn : 0.f;
-                h_hh = keep_hh ? hv * a.d.s_hh : 0.f;
-                const unsigned long long w_rnn = __ballot(keep_rnn), w_hh = __ballot(keep_hh);   // the wavefront's 64 rows of env b
-                if (b < B) {
-                    if (lane == 0) {
-                        unsigned long long *kw = a.d.keep + (size_t)b * 2 * (Hd / 64) + jc;
-                        kw[0] = w_rnn;
-                        kw[Hd / 64] = w_hh;
-                    }
-                    if (a.d.rnn_out) a.d.rnn_out[(size_t)b * Hd + j] = h_rnn;
-                }
-            }
-            hn[(ew + e) * Hd + j] = h_rnn;
-            if (b < B) {
-                a.h_out[(size_t)b * Hd + j] = h_hh;
-                if (a.gates_out) {
-                    float *go = a.gates_out + (size_t)b * 4 * Hd + j;
-                    go[0] = r;
-                    go[Hd] = z;
-                    go[2 * Hd] = n;
-                    go[3 * Hd] = gh[2][e];
-                }
-            }
-        }
+        dec_cell(a, seed, gi, gh, hl, hn, e0, ew, jc, lane);
     }
-    // q = Wq . h': the first block's barrier completes h' of the tile
-    for (int jc = 0; jc < Hd / 64; ++jc) {
-        const int j = jc * 64 + lane;
-        float acc[1][DEC_E];
-#pragma unroll
-        for (int e = 0; e < DEC_E; ++e) acc[0][e] = 0.f;
-        for (int k0 = 0; k0 < Hd; k0 += DEC_KC) {
-            __syncthreads();
-            dec_fill_weights<1>(lw, a.wq, Hd, 0, jc * 64, k0, DEC_KC, tid);
-            __syncthreads();
-            dec_mac<1>(lw, hn + ew * Hd + k0, Hd, DEC_KC / 4, lane, acc);
-        }
-#pragma unroll
-        for (int e = 0; e < DEC_E; ++e)
-            if (e0 + ew + e < B) a.q_out[(size_t)(e0 + ew + e) * Hd + j] = acc[0][e];
+    dec_q(a, lw, hn, e0, ew, lane, tid);
+}
+
+// the checks and the launch of both forms: d null = the plain step; form = what its messages add to "height-map"
+int hm_step(tap_ctx *ctx, HmArgs a, const DecDropArgs *d, const char *form, void *stream)
+{
+    const int B = a.B, Hd = a.Hd, Ks = a.Ks, m = a.m, C = a.C, W = a.W, L = a.L;
+    if (B < 0 || Ks < 0 || C < 1 || W < 1 || L < 1 || Hd < 1 || m < 1)
+        return tap_fail(ctx, TAP_E_INVALID, "decoder step (height-map%s): B %d, Ks %d, C %d, W %d, L %d, Hd %d, m %d", form, B, Ks, C, W, L, Hd, m);
+    if (B == 0) return TAP_OK; // an empty batch has no buffers to check
+    if ((Ks > 0 && !a.xs) || !a.hm || !a.w1 || !a.b1 || !a.w2 || !a.b2 || !a.w3 || !a.b3 || !a.P || !a.c || !a.w_hh || !a.b_hh || !a.wq ||
+        !a.h_out || !a.q_out || (d && dec_drop_null(d->state, d->keep)))
+        return tap_fail(ctx, TAP_E_INVALID, "decoder step (height-map%s): null buffer", form);
+    if (!dec_hd_ok(Hd) || (m != Hd && 2 * m != Hd) || (C != 1 && C != 2 && C != 4) || W > HM_MAX_SIDE || L > HM_MAX_SIDE || Ks > 16 ||
+        Ks + m > Hd + 16)
+        return tap_fail(ctx, TAP_E_UNSUPPORTED,
+                        "decoder step (height-map%s): Ks %d, C %d, W %d, L %d, m %d, Hd %d (needs Hd 64, 128 or 256, m = Hd / 2 or Hd, C 1, 2 or 4, "
+                        "W and L <= 12, Ks <= 16 and Ks + m <= Hd + 16)", form, Ks, C, W, L, m, Hd);
+    const void *f32[] = {a.xs, a.hm, a.h, a.w1, a.b1, a.w2, a.b2, a.w3, a.b3, a.P, a.c, a.w_hh, a.b_hh, a.wq, a.h_out, a.q_out, a.gates_out,
+                         a.enc_out, d ? d->rnn_out : nullptr};
+    bool bad = d && dec_drop_misaligned(d->state, d->keep);
+    for (const void *p : f32) bad = bad || dec_misaligned(p);
+    if (bad)
+        return tap_fail(ctx, TAP_E_INVALID, "decoder step (height-map%s): every %s", form,
+                        d ? "float buffer must be 4-byte aligned, state and keep_out 8-byte" : "buffer must be 4-byte aligned");
+    a.nl = (L + 3) / 4;
+    a.Np = ((W + 3) / 4) * a.nl;
+    const size_t lds = hm_lds_bytes(m, a.Np, Hd);
+    if (lds > tap_lds_limit(ctx))
+        return tap_fail(ctx, TAP_E_UNSUPPORTED, "decoder step (height-map%s): %zu bytes of LDS for m %d, Np %d, Hd %d do not fit a workgroup", form,
+                        lds, m, a.Np, Hd);
+    const dim3 blocks((unsigned)((B + DEC_TE - 1) / DEC_TE));
+    if (d) {
+        TAP_HIP_CHECK(ctx, tap_allow_lds(k_decoder_step_hm<HmArgsDrop>, lds));
+        hipLaunchKernelGGL(k_decoder_step_hm<HmArgsDrop>, blocks, dim3(TAP_BLOCK), lds, (hipStream_t)stream, HmArgsDrop{a, *d});
+    } else {
+        TAP_HIP_CHECK(ctx, tap_allow_lds(k_decoder_step_hm<HmArgs>, lds));
+        hipLaunchKernelGGL(k_decoder_step_hm<HmArgs>, blocks, dim3(TAP_BLOCK), lds, (hipStream_t)stream, a);
     }
+    TAP_LAUNCH_CHECK(ctx, d ? "k_decoder_step_hm<dropout>" : "k_decoder_step_hm");
+    tap_variant_hit(ctx, TAP_HIT_HEIGHTMAP, C, a.Np, TapVariant{Hd / 64, a.h ? 1 : 0, d ? 2 : 0}, 0);
+    return TAP_OK;
 }
 
 } // namespace
@@ -277,32 +260,8 @@ extern "C" int tap_decoder_step_hm(tap_ctx *ctx, const float *xs, int Ks, const 
                                    const float *b3, const float *P, const float *c, const float *w_hh, const float *b_hh, const float *wq,
                                    float *h_out, float *q_out, float *gates_out, float *enc_out, void *stream)
 {
-    if (B < 0 || Ks < 0 || C < 1 || W < 1 || L < 1 || Hd < 1 || m < 1)
-        return tap_fail(ctx, TAP_E_INVALID, "decoder step (height-map): B %d, Ks %d, C %d, W %d, L %d, Hd %d, m %d", B, Ks, C, W, L, Hd, m);
-    if (B == 0) return TAP_OK; // an empty batch has no buffers to check
-    if ((Ks > 0 && !xs) || !hm || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !P || !c || !w_hh || !b_hh || !wq || !h_out || !q_out)
-        return tap_fail(ctx, TAP_E_INVALID, "decoder step (height-map): null buffer");
-    if (!dec_hd_ok(Hd) || (m != Hd && 2 * m != Hd) || (C != 1 && C != 2 && C != 4) || W > HM_MAX_SIDE || L > HM_MAX_SIDE || Ks > 16 ||
-        Ks + m > Hd + 16)
-        return tap_fail(ctx, TAP_E_UNSUPPORTED,
-                        "decoder step (height-map): Ks %d, C %d, W %d, L %d, m %d, Hd %d (needs Hd 64, 128 or 256, m = Hd / 2 or Hd, C 1, 2 or 4, "
-                        "W and L <= 12, Ks <= 16 and Ks + m <= Hd + 16)", Ks, C, W, L, m, Hd);
-    const void *f32[] = {xs, hm, h, w1, b1, w2, b2, w3, b3, P, c, w_hh, b_hh, wq, h_out, q_out, gates_out, enc_out};
-    bool bad = false;
-    for (const void *p : f32) bad = bad || dec_misaligned(p);
-    if (bad) return tap_fail(ctx, TAP_E_INVALID, "decoder step (height-map): every buffer must be 4-byte aligned");
-    const int nw = (W + 3) / 4, nl = (L + 3) / 4, Np = nw * nl;
-    const size_t lds = hm_lds_bytes(m, Np, Hd);
-    if (lds > tap_lds_limit(ctx))
-        return tap_fail(ctx, TAP_E_UNSUPPORTED, "decoder step (height-map): %zu bytes of LDS for m %d, Np %d, Hd %d do not fit a workgroup", lds, m,
-                        Np, Hd);
-    const HmArgs a = {xs, hm, h, w1, b1, w2, b2, w3, b3, P, c, w_hh, b_hh, wq, h_out, q_out, gates_out, enc_out, B, Hd, Ks, m, C, W, L, nl, Np};
-    const unsigned blocks = (unsigned)((B + DEC_TE - 1) / DEC_TE);
-    TAP_HIP_CHECK(ctx, tap_allow_lds(k_decoder_step_hm<HmArgs>, lds));
-    hipLaunchKernelGGL(k_decoder_step_hm<HmArgs>, dim3(blocks), dim3(TAP_BLOCK), lds, (hipStream_t)stream, a);
-    TAP_LAUNCH_CHECK(ctx, "k_decoder_step_hm");
-    tap_variant_hit(ctx, TAP_HIT_HEIGHTMAP, C, Np, TapVariant{Hd / 64, h ? 1 : 0, 0}, 0);
-    return TAP_OK;
+    return hm_step(ctx, {{h, c, w_hh, b_hh, wq, h_out, q_out, gates_out, B, Hd}, xs, hm, w1, b1, w2, b2, w3, b3, P, enc_out, Ks, m, C, W, L, 0, 0},
+                   nullptr, "", stream);
 }
 
 extern "C" int tap_decoder_step_hm_dropout(tap_ctx *ctx, const float *xs, int Ks, const float *hm, int C, int W, int L, const float *h, int B,
@@ -312,33 +271,7 @@ extern "C" int tap_decoder_step_hm_dropout(tap_ctx *ctx, const float *xs, int Ks
                                            uint32_t thr_rnn, uint32_t thr_hh, float s_rnn, float s_hh, float *h_out, float *q_out,
                                            float *gates_out, float *enc_out, float *rnn_out, int64_t *keep_out, void *stream)
 {
-    if (B < 0 || Ks < 0 || C < 1 || W < 1 || L < 1 || Hd < 1 || m < 1)
-        return tap_fail(ctx, TAP_E_INVALID, "decoder step (height-map, dropout): B %d, Ks %d, C %d, W %d, L %d, Hd %d, m %d", B, Ks, C, W, L, Hd, m);
-    if (B == 0) return TAP_OK; // an empty batch has no buffers to check
-    if ((Ks > 0 && !xs) || !hm || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !P || !c || !w_hh || !b_hh || !wq || !h_out || !q_out ||
-        dec_drop_null(state, keep_out))
-        return tap_fail(ctx, TAP_E_INVALID, "decoder step (height-map, dropout): null buffer");
-    if (!dec_hd_ok(Hd) || (m != Hd && 2 * m != Hd) || (C != 1 && C != 2 && C != 4) || W > HM_MAX_SIDE || L > HM_MAX_SIDE || Ks > 16 ||
-        Ks + m > Hd + 16)
-        return tap_fail(ctx, TAP_E_UNSUPPORTED,
-                        "decoder step (height-map, dropout): Ks %d, C %d, W %d, L %d, m %d, Hd %d (needs Hd 64, 128 or 256, m = Hd / 2 or Hd, "
-                        "C 1, 2 or 4, W and L <= 12, Ks <= 16 and Ks + m <= Hd + 16)", Ks, C, W, L, m, Hd);
-    const void *f32[] = {xs, hm, h, w1, b1, w2, b2, w3, b3, P, c, w_hh, b_hh, wq, h_out, q_out, gates_out, enc_out, rnn_out};
-    bool bad = dec_drop_misaligned(state, keep_out);
-    for (const void *p : f32) bad = bad || dec_misaligned(p);
-    if (bad)
-        return tap_fail(ctx, TAP_E_INVALID, "decoder step (height-map, dropout): every float buffer must be 4-byte aligned, state and keep_out 8-byte");
-    const int nw = (W + 3) / 4, nl = (L + 3) / 4, Np = nw * nl;
-    const size_t lds = hm_lds_bytes(m, Np, Hd);
-    if (lds > tap_lds_limit(ctx))
-        return tap_fail(ctx, TAP_E_UNSUPPORTED, "decoder step (height-map, dropout): %zu bytes of LDS for m %d, Np %d, Hd %d do not fit a workgroup",
-                        lds, m, Np, Hd);
-    const HmArgsDrop a = {{xs, hm, h, w1, b1, w2, b2, w3, b3, P, c, w_hh, b_hh, wq, h_out, q_out, gates_out, enc_out, B, Hd, Ks, m, C, W, L, nl, Np},
-                          {(const long long *)state, (unsigned long long *)keep_out, rnn_out, step, env_offset, thr_rnn, thr_hh, s_rnn, s_hh}};
-    const unsigned blocks = (unsigned)((B + DEC_TE - 1) / DEC_TE);
-    TAP_HIP_CHECK(ctx, tap_allow_lds(k_decoder_step_hm<HmArgsDrop>, lds));
-    hipLaunchKernelGGL(k_decoder_step_hm<HmArgsDrop>, dim3(blocks), dim3(TAP_BLOCK), lds, (hipStream_t)stream, a);
-    TAP_LAUNCH_CHECK(ctx, "k_decoder_step_hm<dropout>");
-    tap_variant_hit(ctx, TAP_HIT_HEIGHTMAP, C, Np, TapVariant{Hd / 64, h ? 1 : 0, 2}, 0);
-    return TAP_OK;
+    const DecDropArgs d = {(const long long *)state, (unsigned long long *)keep_out, rnn_out, step, env_offset, thr_rnn, thr_hh, s_rnn, s_hh};
+    return hm_step(ctx, {{h, c, w_hh, b_hh, wq, h_out, q_out, gates_out, B, Hd}, xs, hm, w1, b1, w2, b2, w3, b3, P, enc_out, Ks, m, C, W, L, 0, 0},
+                   &d, ", dropout", stream);
 }

@@ -1,6 +1,7 @@
 // tap_decoder.h -- what the decoder-step kernels share (decoder.hip: k_decoder_step; heightmap.hip: k_decoder_step_hm): the
 // tile geometry, the weight-block fill and the multiply-accumulate of a (64 rows x NG gates) x (DEC_E envs) register
-// tile.  decoder.hip's opening comment describes the geometry.
+// tile; the step's own pieces -- seed read, h tile, GRU cell with the two dropout masks, q -- on the kernels' argument
+// structs; the body of the element-wise backward.  decoder.hip's opening comment describes the geometry.
 #pragma once
 #include "tap_common.h"
 
@@ -101,6 +102,155 @@ __device__ __forceinline__ void dec_keep(const DecDropArgs &d, unsigned seed_lo,
     const uint2 w = dec_philox2(d.env_offset + (unsigned)b, (unsigned)j, d.step, episode, seed_lo, seed_hi);
     keep_rnn = w.x >= d.thr_rnn;
     keep_hh = w.y >= d.thr_hh;
+}
+
+// ---- the step's pieces, shared by k_decoder_step and k_decoder_step_hm -------------------------------------------------
+// What the pieces read of a step kernel's argument struct: DecArgs and HmArgs derive from it and add their own inputs.
+struct DecCellArgs {
+    const float *h;                         // (B, Hd) or null
+    const float *c, *w_hh, *b_hh, *wq;      // (3 Hd,), (3 Hd, Hd), (3 Hd,), (Hd, Hd)
+    float *h_out, *q_out, *gates_out;       // (B, Hd), (B, Hd), (B, 4, Hd) or null
+    int B, Hd;
+};
+
+// the dropout form of an argument struct is the struct plus a DecDropArgs member d: this is what DROP means, to the kernels
+// and to every piece below
+template <typename A, typename = void> struct dec_has_drop : std::false_type {};
+template <typename A> struct dec_has_drop<A, std::enable_if_t<std::is_same<decltype(A::d), DecDropArgs>::value>> : std::true_type {};
+
+struct DecSeed {
+    unsigned lo, hi, episode;
+};
+
+// the launch's (seed, episode), read from device memory; the plain form reads nothing
+template <typename A>
+__device__ __forceinline__ DecSeed dec_seed(const A &a)
+{
+    static_assert(std::is_base_of<DecCellArgs, A>::value, "a step kernel's arguments derive from DecCellArgs");
+    DecSeed s = {0, 0, 0};
+    if constexpr (dec_has_drop<A>::value) {
+        const unsigned long long seed = (unsigned long long)a.d.state[0];
+        s.lo = (unsigned)seed;
+        s.hi = (unsigned)(seed >> 32);
+        s.episode = (unsigned)(unsigned long long)a.d.state[1];
+    }
+    return s;
+}
+
+// the tile's h rows (zeros for a null h and for the envs past the batch) -> hl; the caller's next barrier publishes them
+__device__ __forceinline__ void dec_load_h(const DecCellArgs &a, float *hl, int e0, int tid)
+{
+    const int B = a.B, Hd = a.Hd;
+    const bool have_h = a.h != nullptr;
+#pragma unroll 4
+    for (int i = tid; i < DEC_TE * Hd; i += TAP_BLOCK) {
+        const int e = i / Hd, k = i - e * Hd;
+        hl[i] = (have_h && e0 + e < B) ? a.h[(size_t)(e0 + e) * Hd + k] : 0.f;
+    }
+}
+
+// The GRU cell of the 64-row chunk jc for the wavefront's DEC_E envs, from the finished sums gi and gh: r, z, n and h'; under
+// dropout the two masks applied where h' leaves the registers, the wavefront's 64 rows of an env one ballot = one keep word;
+// h' (as q reads it) to the hn tile, h_out and the gates to global memory.
+template <typename A>
+__device__ __forceinline__ void dec_cell(const A &a, const DecSeed &s, const float (&gi)[3][DEC_E], const float (&gh)[3][DEC_E],
+                                         const float *hl, float *hn, int e0, int ew, int jc, int lane)
+{
+    const int B = a.B, Hd = a.Hd, j = jc * 64 + lane;
+#pragma unroll
+    for (int e = 0; e < DEC_E; ++e) {
+        const int b = e0 + ew + e;
+        const float r = dec_sigmoid(gi[0][e] + gh[0][e]), z = dec_sigmoid(gi[1][e] + gh[1][e]);
+        const float n = tanhf(gi[2][e] + r * gh[2][e]);
+        const float hv = (1.f - z) * n + z * hl[(ew + e) * Hd + j];
+        float h_rnn = hv, h_hh = hv;
+        if constexpr (dec_has_drop<A>::value) {
+            bool keep_rnn, keep_hh;
+            dec_keep(a.d, s.lo, s.hi, s.episode, b, j, keep_rnn, keep_hh);
+            h_rnn = keep_rnn ? hv * a.d.s_rnn : 0.f;
+            h_hh = keep_hh ? hv * a.d.s_hh : 0.f;
+            const unsigned long long w_rnn = __ballot(keep_rnn), w_hh = __ballot(keep_hh);   // the wavefront's 64 rows of env b
+            if (b < B) {
+                if (lane == 0) {
+                    unsigned long long *kw = a.d.keep + (size_t)b * 2 * (Hd / 64) + jc;
+                    kw[0] = w_rnn;
+                    kw[Hd / 64] = w_hh;
+                }
+                if (a.d.rnn_out) a.d.rnn_out[(size_t)b * Hd + j] = h_rnn;
+            }
+        }
+        hn[(ew + e) * Hd + j] = h_rnn;
+        if (b < B) {
+            a.h_out[(size_t)b * Hd + j] = h_hh;
+            if (a.gates_out) {
+                float *go = a.gates_out + (size_t)b * 4 * Hd + j;
+                go[0] = r;
+                go[Hd] = z;
+                go[2 * Hd] = n;
+                go[3 * Hd] = gh[2][e];
+            }
+        }
+    }
+}
+
+// q = Wq . h' from the hn tile: the first block's barrier completes h' of the tile
+__device__ __forceinline__ void dec_q(const DecCellArgs &a, float *lw, const float *hn, int e0, int ew, int lane, int tid)
+{
+    const int B = a.B, Hd = a.Hd;
+    for (int jc = 0; jc < Hd / 64; ++jc) {
+        const int j = jc * 64 + lane;
+        float acc[1][DEC_E];
+#pragma unroll
+        for (int e = 0; e < DEC_E; ++e) acc[0][e] = 0.f;
+        for (int k0 = 0; k0 < Hd; k0 += DEC_KC) {
+            __syncthreads();
+            dec_fill_weights<1>(lw, a.wq, Hd, 0, jc * 64, k0, DEC_KC, tid);
+            __syncthreads();
+            dec_mac<1>(lw, hn + ew * Hd + k0, Hd, DEC_KC / 4, lane, acc);
+        }
+#pragma unroll
+        for (int e = 0; e < DEC_E; ++e)
+            if (e0 + ew + e < B) a.q_out[(size_t)(e0 + ew + e) * Hd + j] = acc[0][e];
+    }
+}
+
+// ---- the element-wise backward of a step, from the saved gates ----------------------------------------------------------
+// from h' = (1 - z) n + z h, n = tanh(gi_n + r gh_n), r / z = sigmoid(gi + gh): per element
+//   carry = g z;  da_n = g (1 - z) (1 - n^2);  dgh_n = da_n r;  da_r = da_n gh_n r (1 - r);  da_z = g (h - n) z (1 - z)
+// DROP = false: g = g_h (g_r, keep and the scales are not read).  DROP = true, a step that ran with dropout: last_hh =
+// drop_hh(h') and rnn_out = drop_rnn(h') both hang on h', so the gradient arriving at h' is g = keep_hh s_hh g_h + keep_rnn
+// s_rnn g_r (g_r = g_q . wq, the caller's matmul), each product and the sum rounded; a dropped element contributes an exact zero
+// The body of decoder.hip's two kernels, which keep an argument list each: the plain one's listing is then what it was
+template <bool DROP>
+__device__ __forceinline__ void dec_step_bw(const float *gates, const float *h, const float *g_h, const float *g_r, const unsigned long long *keep,
+                                            float s_rnn, float s_hh, float *dgi, float *dghn, float *carry, size_t total, int Hd)
+{
+    const size_t i = (size_t)blockIdx.x * TAP_BLOCK + threadIdx.x;
+    if (i >= total) return;
+    const size_t b = i / (size_t)Hd;
+    const int j = (int)(i - b * (size_t)Hd);
+    bool keep_rnn = true, keep_hh = true;
+    if constexpr (DROP) {
+        const int nw = Hd >> 6;
+        const unsigned long long *kw = keep + b * 2 * (size_t)nw + (j >> 6);
+        keep_rnn = (kw[0] >> (j & 63)) & 1;
+        keep_hh = (kw[nw] >> (j & 63)) & 1;
+    }
+    const float *gp = gates + b * 4 * (size_t)Hd + j;
+    const float r = gp[0], z = gp[Hd], n = gp[2 * Hd], ghn = gp[3 * Hd];
+    float g;
+    if constexpr (DROP)
+        g = (keep_hh ? s_hh * g_h[i] : 0.f) + (keep_rnn ? s_rnn * g_r[i] : 0.f);
+    else
+        g = g_h[i];
+    const float hp = h ? h[i] : 0.f;
+    const float dan = g * (1.f - z) * (1.f - n * n);
+    float *dp = dgi + b * 3 * (size_t)Hd + j;
+    dp[0] = dan * ghn * (r * (1.f - r));
+    dp[Hd] = g * (hp - n) * (z * (1.f - z));
+    dp[2 * Hd] = dan;
+    dghn[i] = dan * r;
+    carry[i] = g * z;
 }
 
 // the host side's checks of a dropout launch's own arguments

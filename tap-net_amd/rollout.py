@@ -124,9 +124,14 @@ class BestRatioPolicy(object):
         return best
 
 
-def _as_f32(t, dev):
-    if t.dtype is not torch.float32 or not t.is_contiguous() or t.device != dev:
-        t = t.to(device=dev, dtype=torch.float32).contiguous()
+def _prep_f32(t, dev):
+    """``t`` as a contiguous float32 tensor on ``dev`` (None stays None); the cast is ``.float()``, so autograd sees it"""
+    if t is None:
+        return None
+    if t.dtype is not torch.float32:
+        t = t.float()
+    if not t.is_contiguous() or t.device != dev:
+        t = t.to(dev).contiguous()
     return t
 
 
@@ -159,7 +164,7 @@ class _PointerPick(torch.autograd.Function):
     @staticmethod
     def backward(ctx, _g_ptr, g, _g_probs):
         probs, ptr, logp = ctx.saved_tensors
-        g = _as_f32(g, probs.device)
+        g = _prep_f32(g, probs.device)
         B, nR = probs.shape
         out = torch.empty_like(probs)
         c = _lib.ctx(probs.device)
@@ -190,12 +195,9 @@ def pointer_pick(logits, mask, u=None, want_probs=False):
         raise ValueError("mask must be (%d, %d), got %s" % (B, nR, tuple(mask.shape)))
     if u is not None and tuple(u.shape) != (B,):
         raise ValueError("u must be (%d,), got %s" % (B, tuple(u.shape)))
-    if logits.dtype is not torch.float32:
-        logits = logits.float()
-    if not logits.is_contiguous() or logits.device != dev:
-        logits = logits.to(dev).contiguous()
-    mask = _as_f32(mask.detach(), dev)
-    u = None if u is None else _as_f32(u.detach(), dev)
+    logits = _prep_f32(logits, dev)
+    mask = _prep_f32(mask.detach(), dev)
+    u = None if u is None else _prep_f32(u.detach(), dev)
     if torch.is_grad_enabled() and logits.requires_grad:
         ptr, logp, probs = _PointerPick.apply(logits, mask, u)
     else:
@@ -237,7 +239,7 @@ class _EncodeBits(torch.autograd.Function):
         bits, = ctx.saved_tensors
         B, nR, rows, H = ctx.shape
         dev = bits.device
-        g = _as_f32(g, dev)
+        g = _prep_f32(g, dev)
         L, c = _lib.lib(), _lib.ctx(dev)
         dweight = torch.empty(H, rows, dtype=torch.float32, device=dev)
         dbias = torch.empty(H, dtype=torch.float32, device=dev) if ctx.has_bias and ctx.needs_input_grad[2] else None
@@ -289,15 +291,8 @@ def encode_dynamic_bits(bits, weight, bias=None, rows=None):
     dev = _lib.resolve_device(bits.device)
     if not bits.is_contiguous() or bits.device != dev:
         bits = bits.to(dev).contiguous()
-
-    def prep(t):
-        if t.dtype is not torch.float32:
-            t = t.float()
-        if not t.is_contiguous() or t.device != dev:
-            t = t.to(dev).contiguous()
-        return t
-    weight = prep(weight)
-    bias = None if bias is None else prep(bias)
+    weight = _prep_f32(weight, dev)
+    bias = _prep_f32(bias, dev)
     if torch.is_grad_enabled() and (weight.requires_grad or (bias is not None and bias.requires_grad)):
         return _EncodeBits.apply(bits, weight, bias, rows, nR)
     out = torch.empty(B, H, nR, dtype=torch.float32, device=dev)
@@ -355,7 +350,7 @@ class _PointerScores(torch.autograd.Function):
             for z in (dva, dvp, dM, dk):
                 z.zero_()
             return dU.view(B, 3, Hd, nR).transpose(2, 3), None, dM, dk, dq, dva, dvp, None
-        g = _as_f32(g, dev)
+        g = _prep_f32(g, dev)
         need = int(L.tap_pointer_scores_backward_scratch(B, nR, rows, Hd))
         need2 = int(L.tap_encode_bits_backward_scratch(B, nR, rows, 3 * Hd))
         scratch = torch.empty(max(need, need2, 16) // 4, dtype=torch.float32, device=dev)
@@ -408,14 +403,7 @@ def pointer_scores(proj, bits, M, k, q, va, vp, rows=None):
     dev = _lib.resolve_device(bits.device)
     if not bits.is_contiguous() or bits.device != dev:
         bits = bits.to(dev).contiguous()
-
-    def prep(t):
-        if t.dtype is not torch.float32:
-            t = t.float()
-        if not t.is_contiguous() or t.device != dev:
-            t = t.to(dev).contiguous()
-        return t
-    args = [prep(v) for v in (proj, M, k, q, va, vp)]
+    args = [_prep_f32(v, dev) for v in (proj, M, k, q, va, vp)]
     if torch.is_grad_enabled() and any(v.requires_grad for v in args):
         return _PointerScores.apply(args[0], bits, *args[1:], rows)
     proj, M, k, q, va, vp = (v.detach() for v in args)
@@ -473,7 +461,7 @@ class _PointerScoresStatic(torch.autograd.Function):
             for z in (dva, dvp, dM, dk):
                 z.zero_()
             return None, None, torch.zeros_like(G), dk, dM, dk.clone(), dq, dva, dvp, None
-        grad = _as_f32(grad, dev)
+        grad = _prep_f32(grad, dev)
         dU = f(B, 3 * Hd, nR)
         need = int(L.tap_pointer_scores_static_backward_scratch(B, nR, rows, Hd, S))
         need2 = int(L.tap_encode_bits_backward_scratch(B, nR, rows, 3 * Hd))
@@ -531,15 +519,8 @@ def pointer_scores_static(xs, bits, G, g, M, k, q, va, vp, rows=None):
     dev = _lib.resolve_device(bits.device)
     if not bits.is_contiguous() or bits.device != dev:
         bits = bits.to(dev).contiguous()
-
-    def prep(t):
-        if t.dtype is not torch.float32:
-            t = t.float()
-        if not t.is_contiguous() or t.device != dev:
-            t = t.to(dev).contiguous()
-        return t
-    xs = prep(xs.detach())
-    args = [prep(v) for v in (G, g, M, k, q, va, vp)]
+    xs = _prep_f32(xs.detach(), dev)
+    args = [_prep_f32(v, dev) for v in (G, g, M, k, q, va, vp)]
     if torch.is_grad_enabled() and any(v.requires_grad for v in args):
         return _PointerScoresStatic.apply(xs, bits, *args, rows)
     args = [v.detach() for v in args]
@@ -603,7 +584,7 @@ class _CriticValue(torch.autograd.Function):
         if B == 0:
             zero = lambda t: torch.zeros_like(t)
             return None, None, zero(G), zero(g), zero(M), f(q0_rows, H).zero_(), zero(v), zero(w2), f(1).zero_(), None, None
-        gv = _as_f32(gv, dev)
+        gv = _prep_f32(gv, dev)
         relu = z.clamp_min(0)
         dz = gv.unsqueeze(1) * w2.unsqueeze(0) * (z > 0).to(torch.float32)
         dU, dq, dv, dM, dk = f(B, H, nR), f(B, n, H), f(H), f(H, rows), f(H)
@@ -672,15 +653,8 @@ def critic_value(x, bits, G, g, M, q0, v, w2, b2, blocks, rows=None):
     dev = _lib.resolve_device(bits.device)
     if not bits.is_contiguous() or bits.device != dev:
         bits = bits.to(dev).contiguous()
-
-    def prep(t):
-        if t.dtype is not torch.float32:
-            t = t.float()
-        if not t.is_contiguous() or t.device != dev:
-            t = t.to(dev).contiguous()
-        return t
-    x = prep(x.detach())
-    args = [prep(t) for t in (G, g, M, q0, v, w2, b2)]
+    x = _prep_f32(x.detach(), dev)
+    args = [_prep_f32(t, dev) for t in (G, g, M, q0, v, w2, b2)]
     if torch.is_grad_enabled() and any(t.requires_grad for t in args):
         return _CriticValue.apply(x, bits, *args, blocks, rows)
     args = [t.detach() for t in args]
@@ -845,99 +819,92 @@ def _decoder_dropout_backward_into(gates, h, g_h, g_r, keep, s_rnn, s_hh, dgi, d
                                                             p(dghn), p(carry), _lib.stream_of(dev)), c_)
 
 
-def _dropout_backward_launch(gates, h, g_h, g_q, wq, keep, scales):
-    """the element-wise part of a dropout step's backward -> g_q (float32), dgi, dgh, carry"""
+def _step_outputs(B, Hd, dev, drop, grad):
+    """what a step's launch writes -> h_new, q, gates, rnn_out, keep: ``gates`` only for a backward (``grad``), ``rnn_out`` only
+    for the backward of a dropout step, the keep words for every dropout step (its launch always writes them) -- the plain
+    forms allocate neither"""
+    f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    return (f(B, Hd), f(B, Hd), f(B, 4, Hd) if grad else None, f(B, Hd) if grad and drop is not None else None,
+            None if drop is None else torch.empty(B, 2, Hd // 64, dtype=torch.int64, device=dev))
+
+
+def _step_no_grad(launch, args, drop, B, Hd, dev):
+    """a step outside autograd: ``launch`` (_decoder_launch or _decoder_hm_launch) on the detached ``args``, nothing kept"""
+    h_new, q, _, _, keep = _step_outputs(B, Hd, dev, drop, False)
+    launch([None if v is None else v.detach() for v in args], drop, h_new, q, None, None, keep)
+    return h_new, q
+
+
+def _step_backward_launch(gates, h, g_h, g_q, wq, keep, scales):
+    """the element-wise part of a step's backward -> g_q (float32), dgi, dgh, carry.  ``keep`` None, the plain step: q = h' .
+    wq^T, so wq^T . dq joins the gradient arriving at h' here, g = g_h + g_q . wq.  A dropout step: the two masks join g_h
+    and g_r = g_q . wq at h' inside the launch."""
     B, Hd = int(gates.shape[0]), int(gates.shape[2])
     dev = gates.device
-    g_q = _as_f32(g_q, dev)
+    g_q = _prep_f32(g_q, dev)
     dgi = torch.empty(B, 3 * Hd, dtype=torch.float32, device=dev)
     dghn = torch.empty(B, Hd, dtype=torch.float32, device=dev)
     carry = torch.empty(B, Hd, dtype=torch.float32, device=dev)
-    _decoder_dropout_backward_into(gates, h, _as_f32(g_h, dev), g_q.matmul(wq), keep, scales[0], scales[1], dgi, dghn, carry)
-    return g_q, dgi, torch.cat((dgi[:, :2 * Hd], dghn), dim=1), carry
+    if keep is None:
+        _decoder_backward_into(gates, h, _prep_f32(g_h, dev) + g_q.matmul(wq), dgi, dghn, carry)
+    else:
+        _decoder_dropout_backward_into(gates, h, _prep_f32(g_h, dev), g_q.matmul(wq), keep, scales[0], scales[1], dgi, dghn, carry)
+    return g_q, dgi, torch.cat((dgi[:, :2 * Hd], dghn), dim=1), carry            # the r and z parts of dgh are those of dgi
 
 
-class _DecoderStepDropout(torch.autograd.Function):
-    """decoder_step(dropout=...) under autograd: forward = the dropout launch with gates, rnn_out = drop_rnn(h') and the keep
-    words kept; backward = tap_decoder_step_dropout_backward (element-wise: the two masks join g_h and g_q . wq at h') and
-    _DecoderStep's matmuls, with dwq = g_q^T . rnn_out.  The state tensor is NOT kept -- the masks are, so advancing the
-    episode cannot change a pending backward.  Inputs by reference, as _DecoderStep."""
+def _step_grads(need, xs, xd, h, hq, P, w_hh, g_q, dgi, dgh, carry):
+    """the sums over the batch of a step's backward, as matmuls -> dxs, dxd, dh, dP, dc, dw_hh, db_hh, dwq (None where ``need``,
+    eight flags in that order, does not ask).  ``xd`` is the dynamic half of the GRU's input -- the height-map step's enc --,
+    ``hq`` what q was formed from: h', or drop_rnn(h') of a dropout step."""
+    Ks = 0 if xs is None else int(xs.shape[1])
+    x = xd if xs is None else xs if xd is None else torch.cat((xs, xd), dim=1)
+    dxs = dgi.matmul(P[:, :Ks]) if xs is not None and need[0] else None
+    dxd = dgi.matmul(P[:, Ks:]) if xd is not None and need[1] else None
+    dh = carry + dgh.matmul(w_hh) if h is not None and need[2] else None
+    dP = dgi.t().matmul(x) if need[3] else None
+    dc = dgi.sum(0) if need[4] else None
+    dw_hh = (torch.zeros_like(w_hh) if h is None else dgh.t().matmul(h)) if need[5] else None
+    db_hh = dgh.sum(0) if need[6] else None
+    dwq = g_q.t().matmul(hq) if need[7] else None
+    return dxs, dxd, dh, dP, dc, dw_hh, db_hh, dwq
+
+
+def _drop_scales(drop):
+    return None if drop is None else (dropout_scale(drop.p_rnn), dropout_scale(drop.p_hh))
+
+
+def _decoder_launch(args, drop, h_new, q, gates, rnn_out, keep):
+    """the plain or the dropout launch of a step on prepared ``args`` = xs, xd, h, P, c, w_hh, b_hh, wq"""
+    if drop is None:
+        _decoder_into(*args, h_new, q, gates)
+    else:
+        _decoder_dropout_into(*args, drop, h_new, q, gates, rnn_out, keep)
+
+
+class _DecoderStep(torch.autograd.Function):
+    """decoder_step and decoder_step_dropout under autograd (``drop`` None or the checked record): forward = the one launch
+    with the gates kept, backward = tap_decoder_step_backward (element-wise) and the sums over the batch as matmuls.  What a
+    step keeps: xs, xd and h BY REFERENCE (a stepper hands out private copies of its decoder buffers while grad is enabled,
+    and h is the previous step's own output), h', and gates (B, 4, Hd) = r, z, n, gh_n; the parameters by reference.
+    A dropout step keeps rnn_out = drop_rnn(h') in h''s place (dwq = g_q^T . rnn_out) and the keep words; its backward is
+    tap_decoder_step_dropout_backward.  The state tensor is NOT kept -- the masks are, so advancing the episode cannot change
+    a pending backward."""
 
     @staticmethod
     def forward(ctx, xs, xd, h, P, c, w_hh, b_hh, wq, drop):
         B = int((xs if xs is not None else xd).shape[0])
-        Hd, dev = int(wq.shape[0]), P.device
-        h_new = torch.empty(B, Hd, dtype=torch.float32, device=dev)
-        q = torch.empty(B, Hd, dtype=torch.float32, device=dev)
-        gates = torch.empty(B, 4, Hd, dtype=torch.float32, device=dev)
-        rnn_out = torch.empty(B, Hd, dtype=torch.float32, device=dev)
-        keep = torch.empty(B, 2, Hd // 64, dtype=torch.int64, device=dev)
-        _decoder_dropout_into(xs, xd, h, P, c, w_hh, b_hh, wq, drop, h_new, q, gates, rnn_out, keep)
-        ctx.save_for_backward(xs, xd, h, gates, rnn_out, keep, P, w_hh, wq)
-        ctx.scales = (dropout_scale(drop.p_rnn), dropout_scale(drop.p_hh))
+        h_new, q, gates, rnn_out, keep = _step_outputs(B, int(wq.shape[0]), P.device, drop, True)
+        _decoder_launch((xs, xd, h, P, c, w_hh, b_hh, wq), drop, h_new, q, gates, rnn_out, keep)
+        ctx.save_for_backward(xs, xd, h, h_new if drop is None else rnn_out, gates, P, w_hh, wq, keep)
+        ctx.scales = _drop_scales(drop)
         return h_new, q
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_h, g_q):
-        xs, xd, h, gates, rnn_out, keep, P, w_hh, wq = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        g_q, dgi, dgh, carry = _dropout_backward_launch(gates, h, g_h, g_q, wq, keep, ctx.scales)
-        Ks = 0 if xs is None else int(xs.shape[1])
-        x = xd if xs is None else xs if xd is None else torch.cat((xs, xd), dim=1)
-        dxs = dgi.matmul(P[:, :Ks]) if xs is not None and need[0] else None
-        dxd = dgi.matmul(P[:, Ks:]) if xd is not None and need[1] else None
-        dh = carry + dgh.matmul(w_hh) if h is not None and need[2] else None
-        dP = dgi.t().matmul(x) if need[3] else None
-        dc = dgi.sum(0) if need[4] else None
-        dw_hh = (torch.zeros_like(w_hh) if h is None else dgh.t().matmul(h)) if need[5] else None
-        db_hh = dgh.sum(0) if need[6] else None
-        dwq = g_q.t().matmul(rnn_out) if need[7] else None
-        return dxs, dxd, dh, dP, dc, dw_hh, db_hh, dwq, None
-
-
-class _DecoderStep(torch.autograd.Function):
-    """decoder_step under autograd: forward = the one launch with the gates kept, backward = tap_decoder_step_backward
-    (element-wise) and the sums over the batch as matmuls.  What a step keeps: xs, xd and h BY REFERENCE (a stepper hands
-    out private copies of its decoder buffers while grad is enabled, and h is the previous step's own output), h', and
-    gates (B, 4, Hd) = r, z, n, gh_n; the parameters by reference."""
-
-    @staticmethod
-    def forward(ctx, xs, xd, h, P, c, w_hh, b_hh, wq):
-        B = int((xs if xs is not None else xd).shape[0])
-        Hd, dev = int(wq.shape[0]), P.device
-        h_new = torch.empty(B, Hd, dtype=torch.float32, device=dev)
-        q = torch.empty(B, Hd, dtype=torch.float32, device=dev)
-        gates = torch.empty(B, 4, Hd, dtype=torch.float32, device=dev)
-        _decoder_into(xs, xd, h, P, c, w_hh, b_hh, wq, h_new, q, gates)
-        ctx.save_for_backward(xs, xd, h, h_new, gates, P, w_hh, wq)
-        return h_new, q
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g_h, g_q):
-        xs, xd, h, h_new, gates, P, w_hh, wq = ctx.saved_tensors
-        B, Hd = (int(v) for v in h_new.shape)
-        dev = h_new.device
-        need = ctx.needs_input_grad
-        g_q = _as_f32(g_q, dev)
-        g = _as_f32(g_h, dev) + g_q.matmul(wq)                     # q = h' . wq^T: wq^T . dq joins the gradient arriving at h'
-        dgi = torch.empty(B, 3 * Hd, dtype=torch.float32, device=dev)
-        dghn = torch.empty(B, Hd, dtype=torch.float32, device=dev)
-        carry = torch.empty(B, Hd, dtype=torch.float32, device=dev)
-        _decoder_backward_into(gates, h, g, dgi, dghn, carry)
-        dgh = torch.cat((dgi[:, :2 * Hd], dghn), dim=1)            # the r and z parts of dgh are those of dgi
-        Ks = 0 if xs is None else int(xs.shape[1])
-        x = xd if xs is None else xs if xd is None else torch.cat((xs, xd), dim=1)
-        dxs = dgi.matmul(P[:, :Ks]) if xs is not None and need[0] else None
-        dxd = dgi.matmul(P[:, Ks:]) if xd is not None and need[1] else None
-        dh = carry + dgh.matmul(w_hh) if h is not None and need[2] else None
-        dP = dgi.t().matmul(x) if need[3] else None
-        dc = dgi.sum(0) if need[4] else None
-        dw_hh = (torch.zeros_like(w_hh) if h is None else dgh.t().matmul(h)) if need[5] else None
-        db_hh = dgh.sum(0) if need[6] else None
-        dwq = g_q.t().matmul(h_new) if need[7] else None
-        return dxs, dxd, dh, dP, dc, dw_hh, db_hh, dwq
+        xs, xd, h, hq, gates, P, w_hh, wq, keep = ctx.saved_tensors
+        g_q, dgi, dgh, carry = _step_backward_launch(gates, h, g_h, g_q, wq, keep, ctx.scales)
+        return _step_grads(ctx.needs_input_grad, xs, xd, h, hq, P, w_hh, g_q, dgi, dgh, carry) + (None,)
 
 
 def decoder_step_dropout(xs, xd, h, P, c, w_hh, b_hh, wq, dropout):
@@ -971,10 +938,31 @@ def decoder_step(xs, xd, h, P, c, w_hh, b_hh, wq):
     return _decoder_step(xs, xd, h, P, c, w_hh, b_hh, wq, None)
 
 
-def _decoder_step(xs, xd, h, P, c, w_hh, b_hh, wq, dropout):
+def _check_step_params(P, dyn, Ks, Kd, h, B, c, w_hh, b_hh, wq):
+    """what both steps check of the GRU's own tensors -> Hd.  ``dyn`` = what the messages call the dynamic half of the input
+    and its ``Kd`` values per env: ("xd", "Kd") or ("the encoder", "m")"""
     if P.dim() != 2 or int(P.shape[0]) % 3 or not P.is_floating_point():
-        raise ValueError("P must be a floating (3 Hd, Ks + Kd) tensor, got %s %s" % (P.dtype, tuple(P.shape)))
+        raise ValueError("P must be a floating (3 Hd, Ks + %s) tensor, got %s %s" % (dyn[1], P.dtype, tuple(P.shape)))
     Hd = int(P.shape[0]) // 3
+    if Ks + Kd != int(P.shape[1]):
+        raise ValueError("P has %d columns, xs and %s have %d + %d values per env" % (int(P.shape[1]), dyn[0], Ks, Kd))
+    for name, v, shape in (("c", c, (3 * Hd,)), ("w_hh", w_hh, (3 * Hd, Hd)), ("b_hh", b_hh, (3 * Hd,)), ("wq", wq, (Hd, Hd))) + \
+            ((("h", h, (B, Hd)),) if h is not None else ()):
+        if tuple(v.shape) != shape or not v.is_floating_point():
+            raise ValueError("%s must be a floating %s tensor, got %s %s" % (name, shape, v.dtype, tuple(v.shape)))
+    return Hd
+
+
+def _step_record_on(dropout, P):
+    """-> (the checked record or None, the step's device); a record whose state lives on another device is refused"""
+    drop = None if dropout is None else _dropout_record(dropout)
+    dev = _lib.resolve_device(P.device)
+    if drop is not None:
+        _dropout_state_on(drop, dev)
+    return drop, dev
+
+
+def _decoder_step(xs, xd, h, P, c, w_hh, b_hh, wq, dropout):
     if xs is None and xd is None:
         raise ValueError("decoder_step needs xs, xd or both")
     B = int((xs if xs is not None else xd).shape[0])
@@ -985,38 +973,14 @@ def _decoder_step(xs, xd, h, P, c, w_hh, b_hh, wq, dropout):
     xd = None if xd is None else xd.reshape(B, -1)
     Ks, Kd = (0 if v is None else int(v.shape[1]) for v in (xs, xd))
     xs, xd = (None if v is None or int(v.shape[1]) == 0 else v for v in (xs, xd))
-    if Ks + Kd != int(P.shape[1]):
-        raise ValueError("P has %d columns, xs and xd have %d + %d values per env" % (int(P.shape[1]), Ks, Kd))
-    for name, v, shape in (("c", c, (3 * Hd,)), ("w_hh", w_hh, (3 * Hd, Hd)), ("b_hh", b_hh, (3 * Hd,)), ("wq", wq, (Hd, Hd))) + \
-            ((("h", h, (B, Hd)),) if h is not None else ()):
-        if tuple(v.shape) != shape or not v.is_floating_point():
-            raise ValueError("%s must be a floating %s tensor, got %s %s" % (name, shape, v.dtype, tuple(v.shape)))
+    Hd = _check_step_params(P, ("xd", "Kd"), Ks, Kd, h, B, c, w_hh, b_hh, wq)
     if not decoder_step_supported(Ks, Kd, Hd):
         raise ValueError("no decoder-step kernel for Ks %d, Kd %d, Hd %d (Hd 64 / 128 / 256, 1 <= Ks + Kd <= Hd + 16)" % (Ks, Kd, Hd))
-    drop = None if dropout is None else _dropout_record(dropout)
-    dev = _lib.resolve_device(P.device)
-    if drop is not None:
-        _dropout_state_on(drop, dev)
-
-    def prep(t):
-        if t is None:
-            return None
-        if t.dtype is not torch.float32:
-            t = t.float()
-        if not t.is_contiguous() or t.device != dev:
-            t = t.to(dev).contiguous()
-        return t
-    args = [prep(v) for v in (xs, xd, h, P, c, w_hh, b_hh, wq)]
+    drop, dev = _step_record_on(dropout, P)
+    args = [_prep_f32(v, dev) for v in (xs, xd, h, P, c, w_hh, b_hh, wq)]
     if torch.is_grad_enabled() and any(v is not None and v.requires_grad for v in args):
-        return _DecoderStep.apply(*args) if drop is None else _DecoderStepDropout.apply(*args, drop)
-    h_new = torch.empty(B, Hd, dtype=torch.float32, device=dev)
-    q = torch.empty(B, Hd, dtype=torch.float32, device=dev)
-    if drop is None:
-        _decoder_into(*(None if v is None else v.detach() for v in args), h_new, q, None)
-    else:
-        keep = torch.empty(B, 2, Hd // 64, dtype=torch.int64, device=dev)
-        _decoder_dropout_into(*(None if v is None else v.detach() for v in args), drop, h_new, q, None, None, keep)
-    return h_new, q
+        return _DecoderStep.apply(*args, drop)
+    return _step_no_grad(_decoder_launch, args, drop, B, Hd, dev)
 
 
 def decoder_step_heightmap_supported(Ks, C, W, L, m, Hd):
@@ -1046,57 +1010,67 @@ def _leaky_slope(z):
     return torch.where(z > 0, torch.ones_like(z), torch.full_like(z, 0.01))
 
 
+def _decoder_hm_dropout_into(xs, hm, h, enc_w, P, c, w_hh, b_hh, wq, drop, h_out, q_out, gates, enc_out, rnn_out, keep):
+    """tap_decoder_step_hm_dropout on prepared buffers (as _decoder_hm_into and _decoder_dropout_into): one launch on the
+    current stream, nothing allocated"""
+    dev = P.device
+    _dropout_state_on(drop, dev)
+    c_ = _lib.ctx(dev)
+    B, Hd = int(h_out.shape[0]), int(h_out.shape[1])
+    Ks = 0 if xs is None else int(xs.shape[1])
+    C, W, L = (int(v) for v in hm.shape[1:])
+    p = _lib.ptr
+    _lib.check(_lib.lib().tap_decoder_step_hm_dropout(c_, p(xs), Ks, p(hm), C, W, L, p(h), B, Hd, int(enc_w[4].shape[0]),
+                                                      *(p(w) for w in enc_w), p(P), p(c), p(w_hh), p(b_hh), p(wq), p(drop.state),
+                                                      *_drop_scalars(drop), p(h_out), p(q_out), p(gates), p(enc_out), p(rnn_out),
+                                                      p(keep), _lib.stream_of(dev)), c_)
+
+
+def _decoder_hm_launch(args, drop, h_new, q, gates, rnn_out, keep, enc=None):
+    """_decoder_launch for the height-map step: ``args`` = xs, hm, h, the encoder's six tensors, P, c, w_hh, b_hh, wq"""
+    xs, hm, h = args[:3]
+    if drop is None:
+        _decoder_hm_into(xs, hm, h, tuple(args[3:9]), *args[9:], h_new, q, gates, enc)
+    else:
+        _decoder_hm_dropout_into(xs, hm, h, tuple(args[3:9]), *args[9:], drop, h_new, q, gates, enc, rnn_out, keep)
+
+
 class _DecoderStepHeightmap(torch.autograd.Function):
-    """decoder_step_heightmap under autograd: forward = the one launch with gates and enc kept; backward = _DecoderStep's
-    (tap_decoder_step_backward and the matmuls over the batch, with xd = enc), then the encoder's six gradients and hm's from
-    d_enc by recomputing a1 / a2 in torch on the gathered cells hm[:, :, ::4, ::4].  Inputs by reference, as _DecoderStep."""
+    """decoder_step_heightmap and decoder_step_heightmap_dropout under autograd (``drop`` None or the checked record): forward
+    = the one launch with gates and enc kept; backward = _DecoderStep's (the element-wise launch and the matmuls over the
+    batch, with xd = enc), then the encoder's six gradients and hm's from d_enc by recomputing a1 / a2 in torch on the
+    gathered cells hm[:, :, ::4, ::4].  Inputs by reference, and rnn_out and the keep words of a dropout step, as
+    _DecoderStep; the encoder's backward is the same for both: it receives d_enc."""
 
     @staticmethod
-    def forward(ctx, xs, hm, h, w1, b1, w2, b2, w3, b3, P, c, w_hh, b_hh, wq):
-        B, Hd, dev = int(hm.shape[0]), int(wq.shape[0]), P.device
-        h_new = torch.empty(B, Hd, dtype=torch.float32, device=dev)
-        q = torch.empty(B, Hd, dtype=torch.float32, device=dev)
-        gates = torch.empty(B, 4, Hd, dtype=torch.float32, device=dev)
+    def forward(ctx, xs, hm, h, w1, b1, w2, b2, w3, b3, P, c, w_hh, b_hh, wq, drop):
+        B, dev = int(hm.shape[0]), P.device
+        h_new, q, gates, rnn_out, keep = _step_outputs(B, int(wq.shape[0]), dev, drop, True)
         enc = torch.empty(B, int(w3.shape[0]), dtype=torch.float32, device=dev)
-        _decoder_hm_into(xs, hm, h, (w1, b1, w2, b2, w3, b3), P, c, w_hh, b_hh, wq, h_new, q, gates, enc)
-        ctx.save_for_backward(xs, hm, h, h_new, gates, enc, w1, b1, w2, b2, w3, P, w_hh, wq)
+        _decoder_hm_launch((xs, hm, h, w1, b1, w2, b2, w3, b3, P, c, w_hh, b_hh, wq), drop, h_new, q, gates, rnn_out, keep, enc)
+        ctx.save_for_backward(xs, hm, h, h_new if drop is None else rnn_out, gates, enc, w1, b1, w2, b2, w3, P, w_hh, wq, keep)
+        ctx.scales = _drop_scales(drop)
         return h_new, q
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_h, g_q):
-        xs, hm, h, h_new, gates, enc, w1, b1, w2, b2, w3, P, w_hh, wq = ctx.saved_tensors
-        B, Hd = (int(v) for v in h_new.shape)
-        dev = h_new.device
+        xs, hm, h, hq, gates, enc, w1, b1, w2, b2, w3, P, w_hh, wq, keep = ctx.saved_tensors
         need = ctx.needs_input_grad
-        g_q = _as_f32(g_q, dev)
-        g = _as_f32(g_h, dev) + g_q.matmul(wq)
-        dgi = torch.empty(B, 3 * Hd, dtype=torch.float32, device=dev)
-        dghn = torch.empty(B, Hd, dtype=torch.float32, device=dev)
-        carry = torch.empty(B, Hd, dtype=torch.float32, device=dev)
-        _decoder_backward_into(gates, h, g, dgi, dghn, carry)
-        dgh = torch.cat((dgi[:, :2 * Hd], dghn), dim=1)
-        Ks = 0 if xs is None else int(xs.shape[1])
-        x = enc if xs is None else torch.cat((xs, enc), dim=1)
-        dxs = dgi.matmul(P[:, :Ks]) if xs is not None and need[0] else None
-        dh = carry + dgh.matmul(w_hh) if h is not None and need[2] else None
-        dP = dgi.t().matmul(x) if need[9] else None
-        dc = dgi.sum(0) if need[10] else None
-        dw_hh = (torch.zeros_like(w_hh) if h is None else dgh.t().matmul(h)) if need[11] else None
-        db_hh = dgh.sum(0) if need[12] else None
-        dwq = g_q.t().matmul(h_new) if need[13] else None
-        dhm, dw1, db1, dw2, db2, dw3, db3 = _heightmap_encoder_backward(need, dgi, P, Ks, hm, w1, b1, w2, b2, w3)
-        return dxs, dhm, dh, dw1, db1, dw2, db2, dw3, db3, dP, dc, dw_hh, db_hh, dwq
+        g_q, dgi, dgh, carry = _step_backward_launch(gates, h, g_h, g_q, wq, keep, ctx.scales)
+        dxs, d_enc, dh, dP, dc, dw_hh, db_hh, dwq = _step_grads((need[0], need[1] or any(need[3:9]), need[2]) + tuple(need[9:14]),
+                                                               xs, enc, h, hq, P, w_hh, g_q, dgi, dgh, carry)
+        dhm, dw1, db1, dw2, db2, dw3, db3 = _heightmap_encoder_backward(need, d_enc, hm, w1, b1, w2, b2, w3)
+        return dxs, dhm, dh, dw1, db1, dw2, db2, dw3, db3, dP, dc, dw_hh, db_hh, dwq, None
 
 
-def _heightmap_encoder_backward(need, dgi, P, Ks, hm, w1, b1, w2, b2, w3):
-    """the encoder's half of a height-map step's backward, from dgi (B, 3 Hd): d_enc = dgi . P[:, Ks:], then the two hidden
-    layers recomputed in torch on the gathered cells -> dhm, dw1, db1, dw2, db2, dw3, db3 (None where ``need``, the
-    Function's needs_input_grad, does not ask)"""
+def _heightmap_encoder_backward(need, d_enc, hm, w1, b1, w2, b2, w3):
+    """the encoder's half of a height-map step's backward, from d_enc = dgi . P[:, Ks:] (B, m), or None when nothing of the
+    encoder asks: the two hidden layers recomputed in torch on the gathered cells -> dhm, dw1, db1, dw2, db2, dw3, db3 (None
+    where ``need``, the Function's needs_input_grad, does not ask)"""
     dhm = dw1 = db1 = dw2 = db2 = dw3 = db3 = None
-    if need[1] or any(need[3:9]):
+    if d_enc is not None:
         B = int(hm.shape[0])
-        d_enc = dgi.matmul(P[:, Ks:])                             # (B, m)
         cells = hm[:, :, ::4, ::4]                                # (B, C, nw, nl)
         C, nw, nl = (int(v) for v in cells.shape[1:])
         Np, C1, C2 = nw * nl, int(w1.shape[0]), int(w2.shape[0])
@@ -1119,64 +1093,10 @@ def _heightmap_encoder_backward(need, dgi, P, Ks, hm, w1, b1, w2, b2, w3):
     return dhm, dw1, db1, dw2, db2, dw3, db3
 
 
-def _decoder_hm_dropout_into(xs, hm, h, enc_w, P, c, w_hh, b_hh, wq, drop, h_out, q_out, gates, enc_out, rnn_out, keep):
-    """tap_decoder_step_hm_dropout on prepared buffers (as _decoder_hm_into and _decoder_dropout_into): one launch on the
-    current stream, nothing allocated"""
-    dev = P.device
-    _dropout_state_on(drop, dev)
-    c_ = _lib.ctx(dev)
-    B, Hd = int(h_out.shape[0]), int(h_out.shape[1])
-    Ks = 0 if xs is None else int(xs.shape[1])
-    C, W, L = (int(v) for v in hm.shape[1:])
-    p = _lib.ptr
-    _lib.check(_lib.lib().tap_decoder_step_hm_dropout(c_, p(xs), Ks, p(hm), C, W, L, p(h), B, Hd, int(enc_w[4].shape[0]),
-                                                      *(p(w) for w in enc_w), p(P), p(c), p(w_hh), p(b_hh), p(wq), p(drop.state),
-                                                      *_drop_scalars(drop), p(h_out), p(q_out), p(gates), p(enc_out), p(rnn_out),
-                                                      p(keep), _lib.stream_of(dev)), c_)
-
-
-class _DecoderStepHeightmapDropout(torch.autograd.Function):
-    """decoder_step_heightmap(dropout=...) under autograd: _DecoderStepHeightmap with _DecoderStepDropout's changes -- the
-    dropout launch forward, rnn_out and the keep words kept, the dropout form of the element-wise backward launch, dwq from
-    rnn_out.  The encoder's backward is unchanged: it receives dgi as before."""
-
-    @staticmethod
-    def forward(ctx, xs, hm, h, w1, b1, w2, b2, w3, b3, P, c, w_hh, b_hh, wq, drop):
-        B, Hd, dev = int(hm.shape[0]), int(wq.shape[0]), P.device
-        h_new = torch.empty(B, Hd, dtype=torch.float32, device=dev)
-        q = torch.empty(B, Hd, dtype=torch.float32, device=dev)
-        gates = torch.empty(B, 4, Hd, dtype=torch.float32, device=dev)
-        enc = torch.empty(B, int(w3.shape[0]), dtype=torch.float32, device=dev)
-        rnn_out = torch.empty(B, Hd, dtype=torch.float32, device=dev)
-        keep = torch.empty(B, 2, Hd // 64, dtype=torch.int64, device=dev)
-        _decoder_hm_dropout_into(xs, hm, h, (w1, b1, w2, b2, w3, b3), P, c, w_hh, b_hh, wq, drop, h_new, q, gates, enc, rnn_out, keep)
-        ctx.save_for_backward(xs, hm, h, gates, enc, rnn_out, keep, w1, b1, w2, b2, w3, P, w_hh, wq)
-        ctx.scales = (dropout_scale(drop.p_rnn), dropout_scale(drop.p_hh))
-        return h_new, q
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g_h, g_q):
-        xs, hm, h, gates, enc, rnn_out, keep, w1, b1, w2, b2, w3, P, w_hh, wq = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        g_q, dgi, dgh, carry = _dropout_backward_launch(gates, h, g_h, g_q, wq, keep, ctx.scales)
-        Ks = 0 if xs is None else int(xs.shape[1])
-        x = enc if xs is None else torch.cat((xs, enc), dim=1)
-        dxs = dgi.matmul(P[:, :Ks]) if xs is not None and need[0] else None
-        dh = carry + dgh.matmul(w_hh) if h is not None and need[2] else None
-        dP = dgi.t().matmul(x) if need[9] else None
-        dc = dgi.sum(0) if need[10] else None
-        dw_hh = (torch.zeros_like(w_hh) if h is None else dgh.t().matmul(h)) if need[11] else None
-        db_hh = dgh.sum(0) if need[12] else None
-        dwq = g_q.t().matmul(rnn_out) if need[13] else None
-        dhm, dw1, db1, dw2, db2, dw3, db3 = _heightmap_encoder_backward(need, dgi, P, Ks, hm, w1, b1, w2, b2, w3)
-        return dxs, dhm, dh, dw1, db1, dw2, db2, dw3, db3, dP, dc, dw_hh, db_hh, dwq, None
-
-
 def decoder_step_heightmap_dropout(xs, hm, h, encoder, P, c, w_hh, b_hh, wq, dropout):
     """``decoder_step_heightmap`` with the pointer's two dropouts inside the same launch (tapenv.h:
     tap_decoder_step_hm_dropout) -> (drop_hh(h'), wq . drop_rnn(h')); ``dropout`` and what a step keeps as
-    ``decoder_step_dropout``.  The encoder stage and its backward are untouched: the backward receives dgi as before."""
+    ``decoder_step_dropout``.  The encoder stage and its backward are untouched: the backward receives d_enc as before."""
     return _decoder_step_heightmap(xs, hm, h, encoder, P, c, w_hh, b_hh, wq, dropout)
 
 
@@ -1198,9 +1118,6 @@ def decoder_step_heightmap(xs, hm, h, encoder, P, c, w_hh, b_hh, wq):
 
 
 def _decoder_step_heightmap(xs, hm, h, encoder, P, c, w_hh, b_hh, wq, dropout):
-    if P.dim() != 2 or int(P.shape[0]) % 3 or not P.is_floating_point():
-        raise ValueError("P must be a floating (3 Hd, Ks + m) tensor, got %s %s" % (P.dtype, tuple(P.shape)))
-    Hd = int(P.shape[0]) // 3
     if hm is None or hm.dim() != 4 or not hm.is_floating_point():
         raise ValueError("hm must be a floating (B, C, W, L) tensor, got %s" % (None if hm is None else "%s %s" % (hm.dtype, tuple(hm.shape)),))
     B, C, W, L = (int(v) for v in hm.shape)
@@ -1219,42 +1136,17 @@ def _decoder_step_heightmap(xs, hm, h, encoder, P, c, w_hh, b_hh, wq, dropout):
         if m % 4 or tuple(cv.weight.shape) != shape or tuple(cv.bias.shape) != shape[:1] or not cv.weight.is_floating_point():
             raise ValueError("encoder.%s must be a floating %s convolution for a %s map and hidden size %d, got %s"
                              % (name, shape, (C, W, L), m, tuple(cv.weight.shape)))
-    if Ks + m != int(P.shape[1]):
-        raise ValueError("P has %d columns, xs and the encoder have %d + %d values per env" % (int(P.shape[1]), Ks, m))
-    for name, v, shape in (("c", c, (3 * Hd,)), ("w_hh", w_hh, (3 * Hd, Hd)), ("b_hh", b_hh, (3 * Hd,)), ("wq", wq, (Hd, Hd))) + \
-            ((("h", h, (B, Hd)),) if h is not None else ()):
-        if tuple(v.shape) != shape or not v.is_floating_point():
-            raise ValueError("%s must be a floating %s tensor, got %s %s" % (name, shape, v.dtype, tuple(v.shape)))
+    Hd = _check_step_params(P, ("the encoder", "m"), Ks, m, h, B, c, w_hh, b_hh, wq)
     if not decoder_step_heightmap_supported(Ks, C, W, L, m, Hd):
         raise ValueError("no height-map decoder-step kernel for Ks %d, C %d, W %d, L %d, m %d, Hd %d (Hd 64 / 128 / 256, m = Hd / 2 or Hd, "
                          "C 1 / 2 / 4, W and L <= 12, Ks <= 16, Ks + m <= Hd + 16)" % (Ks, C, W, L, m, Hd))
-    drop = None if dropout is None else _dropout_record(dropout)
-    dev = _lib.resolve_device(P.device)
-    if drop is not None:
-        _dropout_state_on(drop, dev)
-
-    def prep(t):
-        if t is None:
-            return None
-        if t.dtype is not torch.float32:
-            t = t.float()
-        if not t.is_contiguous() or t.device != dev:
-            t = t.to(dev).contiguous()
-        return t
+    drop, dev = _step_record_on(dropout, P)
     enc_w = (convs[0].weight.reshape(m // 4, C), convs[0].bias, convs[1].weight.reshape(m // 2, m // 4), convs[1].bias,
              convs[2].weight.reshape(m, (m // 2) * nw * nl), convs[2].bias)
-    args = [prep(v) for v in (xs, hm, h) + enc_w + (P, c, w_hh, b_hh, wq)]
+    args = [_prep_f32(v, dev) for v in (xs, hm, h) + enc_w + (P, c, w_hh, b_hh, wq)]
     if torch.is_grad_enabled() and any(v is not None and v.requires_grad for v in args):
-        return _DecoderStepHeightmap.apply(*args) if drop is None else _DecoderStepHeightmapDropout.apply(*args, drop)
-    h_new = torch.empty(B, Hd, dtype=torch.float32, device=dev)
-    q = torch.empty(B, Hd, dtype=torch.float32, device=dev)
-    d = [None if v is None else v.detach() for v in args]
-    if drop is None:
-        _decoder_hm_into(d[0], d[1], d[2], tuple(d[3:9]), *d[9:], h_new, q, None, None)
-    else:
-        keep = torch.empty(B, 2, Hd // 64, dtype=torch.int64, device=dev)
-        _decoder_hm_dropout_into(d[0], d[1], d[2], tuple(d[3:9]), *d[9:], drop, h_new, q, None, None, None, keep)
-    return h_new, q
+        return _DecoderStepHeightmap.apply(*args, drop)
+    return _step_no_grad(_decoder_hm_launch, args, drop, B, Hd, dev)
 
 
 class PointerHeadPolicy(object):
