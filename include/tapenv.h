@@ -598,7 +598,32 @@ enum {
 int tap_policy_pick(tap_ctx *ctx, const float *logits, const float *mask, const float *u, int B, int nR,
                     int flags, int64_t *ptr_out, float *logp_out, float *probs_out /* or NULL */, void *stream);
 
-/* The backward of logp with respect to the logits (model.py:359-372 under autograd: log_softmax gathered at ptr):
+/* The DRAW form: tap_policy_pick's sampling with the row's uniform computed INSIDE the launch, from the generator
+ * tap_decoder_step_dropout defines -- Philox4x32-10, the same multipliers and key increments.  state: the int64[2]
+ * (seed, episode) on the device; key (seed mod 2^32, seed >> 32); counter (env_offset + b, 0xFFFFFFFF, step, episode mod
+ * 2^32) for row b of the call -- 0xFFFFFFFF is a hidden row no dropout launch can use, so one state feeds both without
+ * overlap.  u = (float)(word0 >> 8) * 2^-24, exact in fp32 and in [0, 1); words 1 - 3 are unused.  Everything after u is
+ * the sampling form's code in the sampling form's order: with u_out (B,) f32 (or NULL) fed back as u into tap_policy_pick
+ * the outputs are the same bytes.  An env's pick depends on (seed, episode, step, env_offset + b) and its row alone: not
+ * on B, G or the launch.  k_policy_pick_form<G, 2> / k_policy_pick_wide_form<2>, tap_policy_pick's geometry; launch
+ * record key (26, 0, G, 2, PROBS, 0, 0).  Checks in tap_policy_pick's order, then a null state or one that is not 8-byte
+ * aligned -> TAP_E_INVALID. */
+int tap_policy_pick_draw(tap_ctx *ctx, const float *logits, const float *mask, const int64_t *state, uint32_t step,
+                         uint32_t env_offset, int B, int nR, int64_t *ptr_out, float *logp_out,
+                         float *probs_out /* or NULL */, float *u_out /* or NULL */, void *stream);
+
+/* The GIVEN form: the log-probability of a caller's column (teacher forcing; old tours under new weights).  m and S as
+ * tap_policy_pick computes them, then logp_out = (float)((l[ptr_in] - m) - log S) and probs_out as there.  A ptr_in
+ * outside [0, nR) or on an unselectable column gives logp NaN (it is never used as an address); probs_out is still
+ * written, and tap_policy_pick_backward writes zeros for such a row.  With ptr_in equal to what a sampling or greedy call
+ * returned, logp and probs are that call's bytes.  k_policy_pick_form<G, 3> / k_policy_pick_wide_form<3>; launch record
+ * key (26, 0, G, 3, PROBS, 0, 0).  Checks in tap_policy_pick's order (null logits / mask / logp_out), then a null ptr_in
+ * -> TAP_E_INVALID. */
+int tap_policy_pick_given(tap_ctx *ctx, const float *logits, const float *mask, const int64_t *ptr_in, int B, int nR,
+                          float *logp_out, float *probs_out /* or NULL */, void *stream);
+
+/* The backward of logp with respect to the logits (model.py:359-372 under autograd: log_softmax gathered at ptr), for
+ * tap_policy_pick and both forms above (GIVEN: ptr = ptr_in):
  * dlogits_out[b, c] = -g[b] * probs[b, c] in fp32 for c != ptr[b], and the picked column = minus the fp64 sum of the
  * row's other results, rounded once (g (1 - p[ptr]) with a row that sums to zero within one rounding, as the true
  * gradient does); one thread per element; probs / ptr / logp as

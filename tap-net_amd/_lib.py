@@ -27,7 +27,7 @@ TAP_HIT_EPISODE_MACS2, TAP_HIT_EPISODE_MACS3 = 17, 18          # tap_common.h: T
 TAP_HIT_PLACE_AT = 22
 TAP_HIT_EPISODE_MACS2_WAVE, TAP_HIT_EPISODE_MACS3_WAVE = 23, 24
 TAP_HIT_TRIAL = 25                                             # trial.hip: k_trial_scores
-TAP_HIT_POLICY_PICK = 26                                       # policy.hip: k_policy_pick / _wide / _backward
+TAP_HIT_POLICY_PICK = 26                                       # policy.hip: k_policy_pick / _wide / _form / _wide_form / _backward
 TAP_HIT_ENCODE_BITS = 27                                       # encode.hip: k_encode_bits<HPL> / _bw_partial + _bw_reduce
 TAP_HIT_POINTER = 28                                           # pointer.hip: k_pointer_scores<HPL[, SS]> / _bw + _bw_reduce (last field: S of the static-rows form, 0 = proj)
 TAP_HIT_DECODER = 29                                           # decoder.hip: k_decoder_step / k_decoder_step_bw
@@ -95,6 +95,8 @@ _PROTOS = {
     "tap_env_step_engine": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "tap_env_trial_scores": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "tap_policy_pick": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "tap_policy_pick_draw": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "tap_policy_pick_given": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "tap_policy_pick_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "tap_encode_bits": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "tap_encode_bits_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),

@@ -208,6 +208,181 @@ def pointer_pick(logits, mask, u=None, want_probs=False):
     return (ptr, logp, probs) if want_probs else (ptr, logp)
 
 
+PickRecord = collections.namedtuple("PickRecord", "state step env_offset")
+PickRecord.__doc__ = """what a DRAW pick takes: ``state`` the int64[2] (seed, episode) tensor, ``step`` the decoding step (a Python
+int) and the index of the call's first env in the whole batch (``tools.StepDropout.take_pick``)"""
+
+PICK_ROW = 0xFFFFFFFF          # the hidden row of the pick's Philox counter: no dropout launch has it
+
+
+def _pick_record(source):
+    """-> a checked PickRecord from a ``tools.StepDropout`` (its next pick), a record or a plain (state, step[, env_offset])"""
+    if hasattr(source, "take_pick"):
+        source = source.take_pick()
+    d = PickRecord(*source) if len(source) == 3 else PickRecord(*source, 0)
+    if not torch.is_tensor(d.state) or d.state.dtype is not torch.int64 or tuple(d.state.shape) != (2,) or not d.state.is_contiguous():
+        raise ValueError("the pick's state must be a contiguous int64[2] (seed, episode) tensor")
+    if int(d.step) < 0 or int(d.env_offset) < 0:
+        raise ValueError("the pick's step and env_offset must not be negative, got %r and %r" % (d.step, d.env_offset))
+    return d
+
+
+def pick_uniforms(state, step, B, env_offset=0):
+    """The uniforms of a DRAW pick in torch integer ops (tapenv.h: tap_policy_pick_draw) -> (B,) float32 on ``state``'s
+    device: Philox4x32-10 at counter (env_offset + b, 0xFFFFFFFF, step, episode mod 2^32) and key (seed mod 2^32, seed >> 32),
+    u = (word0 >> 8) * 2^-24.  It reads no value on the host."""
+    dev = state.device
+    seed, episode = state[0], state[1]
+    env = (torch.arange(int(B), dtype=torch.int64, device=dev) + int(env_offset)) & _M32
+    zero = torch.zeros_like(env)
+    w = philox4x32_10((env, zero + PICK_ROW, zero + (int(step) & _M32), zero + (episode & _M32)), (seed & _M32, (seed >> 32) & _M32))
+    return (w[0] >> 8).to(torch.float32) * (2.0 ** -24)
+
+
+def _pick_draw_into(logits, mask, rec, ptr, logp, probs, u):
+    """tap_policy_pick_draw on prepared buffers: one launch on the current stream, nothing allocated"""
+    dev = logits.device
+    if rec.state.device != dev:
+        raise ValueError("the pick's state lives on %s, the logits on %s: the launch reads the state on its own device"
+                         % (rec.state.device, dev))
+    c = _lib.ctx(dev)
+    B, nR = int(logits.shape[0]), int(logits.shape[1])
+    _lib.check(_lib.lib().tap_policy_pick_draw(c, _lib.ptr(logits), _lib.ptr(mask), _lib.ptr(rec.state), int(rec.step) & _M32,
+                                               int(rec.env_offset) & _M32, B, nR, _lib.ptr(ptr), _lib.ptr(logp), _lib.ptr(probs),
+                                               _lib.ptr(u), _lib.stream_of(dev)), c)
+
+
+def _pick_given_into(logits, mask, ptr_in, logp, probs):
+    """tap_policy_pick_given on prepared buffers: one launch on the current stream, nothing allocated"""
+    dev = logits.device
+    c = _lib.ctx(dev)
+    B, nR = int(logits.shape[0]), int(logits.shape[1])
+    _lib.check(_lib.lib().tap_policy_pick_given(c, _lib.ptr(logits), _lib.ptr(mask), _lib.ptr(ptr_in), B, nR, _lib.ptr(logp),
+                                                _lib.ptr(probs), _lib.stream_of(dev)), c)
+
+
+class _PointerPickDraw(torch.autograd.Function):
+    """pointer_pick_draw under autograd: forward = the DRAW launch with probs kept, backward = ``_PointerPick``'s"""
+
+    @staticmethod
+    def forward(ctx, logits, mask, rec, want_u):
+        B, nR = logits.shape
+        ptr = torch.empty(B, dtype=torch.int64, device=logits.device)
+        logp = torch.empty(B, dtype=torch.float32, device=logits.device)
+        probs = torch.empty(B, nR, dtype=torch.float32, device=logits.device)
+        u = torch.empty(B, dtype=torch.float32, device=logits.device) if want_u else None
+        _pick_draw_into(logits, mask, rec, ptr, logp, probs, u)
+        ctx.save_for_backward(probs, ptr, logp)
+        ctx.mark_non_differentiable(*(t for t in (ptr, probs, u) if t is not None))
+        return ptr, logp, probs, u
+
+    @staticmethod
+    def backward(ctx, _g_ptr, g, _g_probs, _g_u):
+        return _PointerPick.backward(ctx, None, g, None)[0], None, None, None
+
+
+class _PointerPickGiven(torch.autograd.Function):
+    """pointer_pick_given under autograd: forward = the GIVEN launch with probs kept, backward = ``_PointerPick``'s on the
+    caller's column (a CLONE of it: a stepper's tour buffer is overwritten by the next episode)"""
+
+    @staticmethod
+    def forward(ctx, logits, mask, ptr_in):
+        B, nR = logits.shape
+        logp = torch.empty(B, dtype=torch.float32, device=logits.device)
+        probs = torch.empty(B, nR, dtype=torch.float32, device=logits.device)
+        _pick_given_into(logits, mask, ptr_in, logp, probs)
+        ctx.save_for_backward(probs, ptr_in.clone(), logp)
+        ctx.mark_non_differentiable(probs)
+        return logp, probs
+
+    @staticmethod
+    def backward(ctx, g, _g_probs):
+        return _PointerPick.backward(ctx, None, g, None)[0], None, None
+
+
+def _pick_inputs(logits, mask):
+    """the checks and conversions of ``pointer_pick`` -> logits, mask (float32, contiguous, on the device), B, nR, dev"""
+    if logits.dim() != 2 or int(logits.shape[1]) < 1:
+        raise ValueError("logits must be (B, nR) with nR >= 1, got %s" % (tuple(logits.shape),))
+    dev = _lib.resolve_device(logits.device)
+    B, nR = int(logits.shape[0]), int(logits.shape[1])
+    if tuple(mask.shape) != (B, nR):
+        raise ValueError("mask must be (%d, %d), got %s" % (B, nR, tuple(mask.shape)))
+    return _prep_f32(logits, dev), _prep_f32(mask.detach(), dev), B, nR, dev
+
+
+def pointer_pick_draw(logits, mask, source, want_probs=False, want_u=False):
+    """``pointer_pick``'s sampling with the uniforms computed INSIDE the launch (tapenv.h: tap_policy_pick_draw): ``source`` is
+    a ``tools.StepDropout`` -- the call takes its next pick record --, a ``PickRecord`` or a plain (state, step[, env_offset])
+    with ``state`` the int64[2] (seed, episode) on the logits' device.  Counter-based: a row's pick depends on (seed, episode,
+    step, env_offset + b) and the row alone -- not on the batch size, the launch or torch's generator --, and a captured
+    episode draws anew on every replay once ``next_episode()`` is captured at its head.  -> (ptr, logp[, probs][, u]); ``u``
+    (B,) float32 is what the launch drew: ``pointer_pick(logits, mask, u)`` returns the same bytes.  Autograd as
+    ``pointer_pick``."""
+    logits, mask, B, nR, dev = _pick_inputs(logits, mask)
+    rec = _pick_record(source)
+    if torch.is_grad_enabled() and logits.requires_grad:
+        ptr, logp, probs, u = _PointerPickDraw.apply(logits, mask, rec, bool(want_u))
+    else:
+        ptr = torch.empty(B, dtype=torch.int64, device=dev)
+        logp = torch.empty(B, dtype=torch.float32, device=dev)
+        probs = torch.empty(B, nR, dtype=torch.float32, device=dev) if want_probs else None
+        u = torch.empty(B, dtype=torch.float32, device=dev) if want_u else None
+        _pick_draw_into(logits, mask, rec, ptr, logp, probs, u)
+    return (ptr, logp) + ((probs,) if want_probs else ()) + ((u,) if want_u else ())
+
+
+def pointer_pick_given(logits, mask, ptr, want_probs=False):
+    """The log-probability of GIVEN columns ``ptr`` (B,) int64 under the head's masked softmax, in one launch (tapenv.h:
+    tap_policy_pick_given): teacher forcing, or old tours under new weights.  -> logp (B,) float32[, probs (B, nR)]; NaN where
+    ``ptr`` lies outside [0, nR) or on an unselectable column.  With ``ptr`` what ``pointer_pick`` returned for the same
+    inputs, ``logp`` and ``probs`` are that call's bytes.  Autograd as ``pointer_pick`` (a NaN row has a zero gradient)."""
+    logits, mask, B, nR, dev = _pick_inputs(logits, mask)
+    if tuple(ptr.shape) != (B,) or ptr.is_floating_point():
+        raise ValueError("ptr must be an integer (%d,) tensor, got %s %s" % (B, ptr.dtype, tuple(ptr.shape)))
+    if ptr.dtype is not torch.int64 or not ptr.is_contiguous() or ptr.device != dev:
+        ptr = ptr.to(device=dev, dtype=torch.int64).contiguous()
+    if torch.is_grad_enabled() and logits.requires_grad:
+        logp, probs = _PointerPickGiven.apply(logits, mask, ptr)
+    else:
+        logp = torch.empty(B, dtype=torch.float32, device=dev)
+        probs = torch.empty(B, nR, dtype=torch.float32, device=dev) if want_probs else None
+        _pick_given_into(logits, mask, ptr, logp, probs)
+    return (logp, probs) if want_probs else logp
+
+
+def pointer_pick_torch(logits, mask, u=None, given=None):
+    """The head in torch ops, float64, for tensors off the GPU (``tools.DRL``'s fallback; the kernels' definition, tapenv.h:
+    tap_policy_pick): ``given`` (B,) int64 scores those columns, else ``u`` (B,) samples and None picks greedily.  -> (ptr,
+    logp in the dtype of ``logits``); differentiable in ``logits``."""
+    sel = mask != 0
+    l = torch.where(sel, logits.double(), torch.full_like(logits, float('-inf'), dtype=torch.float64))
+    any_ = sel.any(1)
+    m = torch.where(any_, l.max(1).values, torch.zeros_like(l[:, 0]))
+    w = torch.where(sel, torch.exp(l - m.unsqueeze(1)), torch.zeros_like(l))
+    S = w.sum(1)
+    nR = int(logits.shape[1])
+    if given is not None:
+        ptr = given.to(torch.int64)
+        ok = (ptr >= 0) & (ptr < nR)
+        at = ptr.clamp(0, nR - 1)
+        ok = ok & sel.gather(1, at.unsqueeze(1))[:, 0]
+    else:
+        if u is None:
+            hit = sel & (l == m.unsqueeze(1))
+        else:
+            hit = sel & (w.cumsum(1) > (u.double() * S).unsqueeze(1))
+        cols = torch.arange(nR, device=logits.device).unsqueeze(0)
+        first = torch.where(hit, cols, torch.full_like(cols, nR)).min(1).values
+        last = torch.where(sel, cols, torch.zeros_like(cols)).max(1).values
+        ptr = at = torch.where(first < nR, first, last)
+        ok = any_
+    # the unselectable columns hold -inf: a picked column is selectable, and gather's gradient reaches that column alone
+    l_ptr = torch.where(ok, l.gather(1, at.unsqueeze(1))[:, 0], torch.zeros_like(m))
+    logp = torch.where(ok, (l_ptr - m) - torch.log(torch.where(ok, S, torch.ones_like(S))), torch.full_like(m, float('nan')))
+    return ptr, logp.to(logits.dtype)
+
+
 def _encode_into(bits, weight, bias, rows, out):
     """tap_encode_bits on prepared buffers: one launch on the current stream, nothing allocated"""
     dev = bits.device
@@ -1156,7 +1331,9 @@ class PointerHeadPolicy(object):
     ``u``: PRE-DRAWN uniforms (steps, B) in [0, 1), step-major so a step's row is contiguous (like TapePolicy's tour):
     the episode is then deterministic given ``u`` and can be captured in a hipGraph and replayed on refreshed uniforms.
     ``greedy=True``: the first maximum instead (the reference's test mode).  With neither, ``torch.rand(B,
-    generator=generator)`` is drawn per step, eagerly.  Each step's logp is kept: ``tour_logp()`` -> (B, steps), the
+    generator=generator)`` is drawn per step, eagerly.  ``PointerHeadPolicy.from_source(scorer, source)`` (``source`` a
+    ``tools.StepDropout``): the uniform is drawn inside the head's launch from the source's next pick record
+    (``pointer_pick_draw``) -- no tensor of uniforms, capturable, new draws on every replay.  Each step's logp is kept: ``tour_logp()`` -> (B, steps), the
     reference's tour_logp (model.py:513); ``reset()`` clears the kept values (step 0 of a new episode does too)."""
 
     def __init__(self, scorer, u=None, greedy=False, generator=None):
@@ -1166,7 +1343,17 @@ class PointerHeadPolicy(object):
         self.u = u
         self.greedy = bool(greedy)
         self.generator = generator
+        self.source = None
         self._logp = []
+
+    @classmethod
+    def from_source(cls, scorer, source):
+        """the policy that draws inside the head's launch: ``source`` a ``tools.StepDropout`` (anything with ``take_pick()``)"""
+        if not hasattr(source, "take_pick"):
+            raise TypeError("source must hand out pick records (tools.StepDropout), got %r" % (source,))
+        pol = cls(scorer)
+        pol.source = source
+        return pol
 
     def reset(self):
         self._logp = []
@@ -1175,13 +1362,16 @@ class PointerHeadPolicy(object):
         if step == 0:
             self._logp = []
         logits = self.scorer(step=step, current_mask=current_mask, **kw)
-        if self.greedy:
-            u = None
-        elif self.u is not None:
-            u = self.u[step]
+        if self.source is not None:
+            ptr, logp = pointer_pick_draw(logits, current_mask, self.source)
         else:
-            u = torch.rand(int(logits.shape[0]), generator=self.generator, device=logits.device)
-        ptr, logp = pointer_pick(logits, current_mask, u)
+            if self.greedy:
+                u = None
+            elif self.u is not None:
+                u = self.u[step]
+            else:
+                u = torch.rand(int(logits.shape[0]), generator=self.generator, device=logits.device)
+            ptr, logp = pointer_pick(logits, current_mask, u)
         while len(self._logp) <= step:
             self._logp.append(None)
         self._logp[step] = logp

@@ -651,16 +651,193 @@ class StepDropout(object):
         self.state = torch.tensor([seed, 0], dtype=torch.int64, device=device)
         self.env_offset = env_offset
         self.step = 0
+        self.pick = 0
 
     def next_episode(self):
         self.state[1] += 1
         self.step = 0
+        self.pick = 0
+
+    def take_pick(self):
+        """-> the ``rollout.PickRecord`` of the head's next DRAW pick (``rollout.pointer_pick_draw``), and advances ``pick``: a
+        counter of its own beside ``step``, so an episode may mix dropout steps and picks in any order.  The pick's Philox
+        counter has the hidden row 0xFFFFFFFF, which no dropout launch has: one state feeds both without overlap."""
+        from .rollout import PickRecord
+        rec = PickRecord(self.state, self.pick, self.env_offset)
+        self.pick += 1
+        return rec
 
     def take_step(self, p_rnn=0.0, p_hh=0.0):
         from .rollout import StepDropoutRecord
         rec = StepDropoutRecord(self.state, self.step, float(p_rnn), float(p_hh), self.env_offset)
         self.step += 1
         return rec
+
+
+class DRL(nn.Module):
+    """The reference's actor (model.DRL, model.py:141-515) as ONE module that owns the episode: the constructor takes the
+    reference's positional arguments, the children carry its names and shapes -- ``static_encoder``, ``dynamic_encoder`` (their
+    only child ``conv``), ``decoder`` / ``dynamic_decoder`` / ``static_decoder`` + ``dynamic_decoder`` by ``decoder_input_type``
+    (a ``HeightmapEncoder`` for ``block_dim == 3``), ``pointer`` (a ``Pointer``) --, so ``load_state_dict(torch.load('actor.pt'),
+    strict=True)`` works on the whole module; every parameter with more than one axis is xavier-uniform, as there.
+    ``update_fn`` / ``mask_fn``: ``pack.update_dynamic`` / ``pack.update_mask`` or None -- the stepper does both; another
+    callable raises NotImplementedError, and so do the input types 'mul', 'mul-with' and 'use-pnet' (the two-container episode
+    and the encoder RNN).  Keyword-only: ``seed`` and ``env_offset`` of the module's ``StepDropout``, ``fold`` 'static'
+    (``Pointer.fold_static``: no static_hidden, no proj) or 'proj' (``Pointer.project_static``).
+
+    ``forward(static, dynamic, decoder_input, last_hh=None, *, tour=None, stepper=None, check='nan')`` -> (tour_idx (B, n)
+    int64, tour_logp (B, n) float32, None, -scores (B,)), the reference's tuple (model.py:515).  One call is one episode of
+    exactly n steps -- every step retires one block, so no host read decides when to stop.  In order: ``stepper.begin``; in
+    training mode ``next_episode()`` on the module's ``StepDropout`` (a torch op); the folds, once (``fold_static`` or
+    ``project_static``, ``fold_decoder``, ``fold_episode``); then per step ``Pointer.forward_step`` (eval, or p = 0) or
+    ``forward_step_dropout`` (training, p > 0), the head, ``stepper.step(ptr)``.  The head: ``rollout.pointer_pick_given`` on
+    ``tour[:, k]`` when a ``tour`` (B, n) is passed (teacher forcing, in either mode), else greedy ``pointer_pick`` in eval
+    and ``pointer_pick_draw`` from the module's ``StepDropout`` in training: torch's generator is never touched.  The first
+    step's decoder input is ``decoder_input`` (a pair for the 'heightmap' types, trainer.py:116-119); ``last_hh=None`` is zeros.
+    These are the launches of the hand-written recipe and no others; under ``pack.set_binary_check(
+    'trust')`` and ``check`` 'nan' or False nothing is read on the host, and the whole call can be captured in one graph: the
+    episode counter advances inside it, so every replay draws new masks and new picks.
+
+    Off the GPU -- and wherever ``Pointer.forward_step`` takes its torch path -- the step is torch, and off the GPU the head is
+    ``rollout.pointer_pick_torch`` with ``rollout.pick_uniforms``: the module in ``double()`` is then its own float64 model
+    (a ``stepper=`` must be given there: the package's steppers live on the device).
+
+    Kept between calls: one ``BatchedContainer`` + ``EpisodeStepper(expand_dynamic=False)`` per (shapes, device) -- ``tour_idx``
+    is that stepper's buffer, valid until the next ``forward`` with these shapes: clone what must outlive it -- and one
+    ``StepDropout`` per device (``step_dropout(device)``).  ``stepper=``: a ``pack.EpisodeStepper`` or anything with its
+    ``begin``, ``step``, ``steps``, ``dynamic_bits``, ``current_mask``, ``decoder_static``, ``decoder_dynamic``, ``tour``,
+    ``ratio`` and ``env``."""
+
+    def __init__(self, static_size, dynamic_size, encoder_hidden_size, decoder_hidden_size, use_cuda, input_type, allow_rot,
+                 container_width, container_height, block_dim, reward_type, decoder_input_type, heightmap_type, packing_strategy,
+                 update_fn, mask_fn, num_layers=1, dropout=0., unit=1, *, seed=0, env_offset=0, fold='static'):
+        super(DRL, self).__init__()
+        from . import pack
+        if dynamic_size < 1:
+            raise ValueError(':param dynamic_size: must be > 0, even if the problem has no dynamic elements')
+        if input_type in ('mul', 'mul-with', 'use-pnet'):
+            raise NotImplementedError("input_type %r: the two-container episode ('mul', 'mul-with') and the encoder RNN "
+                                      "('use-pnet') are not built into DRL" % (input_type,))
+        for name, fn, own in (("update_fn", update_fn, pack.update_dynamic), ("mask_fn", mask_fn, pack.update_mask)):
+            if fn is not None and fn is not own:
+                raise NotImplementedError("%s: the stepper updates dynamic and the masks inside its launch; pass pack.%s or None, "
+                                          "not %r" % (name, own.__name__, fn))
+        if decoder_input_type not in ('shape_only', 'heightmap_only', 'shape_heightmap'):
+            raise ValueError("decoder_input_type must be 'shape_only', 'heightmap_only' or 'shape_heightmap', not %r" % (decoder_input_type,))
+        if fold not in ('static', 'proj'):
+            raise ValueError("fold must be 'static' or 'proj', not %r" % (fold,))
+        self.update_fn, self.mask_fn = update_fn, mask_fn
+        self.static_encoder = _Conv1x1(static_size, encoder_hidden_size)
+        self.dynamic_encoder = DynamicBitsEncoder(dynamic_size, encoder_hidden_size)
+        # model.py:189-202
+        heightmap_num = 1
+        heightmap_width = heightmap_length = container_width * unit
+        if heightmap_type == 'diff':
+            if block_dim == 2:
+                heightmap_width = container_width * unit - 1
+            elif block_dim == 3:
+                heightmap_num = 2
+        heightmap_width, heightmap_length = math.ceil(heightmap_width), math.ceil(heightmap_length)
+
+        def dynamic_decoder(hidden):
+            if block_dim == 3:
+                return HeightmapEncoder(heightmap_num, int(hidden), (heightmap_width, heightmap_length))
+            return _Conv1x1(heightmap_width, int(hidden))
+        if decoder_input_type == 'shape_only':
+            self.decoder = _Conv1x1(static_size, decoder_hidden_size)
+        elif decoder_input_type == 'heightmap_only':
+            self.dynamic_decoder = dynamic_decoder(decoder_hidden_size)
+        else:
+            self.static_decoder = _Conv1x1(static_size, int(decoder_hidden_size / 2))
+            self.dynamic_decoder = dynamic_decoder(decoder_hidden_size / 2)
+        self.pointer = Pointer(encoder_hidden_size, decoder_hidden_size, decoder_input_type, input_type, num_layers, dropout)
+        for p in self.parameters():
+            if len(p.shape) > 1:
+                nn.init.xavier_uniform_(p)
+        self.encoder_hidden_size, self.decoder_hidden_size = encoder_hidden_size, decoder_hidden_size
+        self.use_cuda, self.input_type, self.allow_rot, self.block_dim = use_cuda, input_type, allow_rot, block_dim
+        self.static_size, self.dynamic_size, self.reward_type = static_size, dynamic_size, reward_type
+        self.container_width, self.container_height = math.ceil(container_width * unit), container_height
+        self.decoder_input_type, self.heightmap_type, self.packing_strategy = decoder_input_type, heightmap_type, packing_strategy
+        self.seed, self.env_offset, self.fold = int(seed), int(env_offset), fold
+        self._dropouts, self._steppers = {}, {}
+        self.last_stepper = None            # the stepper of the latest forward: its check() reads the containers' error words
+
+    def step_dropout(self, device):
+        """the module's ``StepDropout`` on ``device`` (made at the first call: seed, episode 0)"""
+        device = torch.device(device)
+        if device not in self._dropouts:
+            self._dropouts[device] = StepDropout(self.seed, device, self.env_offset)
+        return self._dropouts[device]
+
+    def _own_stepper(self, static, dynamic, n):
+        from .pack import EpisodeStepper
+        key = (tuple(static.shape), tuple(dynamic.shape), static.device)
+        if key not in self._steppers:
+            W = self.container_width
+            cs = [W, self.container_height] if self.block_dim == 2 else [W, W, self.container_height]      # model.py:278-281
+            env = BatchedContainer(int(static.shape[0]), cs, n, self.reward_type, self.heightmap_type,
+                                   packing_strategy=self.packing_strategy, device=static.device)
+            self._steppers[key] = EpisodeStepper(static, dynamic, env, self.input_type, self.allow_rot, steps=n, expand_dynamic=False)
+        return self._steppers[key]
+
+    def forward(self, static, dynamic, decoder_input, last_hh=None, *, tour=None, stepper=None, check='nan'):
+        from .rollout import (_flagged_reward, pick_uniforms, pointer_pick, pointer_pick_draw, pointer_pick_given,
+                              pointer_pick_torch)
+        n = int(dynamic.shape[-1]) // ((2 if self.block_dim == 2 else 6) if self.allow_rot else 1)       # model.py:269-276
+        B = int(static.shape[0])
+        sp = stepper if stepper is not None else self._own_stepper(static, dynamic, n)
+        if int(sp.steps) != n:
+            raise ValueError("the stepper was built for %d steps per episode, not %d" % (sp.steps, n))
+        if tour is not None:
+            if tuple(tour.shape) != (B, n):
+                raise ValueError("tour must be (%d, %d), got %s" % (B, n, tuple(tour.shape)))
+            tour = tour.to(torch.int64).t().contiguous()            # step-major: a step's picks are a contiguous row
+        sp.begin(static, dynamic)
+        # (the children straight from the registry and the plain attribute through __dict__: nn.Module's attribute protocol costs
+        #  about a microsecond per access, and an eval episode at c2 is short enough for ten of them to show)
+        self.__dict__['last_stepper'] = sp
+        mods = self._modules
+        drop = None
+        if self.training:
+            drop = self.step_dropout(static.device)
+            drop.next_episode()
+        pointer, static_encoder = mods['pointer'], mods['static_encoder']
+        xs = static if self.input_type == 'rot-old' else static[:, 1:, :]                                 # model.py:318-337
+        proj = pointer.fold_static(static_encoder, xs) if self.fold == 'static' else pointer.project_static(static_encoder(xs))
+        P, c = pointer.fold_decoder(mods.get('decoder', mods.get('static_decoder')), mods.get('dynamic_decoder'), combine='cat')
+        fold = pointer.fold_episode(mods['dynamic_encoder'], P, c)
+        if self.decoder_input_type == 'shape_heightmap':
+            decoder_static, decoder_dynamic = decoder_input
+        elif self.decoder_input_type == 'shape_only':
+            decoder_static, decoder_dynamic = decoder_input, None
+        else:
+            decoder_static, decoder_dynamic = None, decoder_input[1] if isinstance(decoder_input, (tuple, list)) else decoder_input
+        dropping = self.training and (pointer.drop_rnn.p > 0 or pointer.drop_hh.p > 0)
+        logps = []
+        for k in range(n):
+            bits, cur = sp.dynamic_bits, sp.current_mask
+            if dropping:
+                logits, last_hh = pointer.forward_step_dropout(proj, bits, fold, decoder_static, decoder_dynamic, last_hh, drop)
+            else:
+                logits, last_hh = pointer.forward_step(proj, bits, fold, decoder_static, decoder_dynamic, last_hh)
+            if not logits.is_cuda:
+                u = None if drop is None or tour is not None else pick_uniforms(*drop.take_pick()[:2], B, drop.env_offset)
+                ptr, logp = pointer_pick_torch(logits, cur, u, None if tour is None else tour[k])
+            elif tour is not None:
+                ptr = tour[k]
+                logp = pointer_pick_given(logits, cur, ptr)
+            elif drop is not None:
+                ptr, logp = pointer_pick_draw(logits, cur, drop)
+            else:
+                ptr, logp = pointer_pick(logits, cur)
+            logps.append(logp)
+            sp.step(ptr)
+            if self.decoder_input_type != 'heightmap_only':
+                decoder_static = sp.decoder_static
+            if self.decoder_input_type != 'shape_only':
+                decoder_dynamic = sp.decoder_dynamic
+        return sp.tour, torch.stack(logps, dim=1), None, _flagged_reward(-sp.ratio, check, sp.env)
 
 
 class _EngineRow(object):
