@@ -772,12 +772,50 @@ int tap_pointer_scores_static_backward(tap_ctx *ctx, const float *xs, const unsi
 size_t tap_pointer_scores_static_backward_scratch(int B, int nR, int rows, int Hd, int S);
 /* The launch geometry of the four pointer entries for this shape, from the function the launchers themselves call: host
  * only, no context, no GPU code, like tap_bits_words.  S = 0: tap_pointer_scores / _backward; S = 1 .. 8: the static-rows
- * form; backward != 0: the backward.  out = (consecutive envs per workgroup -- max(1, B / 1024), halved while the dynamic
+ * form, and with backward = 0 tap_pointer_pick_static too (its epilogue needs no LDS of its own); backward != 0: the backward.  out = (consecutive envs per workgroup -- max(1, B / 1024), halved while the dynamic
  * LDS exceeds 60 KB --, workgroups = ceil(B / envs per workgroup), bytes of dynamic LDS, columns per pass of the backward's
  * dU tile (0 forward)); the backward's scratch is workgroups * 2 * Hd floats.  TAP_OK; a null out -> TAP_E_INVALID; B, nR,
  * rows or Hd < 1 or S < 0 -> TAP_E_INVALID and a shape the entries refuse -> TAP_E_UNSUPPORTED, both with out = zeros (as
  * the scratch queries answer 0). */
 int tap_pointer_scores_geometry(int B, int nR, int rows, int Hd, int S, int backward, int32_t out[4]);
+
+enum {
+    TAP_PICK_GREEDY = 1, /* the head's greedy form: tap_policy_pick with TAP_P_GREEDY */
+    TAP_PICK_DRAW = 2    /* the head's DRAW form: tap_policy_pick_draw */
+};
+
+/* Scores and pick in ONE launch, for inference on windows whose static rows change every step (the rolling loop):
+ * tap_pointer_scores_static followed by the decoding head, with the logits never leaving the LDS.  No attn, no t, no
+ * gradient.
+ *   xs: env b's S rows start at xs + b * xs_env_stride floats; the rows are nR floats apart and contiguous (xs_env_stride
+ *   >= S nR) -- static[:, 1:, :] of a (B, 1 + S, nR) window is passed as the view it is, xs_env_stride = (1 + S) nR.
+ *   bits, B, nR, rows, Hd, S, G, g, M, k, q, va, vp: tap_pointer_scores_static's.
+ *   mask (B, nR) f32: the stepper's current_mask, column c selectable iff mask != 0 (tap_policy_pick's).
+ *   form: TAP_PICK_GREEDY, or TAP_PICK_DRAW with state / step / env_offset exactly as tap_policy_pick_draw takes them
+ *   (state is not read under TAP_PICK_GREEDY and may be NULL).
+ *   ptr_out (B,) int64, logp_out (B,) f32; logits_out (B, nR) f32 or NULL.
+ * Byte contract: logits_out, when given, holds the bytes tap_pointer_scores_static writes for the same inputs (xs made
+ * contiguous), and ptr_out / logp_out hold the bytes tap_policy_pick with TAP_P_GREEDY / tap_policy_pick_draw writes when
+ * fed those logits and this mask -- for every supported nR, whichever of the head's two geometries the stand-alone launch
+ * takes.  A row without a selectable column: ptr 0, logp NaN.
+ * k_pointer_pick<HPL, SS, FORM> (pointer.hip): k_pointer_scores<HPL, SS>'s three phases on tap_pointer_scores_geometry(B, nR,
+ * rows, Hd, S, 0)'s geometry -- the same LDS, the same orders of summation --; then, where that kernel stores the LDS row of
+ * logits, one wavefront per env of the workgroup's run walks it in 64-column chunks: the head's chunked form (max pass,
+ * fp64 weights, the 64-lane scan with the running prefix, DRAW's second pass; tap_pick.h holds the code both units run).
+ * On rows of at most 64 columns the lane-group form agrees with it bit for bit: its scan's extra steps add lanes that
+ * hold 0.0, and a lane's partial sums are the same operations.  One launch, no allocation, no host read, no stream
+ * synchronisation (capturable in a hipGraph); no atomics: two calls give the same bytes.
+ * Launch record key (28, FORM, HPL, PLANES, CHUNKS, 0, S), FORM = 1 (greedy) or 2 (DRAW) where the entries above have 0.
+ * Checks, in tap_pointer_scores_static's order: B < 0 or nR / rows / Hd / S < 1, or a form that is neither ->
+ * TAP_E_INVALID; B == 0 -> TAP_OK; a null buffer (mask, ptr_out and logp_out among them; not logits_out) ->
+ * TAP_E_INVALID; TAP_PICK_DRAW with a null state or one that is not 8-byte aligned -> TAP_E_INVALID; xs_env_stride <
+ * S nR -> TAP_E_INVALID; a shape outside tap_pointer_scores_static's list -> TAP_E_UNSUPPORTED; a misaligned buffer
+ * (bits and ptr_out 8 bytes, floats 4) -> TAP_E_INVALID. */
+int tap_pointer_pick_static(tap_ctx *ctx, const float *xs, size_t xs_env_stride, const unsigned long long *bits, int B, int nR,
+                            int rows, int Hd, int S, const float *G, const float *g, const float *M, const float *k,
+                            const float *q, const float *va, const float *vp, const float *mask, int form,
+                            const int64_t *state, uint32_t step, uint32_t env_offset, int64_t *ptr_out, float *logp_out,
+                            float *logits_out /* or NULL */, void *stream);
 
 /* The state critic's value estimate in ONE launch from the critic's static input and the bit shadow (critic.hip): the
  * reference's realCritic (trainer.py:18-94) after its GRU step.  With Es, bs / Ed, bd the static / dynamic encoder's

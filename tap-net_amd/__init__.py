@@ -14,9 +14,9 @@ from .pack import (EnvTransition, EpisodeStepper, MaskStepper, PACKDataset, epis
 from .rolling import RollingDataset, RollingStepper, RollingWindows, run_rolling_episode            # noqa: F401
 from .rollout import (BestRatioPolicy, PointerHeadPolicy, RandomFeasiblePolicy, TapePolicy, UniformKeysPolicy,   # noqa: F401
                       UniformPickPolicy, critic_value, decoder_step, decoder_step_dropout, decoder_step_heightmap, decoder_step_heightmap_dropout,
-                      dropout_keep_words, encode_dynamic_bits, pointer_pick, pointer_pick_draw, pointer_pick_given, pointer_scores, pointer_scores_static, run_episode)
-from .tools import DRL, DynamicBitsEncoder, HeightmapEncoder, Pointer, StateCritic, StaticFold, StepDropout, realCritic                # noqa: F401
+                      dropout_keep_words, encode_dynamic_bits, pointer_pick, pointer_pick_draw, pointer_pick_given, pointer_pick_static, pointer_pick_static_supported, pointer_scores, pointer_scores_static, run_episode)
+from .tools import DRL, DynamicBitsEncoder, HeightmapEncoder, Pointer, RollingDRL, StateCritic, StaticFold, StepDropout, realCritic                # noqa: F401
 
 __all__ = ["BatchedContainer", "Container", "MaskStepper", "EnvTransition", "EpisodeStepper", "PACKDataset", "initial_mask", "reward", "render", "episode_scores", "RollingDataset",
            "update_dynamic", "update_mask", "run_episode", "TapePolicy", "RandomFeasiblePolicy", "UniformPickPolicy", "UniformKeysPolicy",
-           "BestRatioPolicy", "PointerHeadPolicy", "pointer_pick", "pointer_pick_draw", "pointer_pick_given", "DRL", "encode_dynamic_bits", "DynamicBitsEncoder", "pointer_scores", "pointer_scores_static", "StaticFold", "decoder_step", "decoder_step_heightmap", "decoder_step_dropout", "decoder_step_heightmap_dropout", "dropout_keep_words", "StepDropout", "HeightmapEncoder", "Pointer", "critic_value", "StateCritic", "realCritic", "generate_instances", "RollingWindows", "RollingStepper", "run_rolling_episode", "TapError", "TapOverflowError"]
+           "BestRatioPolicy", "PointerHeadPolicy", "pointer_pick", "pointer_pick_draw", "pointer_pick_given", "pointer_pick_static", "pointer_pick_static_supported", "DRL", "RollingDRL", "encode_dynamic_bits", "DynamicBitsEncoder", "pointer_scores", "pointer_scores_static", "StaticFold", "decoder_step", "decoder_step_heightmap", "decoder_step_dropout", "decoder_step_heightmap_dropout", "dropout_keep_words", "StepDropout", "HeightmapEncoder", "Pointer", "critic_value", "StateCritic", "realCritic", "generate_instances", "RollingWindows", "RollingStepper", "run_rolling_episode", "TapError", "TapOverflowError"]

@@ -29,11 +29,12 @@ TAP_HIT_EPISODE_MACS2_WAVE, TAP_HIT_EPISODE_MACS3_WAVE = 23, 24
 TAP_HIT_TRIAL = 25                                             # trial.hip: k_trial_scores
 TAP_HIT_POLICY_PICK = 26                                       # policy.hip: k_policy_pick / _wide / _form / _wide_form / _backward
 TAP_HIT_ENCODE_BITS = 27                                       # encode.hip: k_encode_bits<HPL> / _bw_partial + _bw_reduce
-TAP_HIT_POINTER = 28                                           # pointer.hip: k_pointer_scores<HPL[, SS]> / _bw + _bw_reduce (last field: S of the static-rows form, 0 = proj)
+TAP_HIT_POINTER = 28                                           # pointer.hip: k_pointer_scores<HPL[, SS]> / _bw + _bw_reduce (last field: S of the static-rows form, 0 = proj; second field: 1 / 2 = the fused greedy / DRAW pick)
 TAP_HIT_DECODER = 29                                           # decoder.hip: k_decoder_step / k_decoder_step_bw
 TAP_HIT_HEIGHTMAP = 30                                         # heightmap.hip: k_decoder_step_hm
 TAP_HIT_CRITIC = 31                                            # critic.hip: k_critic_value<HPL> / _bw<HPL> + _bw_reduce
 TAP_P_GREEDY = 1
+TAP_PICK_GREEDY, TAP_PICK_DRAW = 1, 2                           # tap_pointer_pick_static's form (the launch record's second field)
 
 
 _vp_t = C.c_void_p
@@ -110,6 +111,7 @@ _PROTOS = {
     "tap_pointer_scores_static_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i] + [_vp] * 15 + [_sz, _vp]),
     "tap_pointer_scores_static_backward_scratch": (_sz, [_i, _i, _i, _i, _i]),
     "tap_pointer_scores_geometry": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32)]),
+    "tap_pointer_pick_static": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _i, _i] + [_vp] * 8 + [_i, _vp, _u32, _u32, _vp, _vp, _vp, _vp]),
     "tap_critic_value": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i] + [_vp] * 9),
     "tap_critic_value_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i] + [_vp] * 11 + [_sz, _vp]),
     "tap_critic_value_backward_scratch": (_sz, [_i, _i, _i, _i, _i, _i]),

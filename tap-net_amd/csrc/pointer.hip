@@ -38,6 +38,7 @@
 #include <algorithm>
 
 #include "tap_common.h"
+#include "tap_pick.h"
 
 namespace {
 
@@ -96,6 +97,17 @@ struct PtrArgsStatic : PtrArgs {
     const float *Gs, *gs;           // (3 Hd, S), (3 Hd,)
     int S;
 };
+// the fused form (tap_pointer_pick_static): the static-rows form with xs strided per env and the head's inputs and outputs.
+// logits may be null; attn and t are not written
+constexpr int PTR_NOPICK = 0, PTR_GREEDY = 1, PTR_DRAW = 2;   // the launch record's FORM field: the head's variant numbers
+struct PtrArgsPick : PtrArgsStatic {
+    size_t xs_env_stride;           // floats between consecutive envs of xs: >= S nR
+    const float *mask;              // (B, nR)
+    const long long *state;         // DRAW: int64[2] (seed, episode) on the device
+    unsigned step, env_offset;      // DRAW
+    int64_t *ptr;                   // (B,)
+    float *logp;                    // (B,)
+};
 
 __device__ __forceinline__ float ptr_wave_sum(float v)
 {
@@ -112,16 +124,22 @@ __device__ __forceinline__ float ptr_wave_max(float v)
 
 // the static term of U in the static-rows form: what a phase keeps of its chunk's G and g, a column's xs, and
 // P[x0 + lane + 64 i, c] = g, then fmaf(G[., s], xs[b, s, c], .) for s ascending (tap_critic_value's order)
-template <int HPL, int SS>
+// (XST: env b's rows start at xs + b es instead of xs + b S nR -- the fused form's strided xs)
+template <int HPL, int SS, bool XST = false>
 struct PtrStat {
     static constexpr int HCK = 64 * HPL, NX = SS > 0 ? SS : PTR_SMAX;
     struct Xs { float x[NX]; };
     const float *xs, *G, *g;
     float *lg;                      // SS == 0: lg[s * HCK + hl] = G[x0 + hl][s]
     int S;
+    size_t es;                      // XST only
     float gg[HPL], gw[HPL][SS > 0 ? SS : 1];
 
-    __device__ __forceinline__ void init(const PtrArgsStatic &a, float *lds_g) { xs = a.xs; G = a.Gs; g = a.gs; S = a.S; lg = lds_g; }
+    template <class A> __device__ __forceinline__ void init(const A &a, float *lds_g)
+    {
+        xs = a.xs; G = a.Gs; g = a.gs; S = a.S; lg = lds_g;
+        if constexpr (XST) es = a.xs_env_stride;
+    }
     // between the caller's barriers, like PtrSeg::fill
     __device__ __forceinline__ void fill(int x0, int tid, int lane)
     {
@@ -141,7 +159,7 @@ struct PtrStat {
     }
     __device__ __forceinline__ void load(int b, int nR, int c, Xs &x) const
     {
-        const float *xp = xs + (size_t)b * S * nR + c;
+        const float *xp = xs + (XST ? (size_t)b * es : (size_t)b * S * nR) + c;
 #pragma unroll
         for (int s = 0; s < NX; ++s) x.x[s] = (SS > 0 || s < S) ? xp[(size_t)s * nR] : 0.f;
     }
@@ -162,8 +180,8 @@ struct PtrStat {
         }
     }
 };
-template <int HPL>
-struct PtrStat<HPL, PTR_PROJ> {     // the proj form keeps nothing
+template <int HPL, bool XST>
+struct PtrStat<HPL, PTR_PROJ, XST> { // the proj form keeps nothing
     struct Xs {};
     __device__ __forceinline__ void init(const PtrArgs &, float *) {}
     __device__ __forceinline__ void fill(int, int, int) {}
@@ -172,14 +190,14 @@ struct PtrStat<HPL, PTR_PROJ> {     // the proj form keeps nothing
 
 // what a phase keeps of its segment's chunk: the LDS copy of the folded weights and the lane's k (and, in the static-rows
 // form, st)
-template <int HPL, int SS = PTR_PROJ>
+template <int HPL, int SS = PTR_PROJ, bool XST = false>
 struct PtrSeg {
     static constexpr int HCK = 64 * HPL, S = HCK + 1;
-    using Xs = typename PtrStat<HPL, SS>::Xs;
+    using Xs = typename PtrStat<HPL, SS, XST>::Xs;
     const float *lw;
     float kk[HPL];
     unsigned long long m0, m1;
-    PtrStat<HPL, SS> st;
+    PtrStat<HPL, SS, XST> st;
 
     // M[x0 + hl][r] -> lw[r * S + hl]: global reads in memory order, LDS writes at the odd stride S.  The caller's barriers
     // stand before (the previous chunk has been consumed) and after.
@@ -273,17 +291,71 @@ __device__ __forceinline__ float ptr_add_waves(const float *tp, int E, int HCK, 
     return v;
 }
 
-// both forms: A is PtrArgs (SS = PTR_PROJ, the proj form) or PtrArgsStatic (SS = 0, 2, 3, 4)
-template <int HPL, int SS = PTR_PROJ, class A = PtrArgs>
+// the head on a row of logits in the LDS, by one wavefront: k_policy_pick_wide<true> (PTR_GREEDY) / k_policy_pick_wide_form<2>
+// (PTR_DRAW) without probs -- the max pass, the weight pass for S (and the greedy pick), DRAW's second weight pass --, the row
+// read from lrow where those read global memory.  On rows of at most 64 columns the lane-group kernels write the same bytes
+// (tapenv.h: tap_pointer_pick_static)
+template <int FORM>
+__device__ __forceinline__ void ptr_pick_row(const PtrArgsPick &a, const float *lrow, size_t env, int lane)
+{
+    const int nR = a.nR;
+    const float *mrow = a.mask + env * nR;
+    const float ninf = -__builtin_huge_valf();
+    float m = ninf;
+    bool mine = false;
+    for (int base = 0; base < nR; base += 64) {                 // the max pass
+        const int col = base + lane, at = min(col, nR - 1);
+        const float l_raw = lrow[at], mv = mrow[at];
+        const bool sel = col < nR && mv != 0.f;
+        m = fmaxf(m, sel ? l_raw : ninf);
+        mine |= sel;
+    }
+    m = group_fmaxf<64>(m);
+    const bool any = __ballot(mine) != 0;
+    double S = 0.0;
+    int p = -1;
+    for (int base = 0; base < nR; base += 64) {                 // the weight pass, for S (and the greedy pick)
+        const Chunk c = pick_chunk(lrow, mrow, base, lane, nR, m, S);
+        if (FORM == PTR_GREEDY && p < 0) {
+            const u64 q = __ballot(c.sel && c.l == m);
+            if (q) p = base + __ffsll((long long)q) - 1;
+        }
+    }
+    if (FORM == PTR_DRAW) {                                     // the weight pass again, for the pick
+        const double t = (double)draw_uniform(a, env) * S;
+        double run = 0.0;
+        int last = 0;
+        for (int base = 0; base < nR; base += 64) {
+            const Chunk c = pick_chunk(lrow, mrow, base, lane, nR, m, run);
+            const u64 q = __ballot(c.sel && c.cum > t), sb = __ballot(c.sel);
+            if (p < 0 && q) p = base + __ffsll((long long)q) - 1;   // the first chunk with a qualifying column decides
+            if (sb) last = base + 63 - __clzll((long long)sb);
+            if (p >= 0) break;                                  // wave-uniform
+        }
+        if (p < 0) p = last;                                    // t >= S: the last selectable column (0 on an empty row)
+    }
+    if (p < 0) p = 0;
+    const float l_ptr = lrow[p];
+    if (lane == 0) {
+        a.ptr[env] = p;
+        a.logp[env] = pick_logp(any, l_ptr, m, S);
+    }
+}
+
+// every forward form.  FORM = PTR_NOPICK: tap_pointer_scores / _static -- A is PtrArgs (SS = PTR_PROJ, the proj form) or
+// PtrArgsStatic (SS = 0, 2, 3, 4).  FORM = PTR_GREEDY / PTR_DRAW: the fused form (A = PtrArgsPick, tap_pointer_pick_static) --
+// xs strided, attn and t stay in the LDS, and the head runs on the LDS row of logits where the others store it
+template <int HPL, int SS = PTR_PROJ, class A = PtrArgs, int FORM = PTR_NOPICK>
 __global__ void __launch_bounds__(TAP_BLOCK) k_pointer_scores(A a)
 {
     constexpr int HCK = 64 * HPL, S = HCK + 1;
+    constexpr bool PICK = FORM != PTR_NOPICK;
     extern __shared__ float ptr_lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = TAP_WAVE_INDEX();
     const int nR = a.nR, Hd = a.Hd, E = a.epb, nch = Hd / HCK;
     float *lw = ptr_lds, *sl = lw + a.rows * S, *tp = sl + E * nR, *tl = tp + PTR_NW * E * HCK;
     const int e0 = (int)blockIdx.x * E, ne = min(E, a.B - e0);
-    PtrSeg<HPL, SS> sg;
+    PtrSeg<HPL, SS, PICK> sg;
     sg.st.init(a, tl + E * Hd);
 
     // phase 1, segment 0: s[c] = sum_j va[j] tanh(U[j, c] + q[j]) -> sl[e][c]
@@ -323,7 +395,7 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_pointer_scores(A a)
         for (int c = lane; c < nR; c += 64) {
             const float x = sl[e * nR + c] / z;
             sl[e * nR + c] = x;
-            a.attn[(size_t)(e0 + e) * nR + c] = x;
+            if constexpr (!PICK) a.attn[(size_t)(e0 + e) * nR + c] = x;
         }
     }
     // phase 2, segment 2: t[j] = sum_c attn[c] U[2 Hd + j, c] -> tl[e][j]
@@ -348,7 +420,7 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_pointer_scores(A a)
             const int e = i / HCK, jl = i - e * HCK;
             const float v = ptr_add_waves(tp, E, HCK, e, jl);
             tl[e * Hd + ch * HCK + jl] = v;
-            a.t[(size_t)(e0 + e) * Hd + ch * HCK + jl] = v;
+            if constexpr (!PICK) a.t[(size_t)(e0 + e) * Hd + ch * HCK + jl] = v;
         }
     }
     // phase 3, segment 1: logits[c] = sum_j vp[j] tanh(U[Hd + j, c] + t[j]) -> sl[e][c] (attn has been consumed)
@@ -373,7 +445,14 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_pointer_scores(A a)
         }
     }
     __syncthreads();
-    for (int i = tid; i < ne * nR; i += TAP_BLOCK) a.logits[(size_t)e0 * nR + i] = sl[i];
+    if constexpr (!PICK) {
+        for (int i = tid; i < ne * nR; i += TAP_BLOCK) a.logits[(size_t)e0 * nR + i] = sl[i];
+    } else {
+        if (a.logits)
+            for (int i = tid; i < ne * nR; i += TAP_BLOCK) a.logits[(size_t)e0 * nR + i] = sl[i];
+        // the head: a wavefront per env, as the softmax above (sl is only read from here on)
+        for (int e = wave; e < ne; e += PTR_NW) ptr_pick_row<FORM>(a, sl + e * nR, (size_t)(e0 + e), lane);
+    }
 }
 
 // ---- backward -----------------------------------------------------------------------------------------------------
@@ -598,6 +677,25 @@ void ptr_hit_static(tap_ctx *ctx, const PtrGeom &geo, int backward, int S)
     tap_variant_hit_key(ctx, key);
 }
 
+// the fused form's launch: the instantiation (HPL, SS, FORM)
+template <int HPL, int SS>
+void ptr_launch_pick_ss(int form, const PtrGeom &geo, hipStream_t st, const PtrArgsPick &a)
+{
+    const dim3 grid((unsigned)geo.blocks), block(TAP_BLOCK);
+    if (form == PTR_GREEDY) hipLaunchKernelGGL((k_pointer_scores<HPL, SS, PtrArgsPick, PTR_GREEDY>), grid, block, geo.lds, st, a);
+    else hipLaunchKernelGGL((k_pointer_scores<HPL, SS, PtrArgsPick, PTR_DRAW>), grid, block, geo.lds, st, a);
+}
+template <int HPL>
+void ptr_launch_pick_hpl(int form, const PtrGeom &geo, hipStream_t st, const PtrArgsPick &a)
+{
+    switch (ptr_static_ss(a.S)) {
+    case 2: ptr_launch_pick_ss<HPL, 2>(form, geo, st, a); break;
+    case 3: ptr_launch_pick_ss<HPL, 3>(form, geo, st, a); break;
+    case 4: ptr_launch_pick_ss<HPL, 4>(form, geo, st, a); break;
+    default: ptr_launch_pick_ss<HPL, 0>(form, geo, st, a); break;
+    }
+}
+
 } // namespace
 
 extern "C" int tap_pointer_scores(tap_ctx *ctx, const float *proj, const unsigned long long *bits, int B, int nR, int rows, int Hd,
@@ -740,5 +838,41 @@ extern "C" int tap_pointer_scores_static_backward(tap_ctx *ctx, const float *xs,
                        static_cast<const float *>(scratch), geo.blocks, Hd, dva_out, dvp_out);
     TAP_LAUNCH_CHECK(ctx, "k_pointer_scores_bw_reduce");
     ptr_hit_static(ctx, geo, 1, S);
+    return TAP_OK;
+}
+
+extern "C" int tap_pointer_pick_static(tap_ctx *ctx, const float *xs, size_t xs_env_stride, const unsigned long long *bits, int B, int nR,
+                                       int rows, int Hd, int S, const float *G, const float *g, const float *M, const float *k,
+                                       const float *q, const float *va, const float *vp, const float *mask, int form,
+                                       const int64_t *state, uint32_t step, uint32_t env_offset, int64_t *ptr_out, float *logp_out,
+                                       float *logits_out, void *stream)
+{
+    int rc = ptr_check_dims_static(ctx, "pointer pick static", B, nR, rows, Hd, S);
+    if (rc != TAP_OK) return rc;
+    if (form != TAP_PICK_GREEDY && form != TAP_PICK_DRAW) return tap_fail(ctx, TAP_E_INVALID, "pointer pick static: form %d", form);
+    if (B == 0) return TAP_OK; // an empty batch has no buffers to check
+    if (!xs || !bits || !G || !g || !M || !k || !q || !va || !vp || !mask || !ptr_out || !logp_out)
+        return tap_fail(ctx, TAP_E_INVALID, "pointer pick static: null buffer");
+    if (form == TAP_PICK_DRAW && (!state || ptr_misaligned(state, 8)))
+        return tap_fail(ctx, TAP_E_INVALID, "pointer pick static: state must be an 8-byte aligned int64[2]");
+    if (xs_env_stride < (size_t)S * (size_t)nR)
+        return tap_fail(ctx, TAP_E_INVALID, "pointer pick static: xs_env_stride %zu below S * nR = %zu", xs_env_stride, (size_t)S * (size_t)nR);
+    if ((rc = ptr_check_shape_static(ctx, "pointer pick static", nR, rows, Hd, S)) != TAP_OK) return rc;
+    const void *f32[] = {xs, G, g, M, k, q, va, vp, mask, logp_out, logits_out};
+    bool bad = ptr_misaligned(bits, 8) || ptr_misaligned(ptr_out, 8);
+    for (const void *p : f32) bad = bad || ptr_misaligned(p, 4);
+    if (bad) return tap_fail(ctx, TAP_E_INVALID, "pointer pick static: bits and ptr_out must be 8-byte and the float buffers 4-byte aligned");
+    static_assert(PTR_GREEDY == TAP_PICK_GREEDY && PTR_DRAW == TAP_PICK_DRAW, "the entry's forms are the kernels'");
+    const PtrGeom geo = ptr_geom(B, nR, rows, Hd, false, S);
+    const PtrArgsPick a = {{{nullptr, bits, M, k, q, va, vp, logits_out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                             B, nR, rows, Hd, geo.planes, geo.epb, 0},
+                            xs, G, g, S},
+                           xs_env_stride, mask, (const long long *)state, step, env_offset, ptr_out, logp_out};
+    hipStream_t st = (hipStream_t)stream;
+    if (geo.hpl == 1) ptr_launch_pick_hpl<1>(form, geo, st, a);
+    else ptr_launch_pick_hpl<2>(form, geo, st, a);
+    TAP_LAUNCH_CHECK(ctx, "k_pointer_scores (pick)");
+    const int32_t key[7] = {TAP_HIT_POINTER, form, geo.hpl, geo.planes, geo.nch, 0, S};
+    tap_variant_hit_key(ctx, key);
     return TAP_OK;
 }

@@ -361,6 +361,47 @@ class RollingDataset(object):
         return blocks[:num_samples, :n], positions[:num_samples]
 
 
+VALIDATE_FILES = ('valid_size', 'box_size', 'empty_size', 'stable_num', 'packing_height', 'time')
+
+
+def validate(actor, valid_data, save_path=None, *, tour=None):
+    """rolling.validate (rolling.py:541-665) for the whole validation set in ONE call of a ``tools.RollingDRL``:
+    ``actor(valid_data.windows)`` in ``eval()``, then the reference's per-instance figures (rolling.py:640-653) read from the
+    module's ``BatchedContainer`` -- ``valid_size``; ``box_size`` = the container's footprint times the highest column;
+    ``empty_size``; ``stable_num`` = the number of stable blocks times net_blocks_num / total_blocks_num, the reference's
+    factor; ``packing_height`` = ``container.bounding_box[-1]``, which the reference's Container never updates
+    (tools.py:3708 is commented out): zeros, as there.  -> the five float64 arrays (B,), in that order.  With ``save_path``
+    they are written with ``np.savetxt`` to the reference's ``batch-*.txt`` names in that directory (rolling.py:660-665), and
+    ``batch-time.txt`` holds the call's wall time divided by the batch for every instance.  Nothing is drawn.  ``tour``
+    (keyword-only, not in the reference): the module's ``tour=``, the figures of a given tour."""
+    import os
+    import time
+
+    import numpy as np
+    actor.eval()
+    rw = valid_data.windows
+    B = int(rw.B)
+    if rw.device.type == 'cuda':
+        torch.cuda.synchronize(rw.device)
+    start = time.time()
+    actor(rw, tour=tour)
+    env = actor.last_env
+    cnt = env.counters.cpu().numpy().astype(np.float64)                              # one launch, one host read
+    height = env.heightmap.reshape(B, -1).max(1).values.cpu().numpy().astype(np.float64)
+    wall = time.time() - start
+    footprint = float(env.desc.W * env.desc.L)
+    valid_size, empty_size = cnt[:, 0], cnt[:, 1]
+    box_size = footprint * height
+    stable_num = cnt[:, 2] * (float(rw.child) / float(rw.N))
+    packing_height = np.zeros(B, np.float64)
+    if save_path is not None:
+        os.makedirs(save_path, exist_ok=True)
+        cols = (valid_size, box_size, empty_size, stable_num, packing_height, np.full(B, wall / max(B, 1)))
+        for name, col in zip(VALIDATE_FILES, cols):
+            np.savetxt(os.path.join(save_path, 'batch-%s.txt' % name), col)
+    return valid_size, box_size, empty_size, stable_num, packing_height
+
+
 def run_rolling_episode(blocks, positions, initial_container_size, policy, container_width, container_height,
                         child_graph_size=10, reward_type='C+P+S-lb-soft', heightmap_type='diff',
                         packing_strategy='LB_GREEDY', record=False, fused=True, steppers=None, check='nan',

@@ -706,6 +706,97 @@ def pointer_scores_static(xs, bits, G, g, M, k, q, va, vp, rows=None):
     return logits
 
 
+def pointer_pick_static_supported(rows, nR, Hd, S):
+    """whether tap_pointer_pick_static has a kernel for this shape: ``pointer_scores_static_supported``'s shapes"""
+    return pointer_scores_static_supported(rows, nR, Hd, S)
+
+
+def _rows_view_stride(xs):
+    """the env stride (in elements) of an ``xs`` (B, S, nR) that the fused launch can read in place -- the last axis
+    contiguous, the rows nR apart, the envs at least S nR apart --, else None"""
+    B, S, nR = (int(v) for v in xs.shape)
+    sb, ss, sc = (int(v) for v in xs.stride())
+    if (nR > 1 and sc != 1) or (S > 1 and ss != nR) or (B > 1 and sb < S * nR):
+        return None
+    return sb if B > 1 else S * nR
+
+
+def _pick_static_into(xs, stride, bits, G, g, M, k, q, va, vp, mask, rec, rows, ptr, logp, logits):
+    """tap_pointer_pick_static on prepared buffers: one launch on the current stream, nothing allocated.  ``rec``: a checked
+    PickRecord (DRAW) or None (GREEDY)"""
+    dev = xs.device
+    c = _lib.ctx(dev)
+    B, S, nR = (int(v) for v in xs.shape)
+    Hd = int(q.shape[1])
+    if rec is None:
+        form, state, step, off = _lib.TAP_PICK_GREEDY, None, 0, 0
+    else:
+        if rec.state.device != dev:
+            raise ValueError("the pick's state lives on %s, the step's tensors on %s: the launch reads the state on its own device"
+                             % (rec.state.device, dev))
+        form, state, step, off = _lib.TAP_PICK_DRAW, rec.state, int(rec.step) & _M32, int(rec.env_offset) & _M32
+    _lib.check(_lib.lib().tap_pointer_pick_static(c, _lib.ptr(xs), stride, _lib.ptr(bits), B, nR, rows, Hd, S, _lib.ptr(G), _lib.ptr(g),
+                                                  _lib.ptr(M), _lib.ptr(k), _lib.ptr(q), _lib.ptr(va), _lib.ptr(vp), _lib.ptr(mask),
+                                                  form, _lib.ptr(state), step, off, _lib.ptr(ptr), _lib.ptr(logp), _lib.ptr(logits),
+                                                  _lib.stream_of(dev)), c)
+
+
+def pointer_pick_static(xs, bits, G, g, M, k, q, va, vp, mask, source=None, rows=None, want_logits=False):
+    """``pointer_scores_static`` and the decoding head in ONE launch (tapenv.h: tap_pointer_pick_static), for inference on
+    windows whose static rows change every step -> (ptr (B,) int64, logp (B,) float32[, logits (B, nR) float32]).  The logits stay
+    in the launch's LDS: no ``attn``, no ``t``, no head launch.  ``xs`` (B, S, nR) may be a view whose last axis is contiguous
+    and whose rows are nR apart -- ``static[:, 1:, :]`` of a (B, 1 + S, nR) window is read where it lies, without a copy --;
+    anything else is made contiguous.  ``mask`` (B, nR): the stepper's ``current_mask``.  ``source`` None picks greedily
+    (``pointer_pick(logits, mask)``'s bytes on ``pointer_scores_static``'s logits); a ``tools.StepDropout`` -- the call takes
+    its next pick record --, a ``PickRecord`` or a plain (state, step[, env_offset]) draws (``pointer_pick_draw``'s bytes).
+    The other arguments as ``pointer_scores_static`` takes them.  No autograd: with grad enabled, an input that requires grad
+    raises ValueError (use ``pointer_scores_static`` and the head).  A shape without a kernel
+    (``pointer_pick_static_supported``) raises ValueError."""
+    if bits.dtype is not torch.int64:
+        raise TypeError("bits must be the int64 shadow (pack.dynamic_bits), got %s" % (bits.dtype,))
+    if xs.dim() != 3 or not xs.is_floating_point():
+        raise ValueError("xs must be a floating (B, S, nR) tensor, got %s %s" % (xs.dtype, tuple(xs.shape)))
+    B, S, nR = (int(v) for v in xs.shape)
+    if not 1 <= S <= 8:
+        raise ValueError("xs has %d static rows; the kernel takes 1 .. 8" % S)
+    if M.dim() != 2 or int(M.shape[0]) % 3 or not M.is_floating_point():
+        raise ValueError("M must be a floating (3 Hd, rows) tensor, got %s %s" % (M.dtype, tuple(M.shape)))
+    Hd = int(M.shape[0]) // 3
+    rows = int(M.shape[1]) if rows is None else int(rows)
+    if rows != int(M.shape[1]):
+        raise ValueError("M has %d rows' columns, rows is %d" % (int(M.shape[1]), rows))
+    for name, v, shape in (("G", G, (3 * Hd, S)), ("g", g, (3 * Hd,)), ("k", k, (3 * Hd,)), ("q", q, (B, Hd)), ("va", va, (Hd,)),
+                           ("vp", vp, (Hd,)), ("mask", mask, (B, nR))):
+        if tuple(v.shape) != shape or not v.is_floating_point():
+            raise ValueError("%s must be a floating %s tensor, got %s %s" % (name, shape, v.dtype, tuple(v.shape)))
+    planes = 2 if rows > 64 else 1
+    if bits.dim() not in (2, 3) or int(bits.shape[0]) != B or int(math.prod(bits.shape[1:])) != planes * nR or \
+            (bits.dim() == 3 and tuple(bits.shape[1:]) != (planes, nR)):
+        raise ValueError("xs of shape %s and bits of shape %s are not (B, S, nR) and the shadow of B envs of a (%d, nR) window"
+                         % (tuple(xs.shape), tuple(bits.shape), rows))
+    if rows < 1 or nR < 1 or not pointer_pick_static_supported(rows, nR, Hd, S):
+        raise ValueError("no pointer kernel for rows %d, nR %d, Hd %d, S %d (rows <= 128, nR %% 4 == 0, nR <= 256, Hd 64 / 128 / 256, "
+                         "S <= 8)" % (rows, nR, Hd, S))
+    if torch.is_grad_enabled() and any(v.requires_grad for v in (xs, G, g, M, k, q, va, vp, mask)):
+        raise ValueError("pointer_pick_static has no backward: call it under torch.no_grad(), or use pointer_scores_static and "
+                         "pointer_pick")
+    rec = None if source is None else _pick_record(source)
+    dev = _lib.resolve_device(bits.device)
+    if not bits.is_contiguous() or bits.device != dev:
+        bits = bits.to(dev).contiguous()
+    xs = xs.detach()
+    stride = _rows_view_stride(xs) if xs.dtype is torch.float32 and xs.device == dev else None
+    if stride is None:
+        xs = _prep_f32(xs, dev)
+        stride = S * nR
+    G, g, M, k, q, va, vp, mask = (_prep_f32(v.detach(), dev) for v in (G, g, M, k, q, va, vp, mask))
+    ptr = torch.empty(B, dtype=torch.int64, device=dev)
+    logp = torch.empty(B, dtype=torch.float32, device=dev)
+    logits = torch.empty(B, nR, dtype=torch.float32, device=dev) if want_logits else None
+    _pick_static_into(xs, stride, bits, G, g, M, k, q, va, vp, mask, rec, rows, ptr, logp, logits)
+    return (ptr, logp, logits) if want_logits else (ptr, logp)
+
+
 def critic_value_supported(rows, nR, H, S, blocks):
     """whether tap_critic_value has a kernel for this shape: a window with a shadow, H 64, 128 or 256, 1 <= S <= 8 static
     rows and 1 <= blocks <= 8 process blocks"""

@@ -450,9 +450,39 @@ class Pointer(nn.Module):
         ``bits`` raises ValueError.  In ``eval()`` it is ``forward_step`` and the step counter stays."""
         return self._forward_step(proj, bits, fold, decoder_static, decoder_dynamic, last_hh, dropout)
 
-    def _forward_step(self, proj, bits, fold, decoder_static, decoder_dynamic, last_hh, dropout):
-        from .rollout import (decoder_step_heightmap_supported, decoder_step_supported, pointer_scores, pointer_scores_static,
-                              pointer_scores_static_supported, pointer_scores_supported, _decoder_step, _decoder_step_heightmap)
+    def forward_step_pick(self, static_fold, bits, fold, decoder_static, decoder_dynamic, last_hh, current_mask, source=None,
+                          dropout=None, want_logits=False):
+        """An INFERENCE step with its pick in TWO launches -> (ptr (B,) int64, logp (B,) float32[, logits], last_hh): the decoder
+        step as ``forward_step`` / ``forward_step_dropout`` chooses it (plain, height-map, dropout -- ``dropout`` is a
+        ``StepDropout``, read in training mode only), then ``rollout.pointer_pick_static``: scores and pick in one launch, the
+        logits never leaving it, ``static_fold.xs`` read as the view it is (``StaticFold.with_rows``).  ``current_mask``: the
+        stepper's; ``source`` None picks greedily, a ``StepDropout`` / ``PickRecord`` draws.  ``want_logits`` returns the
+        logits too (the launch stores them as ``pointer_scores_static`` does).  The bytes are those of ``forward_step[_dropout]``
+        followed by ``rollout.pointer_pick`` / ``pointer_pick_draw``, and exactly those launches run instead -- ``pointer_pick_torch``
+        off the GPU -- when grad is enabled and something requires it, off the GPU, on a shape without a kernel, wherever
+        ``forward_step`` takes its torch path, and when ``static_fold`` is a ``proj`` tensor."""
+        from .rollout import _pick_record, pick_uniforms, pointer_pick, pointer_pick_draw, pointer_pick_torch
+        out = self._forward_step(static_fold, bits, fold, decoder_static, decoder_dynamic, last_hh, dropout,
+                                 pick=(current_mask, source, want_logits))
+        if len(out) > 2:
+            return out
+        logits, last_hh = out
+        if not logits.is_cuda:
+            u = None
+            if source is not None:
+                rec = _pick_record(source)
+                u = pick_uniforms(rec.state, rec.step, int(logits.shape[0]), rec.env_offset)
+            ptr, logp = pointer_pick_torch(logits, current_mask, u)
+        elif source is not None:
+            ptr, logp = pointer_pick_draw(logits, current_mask, source)
+        else:
+            ptr, logp = pointer_pick(logits, current_mask)
+        return (ptr, logp, logits, last_hh) if want_logits else (ptr, logp, last_hh)
+
+    def _forward_step(self, proj, bits, fold, decoder_static, decoder_dynamic, last_hh, dropout, pick=None):
+        from .rollout import (decoder_step_heightmap_supported, decoder_step_supported, pointer_pick_static, pointer_scores,
+                              pointer_scores_static, pointer_scores_static_supported, pointer_scores_supported, _decoder_step,
+                              _decoder_step_heightmap)
         static = isinstance(proj, StaticFold)
         Hd, nR = self.decoder_hidden_size, proj.nR if static else int(proj.shape[2])
         Ks = 0 if decoder_static is None or fold.static_decoder is None else int(decoder_static[0].numel())
@@ -484,6 +514,11 @@ class Pointer(nn.Module):
         else:
             h_new, q = _decoder_step(decoder_static if Ks else None, decoder_dynamic if Kd else None,
                                      None if last_hh is None else last_hh[0], fold.P, fold.c, fold.w_hh, fold.b_hh, fold.Wq, rec)
+        if pick is not None and static and not (torch.is_grad_enabled() and any(
+                v.requires_grad for v in (proj.G, proj.g, fold.M, fold.k, q, fold.va, fold.vp))):
+            current_mask, source, want_logits = pick
+            return pointer_pick_static(proj.xs, bits, proj.G, proj.g, fold.M, fold.k, q, fold.va, fold.vp, current_mask, source,
+                                       rows=fold.rows, want_logits=want_logits) + (h_new.unsqueeze(0),)
         if static:
             logits = pointer_scores_static(proj.xs, bits, proj.G, proj.g, fold.M, fold.k, q, fold.va, fold.vp, rows=fold.rows)
         else:
@@ -630,6 +665,21 @@ class StaticFold(object):
     that the static encoder sees, detached and contiguous; ``G`` (3 Hd, S) and ``g`` (3 Hd,) the encoder folded into the two W
     (``rollout.pointer_scores_static``'s parameters); ``static_encoder`` for the torch path; ``nR`` and ``S``."""
     __slots__ = ("xs", "G", "g", "static_encoder", "nR", "S")
+
+    def with_rows(self, xs):
+        """-> a record sharing ``G``, ``g`` and ``static_encoder`` with this one, its ``xs`` re-pointed at other rows of the
+        same shape: a rolling window's ``static[:, 1:, :]`` changes every step while the fold of the parameters does not.
+        ``xs`` (B, S, nR) is kept as the view it is (detached, no copy) and must be one the fused launch can read in place: the
+        last axis contiguous, the rows nR apart, the envs at least S nR apart (``rollout.pointer_pick_static``)."""
+        from .rollout import _rows_view_stride
+        if xs.dim() != 3 or tuple(int(v) for v in xs.shape[1:]) != (self.S, self.nR) or not xs.is_floating_point():
+            raise ValueError("xs must be a floating (B, %d, %d) tensor, got %s %s" % (self.S, self.nR, xs.dtype, tuple(xs.shape)))
+        if _rows_view_stride(xs) is None:
+            raise ValueError("xs of shape %s has strides %s: its last axis must be contiguous, its rows %d apart and its envs at "
+                             "least %d apart" % (tuple(xs.shape), tuple(xs.stride()), self.nR, self.S * self.nR))
+        sf = StaticFold()
+        sf.xs, sf.G, sf.g, sf.static_encoder, sf.nR, sf.S = xs.detach(), self.G, self.g, self.static_encoder, self.nR, self.S
+        return sf
 
 
 class StepDropout(object):
@@ -838,6 +888,146 @@ class DRL(nn.Module):
             if self.decoder_input_type != 'shape_only':
                 decoder_dynamic = sp.decoder_dynamic
         return sp.tour, torch.stack(logps, dim=1), None, _flagged_reward(-sp.ratio, check, sp.env)
+
+
+class RollingDRL(DRL):
+    """The reference's rolling actor (rolling.DRL, rolling.py:201-460, driven by rolling.validate's loop, rolling.py:589-637) as
+    ONE module that owns the rolling episode: a trained ``child``-block actor packs N >= child blocks by sliding a window over
+    the precedence graph.  The constructor is the reference's, argument for argument -- ``model.DRL``'s with ``containers``
+    between ``packing_strategy`` and ``update_fn`` --; ``containers`` may be None or anything else and is ignored: the module
+    keeps its own ``BatchedContainer`` (``last_env`` after a call).  The children are ``DRL``'s, so a trainer's ``actor.pt``
+    loads with ``strict=True``; in 2D these are rolling.DRL's own names and shapes.  In 3D they are model.DRL's (a
+    ``HeightmapEncoder`` from this module): the reference's ``rolling.HeightmapEncoder`` cannot be constructed there -- it
+    divides a tuple by 4.  The input types ``DRL`` refuses are refused.  Keyword-only: ``seed`` and ``env_offset`` of the
+    module's ``StepDropout``, and ``fused_pick``: a step's scores and pick in one launch (``Pointer.forward_step_pick``).
+
+    ``forward(windows, decoder_input=None, last_hh=None, *, tour=None, steppers=None, check='nan', record=False)`` -> (tour_idx
+    (B, N) int64 of window-local picks, tour_logp (B, N) float32, nodes (B, N) int32 global block ids in packing order, reward
+    (B,)).  ``windows``: a fresh ``rolling.RollingWindows`` (``RollingDataset(...).windows``).  The whole call runs under
+    ``torch.no_grad()``: rolling is inference.  One call is rolling.validate's inner loop for the whole batch: N - child
+    one-step windows on a ``RollingStepper``, the hand-over to the ``EpisodeStepper`` of the last graph, ``child`` steps there
+    (``rolling._run_rolling_steppers`` with ``expand_dynamic=False``); ``last_hh`` and the decoder inputs go from window to
+    window; ``fold_static``'s G and g, ``fold_decoder`` and ``fold_episode`` are computed once; every step takes
+    ``StaticFold.with_rows(static[:, 1:, :])`` of the current window and its shadow.  ``decoder_input=None``: the zeros the
+    stepper starts from (the reference's x0).  The head: greedy in ``eval()``; in ``train()`` DRAW from the module's
+    ``StepDropout`` (``next_episode()`` once per call), with dropout as ``forward_step_dropout`` applies it when p > 0; a
+    ``tour`` (B, N) of window-local picks is scored through GIVEN.  With ``fused_pick`` and no ``tour`` a step is
+    ``forward_step_pick`` (two launches and the stepper's), otherwise ``forward_step[_dropout]`` and the stand-alone head.
+    ``record=True`` keeps each step's ``logits`` and ``last_hh`` in ``last_record``.
+
+    Kept between calls: one container and one stepper pair per (B, N, D, child, device) -- ``steppers=`` takes the place of
+    that pair, as in ``run_rolling_episode``; off the GPU it must be given -- and one ``StepDropout`` per device.  ``tour_idx``
+    and ``nodes`` are the pair's buffers.  Windows without a one-word shadow (3 * child > 64, or child * R not a multiple of 4)
+    raise ValueError.  In ``double()`` the module is its own float64 model, as ``DRL`` is."""
+
+    def __init__(self, static_size, dynamic_size, encoder_hidden_size, decoder_hidden_size, use_cuda, input_type, allow_rot,
+                 container_width, container_height, block_dim, reward_type, decoder_input_type, heightmap_type, packing_strategy,
+                 containers, update_fn, mask_fn, num_layers=1, dropout=0., unit=1, *, seed=0, env_offset=0, fused_pick=True):
+        super(RollingDRL, self).__init__(static_size, dynamic_size, encoder_hidden_size, decoder_hidden_size, use_cuda, input_type,
+                                         allow_rot, container_width, container_height, block_dim, reward_type, decoder_input_type,
+                                         heightmap_type, packing_strategy, update_fn, mask_fn, num_layers, dropout, unit, seed=seed,
+                                         env_offset=env_offset, fold='static')
+        self.fused_pick = bool(fused_pick)
+        self._pairs = {}
+        self.last_env = None                # the containers of the latest forward (rolling.validate reads its metrics there)
+        self.last_record = None
+
+    def _own_pair(self, rw):
+        from .pack import EpisodeStepper
+        from .rolling import RollingStepper
+        key = (rw.B, rw.N, rw.D, rw.child, rw.device)
+        if key not in self._pairs:
+            W = self.container_width
+            cs = [W, self.container_height] if rw.D == 2 else [W, W, self.container_height]
+            env = BatchedContainer(rw.B, cs, rw.N, self.reward_type, self.heightmap_type, packing_strategy=self.packing_strategy,
+                                   device=rw.device)
+            roll = RollingStepper(rw, env, expand_dynamic=False)
+            last = EpisodeStepper(roll._static[0], (rw.B, 3 * rw.child, rw.child * rw.R), env, steps=rw.child, tour=roll.tour,
+                                  tour_col0=rw.N - rw.child, expand_dynamic=False)
+            self._pairs[key] = (roll, last)
+        return self._pairs[key]
+
+    def forward(self, windows, decoder_input=None, last_hh=None, *, tour=None, steppers=None, check='nan', record=False):
+        from .rolling import _run_rolling_steppers
+        from .rollout import pick_uniforms, pointer_pick, pointer_pick_draw, pointer_pick_given, pointer_pick_torch
+        rw = windows
+        B, N, child, R = int(rw.B), int(rw.N), int(rw.child), int(rw.R)
+        if 3 * child > 64 or (child * R) % 4:
+            raise ValueError("RollingDRL needs windows with a one-word bit shadow: 3 * child <= 64 and child * R a multiple of 4, "
+                             "got child %d, R %d" % (child, R))
+        if int(rw.D) != self.block_dim:
+            raise ValueError("the windows hold %dD blocks, the actor was built for block_dim %d" % (rw.D, self.block_dim))
+        dev = torch.device(rw.device)
+        if steppers is None:
+            if dev.type != 'cuda':
+                raise ValueError("off the GPU RollingDRL needs steppers=(rolling stepper, last-graph stepper): the package's "
+                                 "steppers live on the device")
+            steppers = self._own_pair(rw)
+        roll, last = steppers
+        if tour is not None:
+            if tuple(tour.shape) != (B, N):
+                raise ValueError("tour must be (%d, %d), got %s" % (B, N, tuple(tour.shape)))
+            tour = tour.to(device=dev, dtype=torch.int64).t().contiguous()      # step-major: a step's picks are a contiguous row
+        with torch.no_grad():
+            mods = self._modules
+            pointer, static_encoder = mods['pointer'], mods['static_encoder']
+            drop = None
+            if self.training:
+                drop = self.step_dropout(dev)
+                drop.next_episode()
+            dropping = self.training and (pointer.drop_rnn.p > 0 or pointer.drop_hh.p > 0)
+            P, c = pointer.fold_decoder(mods.get('decoder', mods.get('static_decoder')), mods.get('dynamic_decoder'), combine='cat')
+            fold = pointer.fold_episode(mods['dynamic_encoder'], P, c)
+            fused = self.fused_pick and tour is None
+            kind = self.decoder_input_type
+            carry = dict(base=None, last_hh=last_hh)
+            logps, rec_steps = [], ([] if record else None)
+
+            def policy(step, static, dynamic, current_mask, mask, decoder_static, decoder_dynamic):
+                bits = roll.bits if step < N - child else last.dynamic_bits
+                xs = static[:, 1:, :]
+                if carry['base'] is None:
+                    carry['base'] = pointer.fold_static(static_encoder, xs)     # G and g, once per call
+                sf = carry['base'].with_rows(xs)
+                if step == 0 and decoder_input is not None:
+                    if kind == 'shape_heightmap':
+                        decoder_static, decoder_dynamic = decoder_input
+                    elif kind == 'shape_only':
+                        decoder_static = decoder_input
+                    else:
+                        decoder_dynamic = decoder_input[1] if isinstance(decoder_input, (tuple, list)) else decoder_input
+                    decoder_static = None if decoder_static is None else decoder_static.expand(B, *decoder_static.shape[1:])
+                    decoder_dynamic = None if decoder_dynamic is None else decoder_dynamic.expand(B, *decoder_dynamic.shape[1:])
+                ds = None if kind == 'heightmap_only' else decoder_static
+                dd = None if kind == 'shape_only' else decoder_dynamic
+                sd = drop if dropping else None
+                if fused:
+                    out = pointer.forward_step_pick(sf, bits, fold, ds, dd, carry['last_hh'], current_mask, drop, sd, want_logits=record)
+                    ptr, logp, hh = out[0], out[1], out[-1]
+                    logits = out[2] if record else None
+                else:
+                    logits, hh = pointer._forward_step(sf, bits, fold, ds, dd, carry['last_hh'], sd)
+                    if not logits.is_cuda:
+                        u = None if drop is None or tour is not None else pick_uniforms(*drop.take_pick()[:2], B, drop.env_offset)
+                        ptr, logp = pointer_pick_torch(logits, current_mask, u, None if tour is None else tour[step])
+                    elif tour is not None:
+                        ptr = tour[step]
+                        logp = pointer_pick_given(logits, current_mask, ptr)
+                    elif drop is not None:
+                        ptr, logp = pointer_pick_draw(logits, current_mask, drop)
+                    else:
+                        ptr, logp = pointer_pick(logits, current_mask)
+                carry['last_hh'] = hh
+                logps.append(logp)
+                if record:
+                    rec_steps.append(dict(logits=logits.clone(), last_hh=hh.clone()))
+                return ptr
+
+            out = _run_rolling_steppers(rw, policy, self.container_width, self.container_height, self.reward_type,
+                                        self.heightmap_type, self.packing_strategy, False, steppers, check, expand_dynamic=False)
+            self.__dict__['last_stepper'], self.__dict__['last_env'] = last, out['env']
+            self.__dict__['last_record'] = rec_steps
+            return out['tour_idx'], torch.stack(logps, dim=1), out['nodes'], out['reward']
 
 
 class _EngineRow(object):
