@@ -1097,6 +1097,48 @@ int tap_roller_begin(tap_roller *r, const int32_t *blocks, const uint64_t *rel, 
 int tap_roller_step(tap_roller *r, const int64_t *ptr, void *stream);
 int tap_roller_steps_done(const tap_roller *r);
 
+/* ---- the tail of a training iteration (train.hip) -------------------------------- */
+
+/* trainer.py:216-225 in ONE launch.  reward (B,), critic_est (B,), tour_logp (B, n) float32 ->
+ *   adv_out (B,)        reward - critic_est
+ *   seed_logp_out (B, n) adv / B in every column: the gradient of mean(adv.detach() * tour_logp.sum(1))
+ *   seed_est_out (B,)   -2 adv / B: the gradient of mean(adv^2) with respect to critic_est
+ *   stats_out (5,)      actor_loss, critic_loss, mean reward, mean critic_est, number of flagged envs
+ * An env whose reward is not finite (a flagged container under check='nan') has adv = 0 and zero seeds, is left out
+ * of the four sums and is counted; the divisor stays B.  The sums are float64 in a fixed order (one thread per env,
+ * 256 envs per workgroup, the workgroups' partials added in ascending order by the one that finishes last): the
+ * same bytes on every call.  scratch: tap_reinforce_losses_scratch(B) bytes, 8-byte aligned, ZEROED by the caller
+ * once and then left to the launches (its first word is their ticket).  B = 0 is TAP_OK and launches nothing. */
+size_t tap_reinforce_losses_scratch(int B);
+int tap_reinforce_losses(tap_ctx *ctx, const float *reward, const float *critic_est, const float *tour_logp, int B, int n,
+                         float *adv_out, float *seed_logp_out, float *seed_est_out, float *stats_out, void *scratch,
+                         size_t scratch_bytes, void *stream);
+
+/* clip_grad_norm_ + Adam.step() for every parameter of several optimizers in two launches.  The caller cuts the
+ * float32 parameters into chunks, one table entry each, the chunks of a group (one optimizer) contiguous: */
+typedef struct tap_adam_chunk {
+    float *param, *grad, *exp_avg, *exp_avg_sq; /* `count` elements each, 4-byte aligned; 16-byte accesses where all four are 16-byte aligned */
+    int32_t count;                              /* >= 1 */
+    int32_t group;
+} tap_adam_chunk;
+/* All arrays live on the device:
+ *   ranges (groups, 2) int32    a group's first chunk and its number of chunks
+ *   hyper (groups, 5) float64   lr, beta1, beta2, eps, max_norm -- read at every launch, so a new lr needs no re-capture
+ *   steps (groups, 2) int64     the step counter, and the snapshot of it that tap_clip_adam_norm takes
+ *   partials (chunks,) float64  tap_clip_adam_norm's output: the sum of squares of a chunk's gradient
+ *   norms_out (groups,) float32 the gradient norm before clipping
+ *   skipped (groups,) int32     goes up by one when a group's step was skipped
+ * tap_clip_adam_apply adds a group's partials in ascending order, then coef = min(1, max_norm / (norm + 1e-6)) and
+ * torch.optim.Adam's step (no weight decay, no amsgrad) on the clipped gradient, bias corrections from the counter,
+ * which it advances; zero_grads != 0 zeroes the gradients.  A norm that is not finite skips that group: parameters,
+ * moments and counter stay, the gradients are zeroed (zero_grads) and skipped goes up.  The two calls belong
+ * together, in this order, on one stream.  chunks = 0 is TAP_OK and launches nothing. */
+int tap_clip_adam_norm(tap_ctx *ctx, const tap_adam_chunk *table, int chunks, int groups, const int32_t *ranges,
+                       int64_t *steps, double *partials, void *stream);
+int tap_clip_adam_apply(tap_ctx *ctx, const tap_adam_chunk *table, int chunks, int groups, const int32_t *ranges,
+                        const double *hyper, int64_t *steps, const double *partials, float *norms_out, int32_t *skipped,
+                        int zero_grads, void *stream);
+
 /* ---- measurement support ------------------------------------------------------------------ */
 
 /* Bandwidth calibration in the hot kernels' own access shape (16 bytes per lane, a wavefront covers 1 KiB): SURVEY

@@ -156,6 +156,10 @@ _PROTOS = {
     "tap_transition_bits": (_i, [_vp, C.POINTER(EnvDesc), _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp,
                                  _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "tap_transition_launches": (_i, [_vp, C.POINTER(EnvDesc), _i, _i, _i, _i]),
+    "tap_reinforce_losses_scratch": (_sz, [_i]),
+    "tap_reinforce_losses": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "tap_clip_adam_norm": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "tap_clip_adam_apply": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "tap_bw_probe": (_i, [_vp, _i, _vp, _vp, _sz, _vp]),
     "tap_stepper_create": (_i, [_vp, C.POINTER(EnvDesc), _vp, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(_vp)]),
     "tap_stepper_destroy": (None, [_vp]),
