@@ -104,7 +104,7 @@ const char *tap_last_error(const tap_ctx *ctx);
  * hipGraph counts once, at capture.  tap_variant_hits writes up to `cap` rows of 8 ints (the key, then the count) and
  * returns the number of rows the record holds (TAP_E_INVALID if a key found no slot since the last reset);
  * tap_variant_hits_reset empties it. */
-/* The whole-episode and rolling kernels count on the same record, under kinds 16 .. 31 (tap_common.h: TapHitKind; 25: trial.hip, 26: policy.hip, 27: encode.hip, 28: pointer.hip, 29: decoder.hip, 30: heightmap.hip, 31: critic.hip), after
+/* The whole-episode and rolling kernels count on the same record, under kinds 16 .. 32 (tap_common.h: TapHitKind; 25: trial.hip, 26: policy.hip, 27: encode.hip, 28: pointer.hip, 29: decoder.hip, 30: heightmap.hip, 31: critic.hip, 32: pack_rnn.hip), after
  * the stream-wave kinds 0 .. 6.  Their keys, fields (kind, D, G, nc, mode, extra, wt):
  *   16 k_episode<D, G, SOFT>                      (16, D, G, SOFT, 0, 0, 0)
  *   17 k_episode_macs2<G, WIDE>                   (17, 2, G, WIDE, 0, 0, 0)
@@ -132,6 +132,7 @@ const char *tap_last_error(const tap_ctx *ctx);
  *   30 k_decoder_step_hm                          (30, C, NP, CHUNKS, H, 0, 0)   C height-map planes, NP = ceil(W / 4) ceil(L / 4) positions read
  *   31 k_critic_value<HPL>                        (31, RES, HPL, PLANES, MALL, 0, 0) HPL = H / 64 hidden rows per lane, RES 1 = U resident in LDS (0: recomputed per block), MALL 1 = all of M staged (0: a 64-row slab at a time)
  *      k_critic_value_bw<HPL> + _bw_reduce        (31, RES, HPL, PLANES, MALL, 1, 0) RES 1 = dU accumulated in LDS (0: in dU_out) (one count per call)
+ *   32 k_pack_rnn_forward<KIND>                   (32, 2, TE, KIND, CHUNKS, 0, 0) TE = 16 envs per workgroup, KIND 0 = G, 1 = LG (TAP_PACK_*), CHUNKS = D / 64 = 4 | 6
  * wt is the launch's RollArgs::wt (the window's fp32 stores; the init kernels store none), 0 for the episode kernels. */
 int tap_variant_hits(tap_ctx *ctx, int32_t *out, int cap);
 int tap_variant_hits_reset(tap_ctx *ctx);
@@ -989,6 +990,64 @@ int tap_decoder_step_hm_dropout(tap_ctx *ctx, const float *xs, int Ks, const flo
 int tap_decoder_step_dropout_backward(tap_ctx *ctx, int B, int Hd, const float *gates, const float *h, const float *g_h,
                                       const float *g_r, const int64_t *keep, float s_rnn, float s_hh, float *dgi_out,
                                       float *dghn_out, float *dh_carry_out, void *stream);
+
+/* ---- the global pack-net's forward, one launch ------------------------------------------------ */
+/* PackRNN.forward (pack_net/LG_RL.py:603-675) in its eval form for all B envs of a TAP_AT_NET descriptor: the encoder GRU
+ * over the T columns of blocks (B, 2, T), then blocks_num decoder steps, each height-map input -> GRU cell -> fc ->
+ * softmax -> first maximum -> PackEngine.step (tap_env_step_engine) -- the height-map never leaves the workgroup.
+ * Notation: Hb = block_hidden_size, Hh = height_hidden_size, D = the decoder GRU's hidden size (Hb + Hh for G, 2 Hb + Hh for
+ * LG), W' = W - 1 for the diff form, W otherwise.
+ * Folds (the caller's, in torch, once per forward; they add no parameter):
+ *   Pe (3 Hb, 2) = encoder.weight_ih_l0 . block_conv.weight      ce = encoder.bias_ih_l0 + encoder.weight_ih_l0 . block_conv.bias
+ *   the columns of decoder.weight_ih_l0 are [encoder_last_hh (Hb) | block_vec (Hb, LG only) | height_vec (Hh)]:
+ *   Pd_e (3 D, Hb) = the first Hb columns      Pd_b (3 D, 2; LG only) = block columns . block_conv.weight
+ *   Pd_h (3 D, W') = height columns . height_map_conv.weight
+ *   cd = bias_ih_l0 + height columns . height_map_conv.bias (+ block columns . block_conv.bias for LG)
+ * Per env, fp32 throughout; every sum is ONE chain of fmaf in ascending term order, as in tap_decoder_step's contract;
+ * sigmoid(x) = 1 / (1 + expf(-x)); the products r gh_n, (1 - z) n and z h are rounded before they are added.
+ *   1. Encoder: h_e = 0; for t = 0 .. T - 1 (all T columns, not blocks_num; LG_RL.py:603-620): gi from ce over
+ *      (blocks[b, 0, t], blocks[b, 1, t]), the raw floats; gh from enc_b_hh over the Hb terms of h_e (exactly enc_b_hh at
+ *      t = 0); the GRU cell.  enc = h_e after T steps (dropout is the identity: the eval form only).
+ *   2. u = the chain from cd over the Hb terms of enc with Pd_e: the constant part of the decoder's input, computed once
+ *      and kept per env in the LDS.
+ *   3. Decoder, i = 0 .. blocks_num - 1: x = the container's height-map in the form `form` -- full, zero (minus its
+ *      minimum) or diff (hm[c + 1] - hm[c], W - 1 values); zeros at step 0 and after a wrap.  gi = the chain CONTINUED from
+ *      u, for LG first over (blocks[b, 0, i], blocks[b, 1, i]) with Pd_b, then over x_0 .. x_{W' - 1} with Pd_h (the full
+ *      chain's order); gh from dec_b_hh over the D terms of h_d (exactly dec_b_hh at i = 0); the cell gives h_d'.
+ *      a = relu(chain from fc0_b over the D terms of h_d'); l_c = the chain from fc2_b[c] over the D terms of a, c < W;
+ *      m = max l; column = the first c with l_c == m; s = sum_c exp((double)(l_c - m)), ascending, fp64;
+ *      logp_out[b, i] = (float)(-log(s)).  Then the engine step at that column, tap_env_step_engine's rules exactly: clamp
+ *      to W - w, z = max over the footprint, stability on the support row before the fill, empty = sum hm - valid, error
+ *      bits 1 and 4, a start from empty at i % max_blocks == 0, the clear after (i + 1) % max_blocks == 0 (max_blocks == 0
+ *      never wraps), the block is blocks[b, :, i] truncated, the tape is indexed by i, the 4th counter is i + 1, the error
+ *      word restarts at step 0.  reward_out[b] = (C + P + S) / 3 in fp64, stored as f32, of the LAST step only, before a
+ *      clear.
+ * After the launch the state blob, tape, stability bytes and error words hold what blocks_num calls of tap_env_step_engine
+ * with these columns leave, and reward_out what the last of them writes: every integer and the reward agree bit for bit.
+ * feature_out (B, W') f32 or NULL: the next input.  No atomics, no cross-env sums: two calls give the same bytes, and an
+ * env's bytes do not depend on the batch or the tile around it.  One launch, no allocation, no host read, no stream
+ * synchronisation (capturable in a hipGraph).  k_pack_rnn_forward<KIND> (pack_rnn.hip): tap_decoder_step's geometry with
+ * the loops over t and i inside the launch.  Launch record key (32, 2, TE, KIND, D / 64, 0, 0): TE = 16 envs per workgroup,
+ * KIND a TAP_PACK_*.
+ * Shapes: Hb = Hh = 128; kind G or LG; 2 <= W <= 64; the three forms; 1 <= blocks_num <= T <= the descriptor's tape;
+ * max_blocks >= 0; anything else -> TAP_E_UNSUPPORTED.  Checks, in tap_decoder_step's order: a null descriptor or weights,
+ * a descriptor that is not TAP_AT_NET, blocks_num outside [1, T] or max_blocks < 0 -> TAP_E_INVALID; B == 0 -> TAP_OK; a
+ * null required buffer (Pd_b is required for LG only) or weights for another W -> TAP_E_INVALID; a shape outside the list
+ * -> TAP_E_UNSUPPORTED; a state blob or a weight buffer that is not 16-byte aligned (the weight blocks are read 16 bytes at a
+ * time), or another buffer that is not 4-byte aligned -> TAP_E_INVALID. */
+enum { TAP_PACK_G = 0, TAP_PACK_LG = 1 };
+typedef struct tap_pack_rnn_weights {
+    int32_t kind;       /* TAP_PACK_* */
+    int32_t Hb, Hh, W;
+    int32_t form;       /* TAP_FEAT_*: the net's heightmap_type */
+    int32_t reserved;
+    const float *Pe, *ce, *enc_w_hh, *enc_b_hh;                 /* (3 Hb, 2), (3 Hb,), (3 Hb, Hb), (3 Hb,) */
+    const float *Pd_e, *Pd_b, *Pd_h, *cd, *dec_w_hh, *dec_b_hh; /* (3 D, Hb), (3 D, 2) | NULL, (3 D, W'), (3 D,), (3 D, D), (3 D,) */
+    const float *fc0_w, *fc0_b, *fc2_w, *fc2_b;                 /* (D, D), (D,), (W, D), (W,) */
+} tap_pack_rnn_weights;
+int tap_pack_rnn_forward(tap_ctx *ctx, const tap_env_desc *d, void *state, const float *blocks, int T, int blocks_num,
+                         int max_blocks, const tap_pack_rnn_weights *w, float *logp_out, float *reward_out,
+                         float *feature_out /* or NULL */, void *stream);
 
 /* ---- the step object of a decoding loop ----------------------------------------------------- */
 /* DRL.forward's loop (model.py:342-496) runs its policy network between the environment steps, so the loop is

@@ -33,6 +33,8 @@ TAP_HIT_POINTER = 28                                           # pointer.hip: k_
 TAP_HIT_DECODER = 29                                           # decoder.hip: k_decoder_step / k_decoder_step_bw
 TAP_HIT_HEIGHTMAP = 30                                         # heightmap.hip: k_decoder_step_hm
 TAP_HIT_CRITIC = 31                                            # critic.hip: k_critic_value<HPL> / _bw<HPL> + _bw_reduce
+TAP_HIT_PACK_RNN = 32                                          # pack_rnn.hip: k_pack_rnn_forward<KIND> (key: 32, 2, TE, KIND, D / 64, 0, 0)
+TAP_PACK_G, TAP_PACK_LG = 0, 1
 TAP_P_GREEDY = 1
 TAP_PICK_GREEDY, TAP_PICK_DRAW = 1, 2                           # tap_pointer_pick_static's form (the launch record's second field)
 
@@ -67,6 +69,15 @@ class RollerBuffers(C.Structure):
 class EnvDesc(C.Structure):
     _fields_ = [(k, C.c_int32) for k in
                 ("B", "D", "W", "L", "H", "n_max", "strategy", "flags", "ratio_mode", "feature")]
+
+
+PACK_RNN_WEIGHTS = ("Pe", "ce", "enc_w_hh", "enc_b_hh", "Pd_e", "Pd_b", "Pd_h", "cd", "dec_w_hh", "dec_b_hh",
+                    "fc0_w", "fc0_b", "fc2_w", "fc2_b")
+
+
+class PackRnnWeights(C.Structure):
+    """tapenv.h: tap_pack_rnn_weights"""
+    _fields_ = [(k, C.c_int32) for k in ("kind", "Hb", "Hh", "W", "form", "reserved")] + [(k, _vp_t) for k in PACK_RNN_WEIGHTS]
 
 
 _lib = None
@@ -121,6 +132,7 @@ _PROTOS = {
     "tap_decoder_step_dropout": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i] + [_vp] * 6 + [_u32] * 4 + [_f, _f] + [_vp] * 6),
     "tap_decoder_step_hm_dropout": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _i] + [_vp] * 12 + [_u32] * 4 + [_f, _f] + [_vp] * 7),
     "tap_decoder_step_dropout_backward": (_i, [_vp, _i, _i] + [_vp] * 5 + [_f, _f] + [_vp] * 4),
+    "tap_pack_rnn_forward": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _i, _i, _i, C.POINTER(PackRnnWeights), _vp, _vp, _vp, _vp]),
     "tap_env_feature": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp]),
     "tap_env_ratio": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp, _vp, _vp]),
     "tap_env_export": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -1658,6 +1658,83 @@ def _run_episode_pack(static, dynamic, policy, pack_policy, container_width, con
     return out
 
 
+# ---- the global pack-net's forward in one launch (tapenv.h: tap_pack_rnn_forward has the contract) ----------------------
+def pack_rnn_forward_supported(Hb, Hh, W, kind='G'):
+    """whether tap_pack_rnn_forward has a kernel for this net: Hb = Hh = 128, G or LG, 2 <= W <= 64"""
+    return int(Hb) == 128 and int(Hh) == 128 and kind in ('G', 'LG') and 2 <= int(W) <= 64
+
+
+def _pack_rnn_blocks(fold, engine, blocks, blocks_num):
+    B, n = int(engine.batch_size), int(blocks_num)
+    if blocks.dim() != 3 or int(blocks.shape[0]) != B or int(blocks.shape[1]) != 2:
+        raise ValueError("blocks must be (%d, 2, T), got %s" % (B, tuple(blocks.shape)))
+    T = int(blocks.shape[2])
+    if not 1 <= n <= T or T > int(engine.T):
+        raise ValueError("blocks_num %d of %d blocks on a tape of %d" % (n, T, engine.T))
+    if engine.heightmap_type != fold.heightmap_type or int(engine.W) != fold.W:
+        raise ValueError("the engine is %d columns / %r, the net was folded for %d / %r"
+                         % (engine.W, engine.heightmap_type, fold.W, fold.heightmap_type))
+    return B, n, T
+
+
+def pack_rnn_forward(fold, engine, blocks, blocks_num, want_input=True):
+    """PackRNN.forward's eval form in ONE launch (tap_pack_rnn_forward): ``fold`` a ``tools.PackFold`` of float32 tensors on
+    the GPU (``tools.PackRNN.fold``), ``engine`` an ``env.PackEngines``, ``blocks`` (B, 2, T) float32 on its device.
+    -> hit_porb_log (B, blocks_num) float32 and the net's next input (B, W', 1) (None without ``want_input``); the engine's
+    blob, tape, error words and ``reward`` hold what ``blocks_num`` ``engine.step`` calls at the picked columns leave.
+    No allocation beyond the two outputs, no host read: capturable."""
+    from .env import PackEngines
+    if not isinstance(engine, PackEngines):
+        raise TypeError("the fused forward steps an env.PackEngines, not %s" % type(engine).__name__)
+    B, n, T = _pack_rnn_blocks(fold, engine, blocks, blocks_num)
+    if not pack_rnn_forward_supported(fold.Hb, fold.Hh, fold.W, fold.kind):
+        raise _lib.TapError(_lib.TAP_E_UNSUPPORTED, "no pack-net kernel for Hb %d, Hh %d, W %d, kind %r" % (fold.Hb, fold.Hh, fold.W, fold.kind))
+    blocks = engine._blocks(blocks.detach())
+    w = fold.weights(engine.device)
+    logp = torch.empty(B, n, dtype=torch.float32, device=engine.device)
+    feat = engine.env._new_feature() if want_input else None
+    engine.env._call(_lib.lib().tap_pack_rnn_forward, _lib.ptr(engine.env._state), _lib.ptr(blocks), T, n, engine.max_blocks_num,
+                     _lib.C.byref(w), _lib.ptr(logp), _lib.ptr(engine.reward), _lib.ptr(feat))
+    engine.last_input = feat
+    return logp, feat
+
+
+def pack_rnn_forward_torch(fold, engine, blocks, blocks_num, want_input=True):
+    """``pack_rnn_forward``'s contract in torch ops, in ``blocks``' dtype (the fold's): the folded algebra, the chains as
+    matmuls, ``engine`` anything with PackEngines' surface.  In float64 it is the model the launch is tested against."""
+    B, n, T = _pack_rnn_blocks(fold, engine, blocks, blocks_num)
+    f, dt, dev = fold, blocks.dtype, blocks.device
+    blocks = blocks.detach()
+
+    def cell(gi, gh, h, H):
+        r = torch.sigmoid(gi[:, :H] + gh[:, :H])
+        z = torch.sigmoid(gi[:, H:2 * H] + gh[:, H:2 * H])
+        nn_ = torch.tanh(gi[:, 2 * H:] + r * gh[:, 2 * H:])
+        return (1 - z) * nn_ + z * h
+    h = torch.zeros(B, f.Hb, dtype=dt, device=dev)
+    for t in range(T):                                                       # all T columns (LG_RL.py:603-620)
+        h = cell(blocks[:, :, t] @ f.Pe.t() + f.ce, h @ f.enc_w_hh.t() + f.enc_b_hh, h, f.Hb)
+    u = h @ f.Pd_e.t() + f.cd
+    hd = torch.zeros(B, f.D, dtype=dt, device=dev)
+    x = torch.zeros(B, f.Wp, dtype=dt, device=dev)
+    logps, feat = [], None
+    for i in range(n):
+        gi = u
+        if f.kind == 'LG':
+            gi = gi + blocks[:, :, i] @ f.Pd_b.t()
+        gi = gi + x @ f.Pd_h.t()
+        hd = cell(gi, hd @ f.dec_w_hh.t() + f.dec_b_hh, hd, f.D)
+        logit = torch.relu(hd @ f.fc0_w.t() + f.fc0_b) @ f.fc2_w.t() + f.fc2_b
+        m, col = logit.max(1)                                                # the first maximum (LG_RL.py:659)
+        s = torch.exp((logit - m.unsqueeze(1)).double()).sum(1)
+        logps.append((-torch.log(s)).to(dt).unsqueeze(1))
+        last = i == n - 1
+        feat = engine.step(i, blocks, col, want_reward=last, want_input=want_input or not last)
+        if feat is not None:
+            x = feat.to(dt)[:, :, 0]
+    return torch.cat(logps, dim=1), feat
+
+
 def _run_episode_rnn(static, dynamic, policy, net, container_width, reward_type, heightmap_type, input_type, allow_rot,
                      record, steps, bits=False, check='nan'):
     """DRL_RNN's decoding loop (model.py:749-852) minus its pointer network.  Per outer step t: ``policy`` -> ptr, the

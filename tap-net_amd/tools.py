@@ -1063,6 +1063,33 @@ class _EngineRows(object):
         return _EngineRow(self, b % len(self))
 
 
+class PackFold(object):
+    """What ``PackRNN.fold`` returns, the parameters of ``rollout.pack_rnn_forward`` / ``_torch`` (tapenv.h:
+    tap_pack_rnn_forward has the algebra): the two 1x1 convolutions folded into the GRUs' input weights -- ``Pe`` (3 Hb, 2),
+    ``ce``; ``Pd_e`` (3 D, Hb), ``Pd_b`` (3 D, 2; LG only, else None), ``Pd_h`` (3 D, W'), ``cd`` --, both GRUs' hidden
+    weights and the fc head as they are; ``kind`` 'G' | 'LG', ``Hb``, ``Hh``, ``D``, ``W``, ``Wp`` = W', ``heightmap_type``.
+    Detached and contiguous, in the net's dtype on the net's device."""
+    __slots__ = ("kind", "Hb", "Hh", "D", "W", "Wp", "heightmap_type") + _lib.PACK_RNN_WEIGHTS + ("_struct",)
+
+    def weights(self, device):
+        """the launch's tap_pack_rnn_weights (built once; the record keeps the tensors it points to alive)"""
+        if getattr(self, "_struct", None) is None:
+            w = _lib.PackRnnWeights()
+            w.kind = _lib.TAP_PACK_LG if self.kind == 'LG' else _lib.TAP_PACK_G
+            w.Hb, w.Hh, w.W, w.form = self.Hb, self.Hh, self.W, _lib.PNET_FORMS[self.heightmap_type]
+            for k in _lib.PACK_RNN_WEIGHTS:
+                t = getattr(self, k)
+                if t is not None and (t.dtype != torch.float32 or t.device != torch.device(device) or not t.is_contiguous()):
+                    raise _lib.TapError(_lib.TAP_E_INVALID, "the fused pack-net forward takes contiguous float32 weights on %s, %s is %s on %s"
+                                        % (device, k, t.dtype, t.device))
+                if t is not None and t.data_ptr() % 16:                    # a view at an odd offset: the launch reads 16 bytes at a time
+                    t = t.clone()
+                    setattr(self, k, t)
+                setattr(w, k, None if t is None else t.data_ptr())
+            self._struct = w
+        return self._struct
+
+
 class PackRNN(nn.Module):
     """The global pack-net (pack_net/LG_RL.py: PackRNN, LG_RL.py:562-675): 'G' (reward type C+P+S-G-soft) or 'LG'
     (C+P+S-LG-soft), what the reference's DRL_RNN (model.py:749-852) and tools.calc_positions_LG_net run.  Stock PyTorch
@@ -1074,11 +1101,19 @@ class PackRNN(nn.Module):
 
     forward(blocks (B, 2, T), blocks_num) -> positions (B, T, 2) int32 (x after the clamp, z; zero beyond blocks_num),
     hit_porb_log (B, blocks_num), -reward (B,) float32 of the last inner step.  Afterwards ``engines[b].get_heightap``
-    answers like the reference's engines (one batched read per forward)."""
+    answers like the reference's engines (one batched read per forward).
+
+    ``fused`` (keyword only, also an attribute; default False): the whole forward in ONE launch
+    (``rollout.pack_rnn_forward``; tapenv.h: tap_pack_rnn_forward) when the module is in eval(), its output needs no
+    gradient (grad is disabled, or neither the blocks nor a parameter require one), the blocks are float32 on the GPU,
+    the engine is an env.PackEngines and the shape has a kernel (Hb = Hh = 128, 2 <= W <= 64).  In every other case the
+    torch path below runs."""
 
     def __init__(self, block_input_size, block_hidden_size, height_input_size, height_hidden_size, container_width,
-                 container_height, heightmap_type, max_blocks_num=10, pack_net_type='LG', engine=None):
+                 container_height, heightmap_type, max_blocks_num=10, pack_net_type='LG', engine=None, *, fused=False):
         super(PackRNN, self).__init__()
+        self.fused = bool(fused)
+        self._fold = None
         if pack_net_type == 'LG':
             decoder_hidden_size = block_hidden_size + block_hidden_size + height_hidden_size    # local + global
         else:
@@ -1121,6 +1156,58 @@ class PackRNN(nn.Module):
                                            self.heightmap_type, self.max_blocks_num, dev)
         return self._engine
 
+    def fold(self):
+        """-> a ``PackFold``: block_conv folded into the encoder GRU's input weights, block_conv and height_map_conv into
+        the decoder GRU's (tapenv.h: tap_pack_rnn_forward), in torch, detached; no parameter is added and the state-dict
+        keys stay the reference's.  The record is kept until a parameter changes (its version, memory or dtype); one
+        computed under hipGraph capture is not kept."""
+        params = list(self.parameters())
+        key = tuple((p.data_ptr(), p._version, p.dtype) for p in params)
+        if self._fold is not None and self._fold[0] == key:
+            return self._fold[1]
+        with torch.no_grad():
+            Hb, Hh = int(self.block_conv.out_channels), int(self.height_map_conv.out_channels)
+            f = PackFold()
+            f.kind, f.Hb, f.Hh, f.W, f.heightmap_type = self.pack_net_type, Hb, Hh, int(self.container_width), self.heightmap_type
+            f.D, f.Wp = int(self.decoder.hidden_size), int(self.height_map_conv.in_channels)
+            bw, bb = self.block_conv.weight[:, :, 0], self.block_conv.bias
+            hw, hb = self.height_map_conv.weight[:, :, 0], self.height_map_conv.bias
+            we, wd = self.encoder.weight_ih_l0, self.decoder.weight_ih_l0
+            f.Pe, f.ce = we @ bw, self.encoder.bias_ih_l0 + we @ bb
+            f.Pd_e = wd[:, :Hb]
+            cd = self.decoder.bias_ih_l0 + wd[:, -Hh:] @ hb
+            f.Pd_b = None
+            if self.pack_net_type == 'LG':
+                f.Pd_b = wd[:, Hb:2 * Hb] @ bw
+                cd = cd + wd[:, Hb:2 * Hb] @ bb
+            f.Pd_h, f.cd = wd[:, -Hh:] @ hw, cd
+            f.enc_w_hh, f.enc_b_hh = self.encoder.weight_hh_l0, self.encoder.bias_hh_l0
+            f.dec_w_hh, f.dec_b_hh = self.decoder.weight_hh_l0, self.decoder.bias_hh_l0
+            f.fc0_w, f.fc0_b, f.fc2_w, f.fc2_b = self.fc[0].weight, self.fc[0].bias, self.fc[2].weight, self.fc[2].bias
+            for k in _lib.PACK_RNN_WEIGHTS:
+                t = getattr(f, k)
+                if t is not None:
+                    setattr(f, k, t.detach().contiguous())
+        if not (params and params[0].is_cuda and torch.cuda.is_current_stream_capturing()):
+            self._fold = (key, f)
+        return f
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state['_fold'] = None                   # a cache holding device addresses: a copy folds again
+        return state
+
+    def _takes_launch(self, blocks, engine):
+        """whether this forward is the one launch (the class docstring has the conditions)"""
+        if not self.fused or self.training or not blocks.is_cuda or blocks.dtype != torch.float32:
+            return False
+        if torch.is_grad_enabled() and (blocks.requires_grad or any(p.requires_grad for p in self.parameters())):
+            return False
+        from .rollout import pack_rnn_forward_supported
+        return isinstance(engine, PackEngines) and self.encoder.weight_ih_l0.dtype == torch.float32 and \
+            pack_rnn_forward_supported(self.block_conv.out_channels, self.height_map_conv.out_channels,
+                                       self.container_width, self.pack_net_type)
+
     def forward(self, blocks, blocks_num):
         """blocks: batch_size x block-dim x blocks-num (LG_RL.py:603-675)"""
         batch_size = blocks.shape[0]
@@ -1130,13 +1217,22 @@ class PackRNN(nn.Module):
                 not any(c is engine for c in self.captured_engines):
             self.captured_engines.append(engine)            # the graph's launches write its blob: keep it alive
 
+        if self._takes_launch(blocks, engine):
+            from .rollout import pack_rnn_forward
+            hit_porb_log, _ = pack_rnn_forward(self.fold(), engine, blocks, blocks_num)
+            positions = engine.positions[:, :blocks.shape[-1]]
+            if blocks_num < positions.shape[1]:
+                positions[:, blocks_num:] = 0
+            self.engines = _EngineRows(engine)
+            return positions, hit_porb_log, -engine.reward
+
         block_vec = self.block_conv(blocks)
         encode_rnn_out, encoder_last_hh = self.encoder(block_vec.transpose(2, 1), None)
         encoder_last_hh = self.dropout(encoder_last_hh)
         encoder_last_hh = encoder_last_hh.squeeze(0).unsqueeze(-1)
 
         width = self.container_width - (1 if self.heightmap_type == 'diff' else 0)
-        height_map = torch.zeros(batch_size, width, 1, dtype=torch.float32, device=blocks.device)   # :627, :633-639
+        height_map = torch.zeros(batch_size, width, 1, dtype=blocks.dtype, device=blocks.device)    # :627, :633-639
         hit_porb_log = []
         last_hh = None
         for block_index in range(blocks_num):
@@ -1150,6 +1246,7 @@ class PackRNN(nn.Module):
             best = hit_map.max(1)                       # log(max) and the first argmax (:654, :659) in one op
             hit_porb_log.append(torch.log(best[0]).unsqueeze(1))
             height_map = engine.step(block_index, blocks.detach(), best[1], want_reward=block_index == blocks_num - 1)
+            height_map = height_map.to(blocks.dtype)        # the engine's is float32: net.double() is the float64 model
 
         positions = engine.positions[:, :blocks.shape[-1]]
         if blocks_num < positions.shape[1]:
@@ -1174,18 +1271,19 @@ _PACK_RNN_H = 4000
 _TAPE_MAX = 4096
 
 
-def load_pack_net(reward_type, container_width, device='cuda', container_height=None):
+def load_pack_net(reward_type, container_width, device='cuda', container_height=None, fused=False):
     """The network tools.calc_positions_net loads for ``reward_type``, in eval mode with the reference's checkpoint:
     DQN(W, True) for the SL / RL types, PackRNN(2, 128, W, 128, W, H, 'diff', pack_net_type='G' | 'LG') for the G / LG
     types (tools.py:3488-3500).  The LG checkpoint is not shipped: FileNotFoundError, as the reference's torch.load.
     ``device=None`` leaves the network on the host.  A host PackRNN fed host blocks then needs a host engine
-    injected (``net.engine_factory``): the default engine, env.PackEngines, has no CPU path and raises TapError."""
+    injected (``net.engine_factory``): the default engine, env.PackEngines, has no CPU path and raises TapError.
+    ``fused`` is PackRNN's (the one-launch forward; the SL / RL nets have none and ignore it)."""
     if reward_type not in PACK_NET_CHECKPOINTS:
         raise NotImplementedError("%s has no pack-net (tools.calc_positions_net)" % reward_type)
     W = int(container_width)
     if reward_type in PACK_RNN_TYPES:
         H = _PACK_RNN_H if container_height is None else int(container_height)
-        net = PackRNN(2, 128, W, 128, W, H, 'diff', pack_net_type=PACK_RNN_TYPES[reward_type])
+        net = PackRNN(2, 128, W, 128, W, H, 'diff', pack_net_type=PACK_RNN_TYPES[reward_type], fused=fused)
     else:
         net = DQN(W, True)
     path = PACK_NET_CHECKPOINTS[reward_type]
