@@ -32,6 +32,7 @@
 // Launch record (tapenv.h: tap_variant_hits): (31, RESIDENT, HPL, PLANES, MALL, BACKWARD, 0).
 #include <algorithm>
 
+#include "tap_bitshadow.h"
 #include "tap_common.h"
 
 namespace {
@@ -49,7 +50,7 @@ struct CrGeom {
 inline CrGeom cr_geom(int B, int nR, int rows, int H, bool backward)
 {
     CrGeom g;
-    g.planes = rows > 64 ? 2 : 1;
+    g.planes = tap_bit_planes(rows);
     g.hpl = H / 64;
     g.mall = (H == 64 || (size_t)rows * (H + 1) * sizeof(float) <= CR_M_ALL) ? 1 : 0;
     // M (or a slab of it), s / p / ds per wavefront; the backward adds the wavefronts' dv
@@ -72,37 +73,6 @@ struct CrArgs {
     int B, nR, rows, S, n, planes, mall, resident, q0s;
 };
 
-__device__ __forceinline__ float cr_wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v = v + __shfl_xor(v, o);                // every lane ends with the same sum
-    return v;
-}
-__device__ __forceinline__ float cr_wave_max(float v)
-{
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-// what one lane of a wavefront wrote to its LDS is read by the others: LDS operations of a wavefront complete in order
-__device__ __forceinline__ void cr_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// M[h0 + hl][r] -> lw[r * (HC + 1) + hl] for HC hidden rows from h0: global reads in memory order, LDS writes at an odd
-// stride.  The caller's barriers stand before (the previous slab has been consumed) and after.
-__device__ __forceinline__ void cr_fill(const CrArgs &a, float *lw, int h0, int HC, int tid)
-{
-    const int rows = a.rows, MS = HC + 1;
-    for (int i = tid; i < HC * rows; i += TAP_BLOCK) {
-        const int hl = i / rows, r = i - hl * rows;
-        lw[r * MS + hl] = a.M[(size_t)h0 * rows + i];
-    }
-}
-
 // the lane's rows of the attention's segment: v, g, and G's S columns in registers (unused ones never read)
 template <int HPL>
 struct CrRows {
@@ -118,9 +88,8 @@ struct CrRows {
 #pragma unroll
             for (int i = 0; i < CR_MAXS; ++i) G0[h][i] = i < a.S ? a.G[(size_t)j * a.S + i] : 0.f;
         }
-        // bits at positions >= rows are ignored: masked off each plane's word
-        m0 = a.rows >= 64 ? ~0ull : (1ull << a.rows) - 1;
-        m1 = a.rows >= 128 ? ~0ull : a.rows > 64 ? (1ull << (a.rows - 64)) - 1 : 0ull;
+        m0 = tap_rows_mask0(a.rows);
+        m1 = tap_rows_mask1(a.rows);
     }
 
     // U[64 (h0 + i) + lane, c] of env b for i < R and every column c in ascending order, use(c, u) on each:
@@ -148,10 +117,11 @@ struct CrRows {
 #pragma unroll
             for (int i = 0; i < CR_MAXS; ++i)
                 if (i < S) xn[i] = xp[i * nR + cn];
-            const unsigned piece[4] = {(unsigned)w0, (unsigned)(w0 >> 32), (unsigned)w1, (unsigned)(w1 >> 32)};
             float u[R];
 #pragma unroll
             for (int i = 0; i < R; ++i) u[i] = gk[H0 + i];
+            // tap_add_set_rows' loop, written out: through the helper HPL = 4 takes 1 (forward) and 2 (backward) more VGPRs
+            const unsigned piece[4] = {(unsigned)w0, (unsigned)(w0 >> 32), (unsigned)w1, (unsigned)(w1 >> 32)};
 #pragma unroll
             for (int p = 0; p < 4; ++p) {                                  // ascending rows: plane 0 before plane 1
                 unsigned y = (unsigned)__builtin_amdgcn_readfirstlane((int)piece[p]);
@@ -222,7 +192,7 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_critic_value(CrArgs a)
         if (live) a.q[(size_t)b * n * H + h * 64 + lane] = qq[h];
     }
     if (a.mall) {
-        cr_fill(a, lw, 0, H, tid);
+        tap_fill_chunk(a.M, lw, 0, H, H, a.rows, tid);
         __syncthreads();
     }
     float xb[CR_MAXS];
@@ -234,7 +204,7 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_critic_value(CrArgs a)
                 float p = rw.vv[0] * tanhf(up[0] + qq[0]);
 #pragma unroll
                 for (int h = 1; h < HPL; ++h) p = p + rw.vv[h] * tanhf(up[h * 64] + qq[h]);
-                p = cr_wave_sum(p);
+                p = tap_wave_sum(p);
                 if (lane == 0) sl[c] = p;
             }
         } else if (a.mall) {
@@ -246,35 +216,35 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_critic_value(CrArgs a)
                 float p = rw.vv[0] * tanhf(u[0] + qq[0]);
 #pragma unroll
                 for (int h = 1; h < HPL; ++h) p = p + rw.vv[h] * tanhf(u[h] + qq[h]);
-                p = cr_wave_sum(p);
+                p = tap_wave_sum(p);
                 if (lane == 0) sl[c] = p;
             });
         } else {
 #pragma unroll
             for (int h = 0; h < HPL; ++h) {
                 __syncthreads();                                           // the previous slab has been consumed
-                cr_fill(a, lw, h * 64, 64, tid);
+                tap_fill_chunk(a.M, lw, h * 64, 64, 64, a.rows, tid);
                 __syncthreads();
                 auto use = [&](int c, float (&u)[1]) {
                     if (a.resident) Ul[c * US + h * 64 + lane] = u[0];
-                    const float p = cr_wave_sum(rw.vv[h] * tanhf(u[0] + qq[h]));
+                    const float p = tap_wave_sum(rw.vv[h] * tanhf(u[0] + qq[h]));
                     if (lane == 0) sl[c] = h == 0 ? p : sl[c] + p;
                 };
                 rw.sweep1(h, a, lw, MS, b, lane, use);
             }
         }
-        cr_wave_sync();
+        tap_wave_lds_sync();
         // p_i = softmax over ALL nR columns, lanes along the columns
         float m = -INFINITY;
         for (int c = lane; c < nR; c += 64) m = fmaxf(m, sl[c]);
-        m = cr_wave_max(m);
+        m = tap_wave_max(m);
         float zs = 0.f;
         for (int c = lane; c < nR; c += 64) {
             const float e = expf(sl[c] - m);
             sl[c] = e;
             zs = zs + e;
         }
-        zs = cr_wave_sum(zs);
+        zs = tap_wave_sum(zs);
         // xbar_i[k] = sum_c p_i[c] x[k, c]: a lane's own columns in order, then the butterfly
         float part[CR_MAXS];
 #pragma unroll
@@ -290,11 +260,11 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_critic_value(CrArgs a)
         for (int k = 0; k < CR_MAXS; ++k) {
             xb[k] = 0.f;
             if (k < S) {
-                xb[k] = cr_wave_sum(part[k]);
+                xb[k] = tap_wave_sum(part[k]);
                 if (live && lane == 0) a.xbar[((size_t)b * n + i) * S + k] = xb[k];
             }
         }
-        cr_wave_sync();                                                    // sl has been consumed
+        tap_wave_lds_sync();                                                    // sl has been consumed
         if (i + 1 < n) {
             cr_affine<HPL>(a, 1, xb, lane, qq);
             if (live) {
@@ -309,7 +279,7 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_critic_value(CrArgs a)
     float t = a.w2[lane] * fmaxf(zz[0], 0.f);
 #pragma unroll
     for (int h = 1; h < HPL; ++h) t = t + a.w2[h * 64 + lane] * fmaxf(zz[h], 0.f);
-    t = cr_wave_sum(t);
+    t = tap_wave_sum(t);
     if (live) {
 #pragma unroll
         for (int h = 0; h < HPL; ++h) a.z[(size_t)b * H + h * 64 + lane] = zz[h];
@@ -342,7 +312,7 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_critic_value_bw(CrArgs a)
         dv[h] = 0.f;
     }
     if (a.mall) {
-        cr_fill(a, lw, 0, H, tid);
+        tap_fill_chunk(a.M, lw, 0, H, H, a.rows, tid);
         __syncthreads();
     }
     for (int i = n - 1; i >= 0; --i) {
@@ -357,7 +327,7 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_critic_value_bw(CrArgs a)
                 float t = a.G[(size_t)(seg * H + lane) * S + k] * dd[0];
 #pragma unroll
                 for (int h = 1; h < HPL; ++h) t = t + a.G[(size_t)(seg * H + h * 64 + lane) * S + k] * dd[h];
-                dx[k] = cr_wave_sum(t);
+                dx[k] = tap_wave_sum(t);
             }
         }
         // dp[c] = sum_k dxbar[k] x[k, c]; ds = p (dp - sum_c p dp) -> sl[c], lanes along the columns
@@ -370,13 +340,13 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_critic_value_bw(CrArgs a)
             sl[c] = dp;
             dot = dot + pp[c] * dp;
         }
-        dot = cr_wave_sum(dot);
+        dot = tap_wave_sum(dot);
         for (int c = lane; c < nR; c += 64) {
             const float ds = pp[c] * (sl[c] - dot);
             sl[c] = ds;
             if (!a.resident && live) a.dsg[((size_t)b * n + i) * nR + c] = ds;  // the second pass reads it
         }
-        cr_wave_sync();
+        tap_wave_lds_sync();
         // the sweep: th = tanh(U + q_i); dv += ds th; dA = ds v (1 - th^2) -> dU; dq_i[j] = sum_c dA[j, c]
         float qq[HPL], dq[HPL];
 #pragma unroll
@@ -407,7 +377,7 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_critic_value_bw(CrArgs a)
 #pragma unroll
             for (int h = 0; h < HPL; ++h) {
                 __syncthreads();                                           // the previous slab has been consumed
-                cr_fill(a, lw, h * 64, 64, tid);
+                tap_fill_chunk(a.M, lw, h * 64, 64, 64, a.rows, tid);
                 __syncthreads();
                 auto use = [&](int c, float (&u)[1]) {
                     const float ds = sl[c];
@@ -425,12 +395,12 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_critic_value_bw(CrArgs a)
             if (live) a.dq[((size_t)b * n + i) * H + h * 64 + lane] = dq[h];
             dd[h] = dq[h];
         }
-        cr_wave_sync();                                                    // sl has been consumed
+        tap_wave_lds_sync();                                                    // sl has been consumed
     }
 #pragma unroll
     for (int h = 0; h < HPL; ++h) dvl[wave * H + h * 64 + lane] = live ? dv[h] : 0.f;
     if (a.resident) {
-        cr_wave_sync();
+        tap_wave_lds_sync();
         if (live) {
             // the env's dU, Ul[c * US + j], to dU_out[j * nR + c] as float4s: consecutive lanes consecutive 16-byte pieces
             const int q4 = nR >> 2;
@@ -479,7 +449,7 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_critic_value_bw(CrArgs a)
 #pragma unroll
             for (int h = 0; h < HPL; ++h) {
                 __syncthreads();                                           // the previous slab has been consumed
-                cr_fill(a, lw, h * 64, 64, tid);
+                tap_fill_chunk(a.M, lw, h * 64, 64, 64, a.rows, tid);
                 __syncthreads();
                 float4 acc;
                 rw.sweep1(h, a, lw, MS, b, lane, [&](int c, float (&u)[1]) { col(c, h, u[0], acc); });
@@ -496,7 +466,8 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_critic_value_bw(CrArgs a)
     }
 }
 
-// dv[j] = part[0][j] + part[1][j] + ...: workgroup order, the same bytes every call
+// dv[j] = part[0][j] + part[1][j] + ...: workgroup order, the same bytes every call (pointer.hip's reduce with one output;
+// one kernel for both was tried and left: DESIGN 7f)
 __global__ void __launch_bounds__(TAP_BLOCK) k_critic_value_bw_reduce(const float *part, int blocks, int H, float *dv)
 {
     const int i = (int)blockIdx.x * TAP_BLOCK + (int)threadIdx.x;
@@ -510,8 +481,8 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_critic_value_bw_reduce(const floa
     dv[i] = s;
 }
 
-// the checks of both entries in tap_pointer_scores' order: dimensions, then the empty batch, then the caller's null
-// check, then the shapes without a kernel
+// the checks of both entries in the order of pointer.hip's ptr_check: dimensions, then the empty batch, then the caller's
+// null check, then the shapes without a kernel
 int cr_check_dims(tap_ctx *ctx, const char *what, int B, int nR, int rows, int H, int S, int n)
 {
     if (B < 0 || nR < 1 || rows < 1 || H < 1 || S < 1 || n < 1)
@@ -520,7 +491,7 @@ int cr_check_dims(tap_ctx *ctx, const char *what, int B, int nR, int rows, int H
 }
 inline bool cr_shape_ok(int nR, int rows, int H, int S, int n)
 {
-    return tap_bits_words(rows, nR) > 0 && (H == 64 || H == 128 || H == 256) && S <= CR_MAXS && n <= CR_MAXN;
+    return tap_has_bit_shadow(rows, nR) && (H == 64 || H == 128 || H == 256) && S <= CR_MAXS && n <= CR_MAXN;
 }
 int cr_check_shape(tap_ctx *ctx, const char *what, int nR, int rows, int H, int S, int n, int q0_stride)
 {
@@ -530,7 +501,6 @@ int cr_check_shape(tap_ctx *ctx, const char *what, int nR, int rows, int H, int 
                         "nR <= 256; H 64, 128 or 256; S <= 8; blocks <= 8; q0 stride 0 or H)", what, rows, nR, H, S, n, q0_stride);
     return TAP_OK;
 }
-inline bool cr_misaligned(const void *p, unsigned to) { return ((uintptr_t)p & (to - 1)) != 0; }
 
 template <class K1, class K2, class K4>
 inline void cr_launch(int hpl, K1 k1, K2 k2, K4 k4, const CrGeom &geo, hipStream_t st, const CrArgs &a)
@@ -553,10 +523,8 @@ extern "C" int tap_critic_value(tap_ctx *ctx, const float *x, const unsigned lon
     if (!x || !bits || !G || !g || !M || !q0 || !v || !w2 || !b2 || !value_out || !z_out || !p_out || !xbar_out || !q_out)
         return tap_fail(ctx, TAP_E_INVALID, "critic value: null buffer");
     if ((rc = cr_check_shape(ctx, "critic value", nR, rows, H, S, blocks, q0_stride)) != TAP_OK) return rc;
-    const void *f32[] = {x, G, g, M, q0, v, w2, b2, value_out, z_out, p_out, xbar_out, q_out};
-    bool bad = cr_misaligned(bits, 8);
-    for (const void *p : f32) bad = bad || cr_misaligned(p, 4);
-    if (bad) return tap_fail(ctx, TAP_E_INVALID, "critic value: bits must be 8-byte and the float buffers 4-byte aligned");
+    if (tap_misaligned(bits, 8) || tap_any_misaligned({x, G, g, M, q0, v, w2, b2, value_out, z_out, p_out, xbar_out, q_out}, 4))
+        return tap_fail(ctx, TAP_E_INVALID, "critic value: bits must be 8-byte and the float buffers 4-byte aligned");
     const CrGeom geo = cr_geom(B, nR, rows, H, false);
     const CrArgs a = {x, bits, G, g, M, q0, v, w2, b2, value_out, z_out, p_out, xbar_out, q_out, nullptr, nullptr, nullptr, nullptr, nullptr,
                       B, nR, rows, S, blocks, geo.planes, geo.mall, geo.resident, q0_stride};
@@ -587,10 +555,9 @@ extern "C" int tap_critic_value_backward(tap_ctx *ctx, const float *x, const uns
     const size_t need = tap_critic_value_backward_scratch(B, nR, rows, H, S, blocks);
     if (!scratch || scratch_bytes < need)
         return tap_fail(ctx, TAP_E_INVALID, "critic value backward: scratch of %zu bytes, %zu needed", scratch ? scratch_bytes : (size_t)0, need);
-    const void *f32[] = {x, G, g, M, v, q, p, dz, dU_out, dq_out, dv_out, scratch};
-    bool bad = cr_misaligned(bits, 8) || cr_misaligned(dU_out, 16);        // dU leaves as float4s
-    for (const void *ptr : f32) bad = bad || cr_misaligned(ptr, 4);
-    if (bad) return tap_fail(ctx, TAP_E_INVALID, "critic value backward: bits must be 8-byte, dU 16-byte and the other float buffers 4-byte aligned");
+    if (tap_misaligned(bits, 8) || tap_misaligned(dU_out, 16) ||        // dU leaves as float4s
+        tap_any_misaligned({x, G, g, M, v, q, p, dz, dU_out, dq_out, dv_out, scratch}, 4))
+        return tap_fail(ctx, TAP_E_INVALID, "critic value backward: bits must be 8-byte, dU 16-byte and the other float buffers 4-byte aligned");
     const CrGeom geo = cr_geom(B, nR, rows, H, true);
     const CrArgs a = {x, bits, G, g, M, nullptr, v, nullptr, nullptr, nullptr, nullptr, const_cast<float *>(p), nullptr,
                       const_cast<float *>(q), dz, dU_out, dq_out, static_cast<float *>(scratch),

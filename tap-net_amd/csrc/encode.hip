@@ -27,6 +27,7 @@
 // the slices' partials in slice order.  No atomics: two calls give the same bytes.
 #include <algorithm>
 
+#include "tap_bitshadow.h"
 #include "tap_common.h"
 
 namespace {
@@ -58,7 +59,7 @@ struct EncGeom {
 inline EncGeom enc_geom(int B, int nR, int rows, int H)
 {
     EncGeom g;
-    g.planes = rows > 64 ? 2 : 1;
+    g.planes = tap_bit_planes(rows);
     g.hpl = (g.planes == 1 && H > 64) ? 2 : 1;
     g.hck = 64 * g.hpl;
     g.CT = std::min(nR, 4096 / g.hck);
@@ -78,7 +79,8 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_encode_bits(EncArgs a)
     const int nR = a.nR, rows = a.rows, CT = a.CT, TS = CT + 1;
     float *lw = enc_lds, *tile = enc_lds + rows * S;
     const int hc0 = (int)blockIdx.y * HCK, hcn = min(HCK, a.H - hc0);     // this block's hidden rows hc0 .. hc0 + hcn - 1
-    // W[hc0 + hl][r] -> lw[r * S + hl]: global reads in memory order, LDS writes at the odd stride S
+    // W[hc0 + hl][r] -> lw[r * S + hl]: tap_fill_chunk's loop and, below, tap_rows_mask0 / 1's masks, written out: through the
+    // helpers this kernel's listing changes and the launch is 2-3 % slower on the largest windows
     for (int i = tid; i < hcn * rows; i += TAP_BLOCK) {
         const int hl = i / rows, r = i - hl * rows;
         lw[r * S + hl] = a.weight[(size_t)hc0 * rows + i];
@@ -107,16 +109,8 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_encode_bits(EncArgs a)
 #pragma unroll
                 for (int i = 0; i < HPL; ++i) acc[i] = b0[i];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {                              // ascending rows: plane 0 before plane 1
-                    unsigned x = (unsigned)__builtin_amdgcn_readlane(piece[q], cl);
-                    while (x) {                                            // scalar: one trip per SET row
-                        const int r = 32 * q + __builtin_ctz(x);
-                        x &= x - 1;
-                        const float *p = lw + r * S + lane;
-#pragma unroll
-                        for (int i = 0; i < HPL; ++i) acc[i] = acc[i] + p[i * 64];
-                    }
-                }
+                for (int q = 0; q < 4; ++q)                                // ascending rows: plane 0 before plane 1
+                    tap_add_set_rows_piece<HPL>(lw, S, lane, q, (unsigned)__builtin_amdgcn_readlane(piece[q], cl), acc);
 #pragma unroll
                 for (int i = 0; i < HPL; ++i) tile[(i * 64 + lane) * TS + cl] = acc[i];
             }
@@ -237,22 +231,21 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_encode_bits_bw_reduce(const float
     else if (dbias) dbias[h] = s;
 }
 
-// the checks of both entries in tap_policy_pick's order: dimensions, then the empty batch (1 = nothing to do), then the
-// caller's null check, then the shapes without a shadow
+// the checks of both entries in tap_policy_pick's order: dimensions, then the empty batch, then the caller's null check,
+// then the shapes without a shadow
 int enc_check_dims(tap_ctx *ctx, const char *what, int B, int nR, int rows, int H)
 {
     if (B < 0 || nR < 1 || rows < 1 || H < 1) return tap_fail(ctx, TAP_E_INVALID, "%s: B %d, nR %d, rows %d, H %d", what, B, nR, rows, H);
     return TAP_OK;
 }
+inline bool enc_shape_ok(int nR, int rows, int H) { return tap_has_bit_shadow(rows, nR) && H <= 1024; }
 int enc_check_shape(tap_ctx *ctx, const char *what, int nR, int rows, int H)
 {
-    if (tap_bits_words(rows, nR) <= 0 || H > 1024)
+    if (!enc_shape_ok(nR, rows, H))
         return tap_fail(ctx, TAP_E_UNSUPPORTED, "%s: rows %d, nR %d, H %d (needs a bit shadow: rows <= 128, nR %% 4 == 0, nR <= 256; H <= 1024)",
                         what, rows, nR, H);
     return TAP_OK;
 }
-
-inline bool enc_misaligned(const void *p, unsigned to) { return ((uintptr_t)p & (to - 1)) != 0; }
 
 } // namespace
 
@@ -265,7 +258,7 @@ extern "C" int tap_encode_bits(tap_ctx *ctx, const unsigned long long *bits, int
     if (!bits || !weight || !out) return tap_fail(ctx, TAP_E_INVALID, "encode bits: null buffer");
     if ((rc = enc_check_shape(ctx, "encode bits", nR, rows, H)) != TAP_OK) return rc;
     // the words are loaded one by one; out leaves as float4s
-    if (enc_misaligned(bits, 8) || enc_misaligned(out, 16))
+    if (tap_misaligned(bits, 8) || tap_misaligned(out, 16))
         return tap_fail(ctx, TAP_E_INVALID, "encode bits: bits must be 8-byte and out 16-byte aligned");
     const EncGeom geo = enc_geom(B, nR, rows, H);
     const EncArgs a = {bits, weight, bias, out, B, nR, rows, H, geo.planes, geo.CT, geo.epb};
@@ -284,7 +277,7 @@ extern "C" int tap_encode_bits_geometry(int B, int nR, int rows, int H, int back
     if (!out) return TAP_E_INVALID;
     out[0] = out[1] = out[2] = out[3] = 0;
     if (B < 1 || nR < 1 || rows < 1 || H < 1) return TAP_E_INVALID;
-    if (tap_bits_words(rows, nR) <= 0 || H > 1024) return TAP_E_UNSUPPORTED;
+    if (!enc_shape_ok(nR, rows, H)) return TAP_E_UNSUPPORTED;
     if (backward) {
         const EncBwGeom g = enc_bw_geom(B, nR, rows, H);
         out[0] = g.per;
@@ -303,7 +296,7 @@ extern "C" int tap_encode_bits_geometry(int B, int nR, int rows, int H, int back
 
 extern "C" size_t tap_encode_bits_backward_scratch(int B, int nR, int rows, int H)
 {
-    if (B < 1 || nR < 1 || rows < 1 || H < 1 || tap_bits_words(rows, nR) <= 0 || H > 1024) return 0;
+    if (B < 1 || nR < 1 || rows < 1 || H < 1 || !enc_shape_ok(nR, rows, H)) return 0;
     const EncBwGeom g = enc_bw_geom(B, nR, rows, H);
     return (size_t)g.slices * (size_t)H * (size_t)(rows + 1) * sizeof(float);
 }
@@ -320,10 +313,10 @@ extern "C" int tap_encode_bits_backward(tap_ctx *ctx, const unsigned long long *
     if (!scratch || scratch_bytes < need)
         return tap_fail(ctx, TAP_E_INVALID, "encode bits backward: scratch of %zu bytes, %zu needed", scratch ? scratch_bytes : (size_t)0, need);
     // g is copied to LDS as float4s; the words and the partials go one by one
-    if (enc_misaligned(bits, 8) || enc_misaligned(g, 16) || enc_misaligned(scratch, 4))
+    if (tap_misaligned(bits, 8) || tap_misaligned(g, 16) || tap_misaligned(scratch, 4))
         return tap_fail(ctx, TAP_E_INVALID, "encode bits backward: bits must be 8-byte, g 16-byte and scratch 4-byte aligned");
     const EncBwGeom geo = enc_bw_geom(B, nR, rows, H);
-    const EncBwArgs a = {bits, g, static_cast<float *>(scratch), B, nR, rows, H, rows > 64 ? 2 : 1, geo.hc, geo.per};
+    const EncBwArgs a = {bits, g, static_cast<float *>(scratch), B, nR, rows, H, tap_bit_planes(rows), geo.hc, geo.per};
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_encode_bits_bw_partial, dim3((unsigned)geo.slices, (unsigned)geo.chunks), dim3(TAP_BLOCK), 0, st, a);
     TAP_LAUNCH_CHECK(ctx, "k_encode_bits_bw_partial");

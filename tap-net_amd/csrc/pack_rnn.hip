@@ -24,6 +24,7 @@
 // Every sum is ONE chain of fmaf in ascending term order and nothing crosses an env: two calls give the same bytes and
 // an env's bytes do not depend on the batch or the tile around it.  The only cross-lane operations are the maximum of
 // the logits / of the footprint (order-free), two ballots, and the integer sums of the height-map.
+#include "tap_bitshadow.h"
 #include "tap_decoder.h"
 #include "tap_place.h"
 
@@ -45,31 +46,6 @@ struct PrnArgs {
 inline size_t prn_lds_bytes(int D)
 {
     return ((size_t)DEC_WROWS * DEC_WS + 2 * (size_t)DEC_TE * PRN_XS + 5 * (size_t)DEC_TE * D) * sizeof(float);
-}
-
-__device__ __forceinline__ int prn_wave_max(int v)
-{
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v = max(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ int prn_wave_min(int v)
-{
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v = min(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ int prn_wave_sum(int v)
-{
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ float prn_wave_fmax(float v)
-{
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
 }
 
 // One weight block on its way to the LDS, in two halves, so that the global loads of block k + 1 are in flight while block k
@@ -184,7 +160,7 @@ __device__ __forceinline__ void prn_rows(float *lw, const float *W, int ld, int 
 __device__ __forceinline__ float prn_input(const int *hm, int form, int W, int c)
 {
     if (form == TAP_FEAT_ZERO) {
-        const int mn = prn_wave_min(c < W ? hm[c] : INT_MAX);
+        const int mn = tap_wave_min(c < W ? hm[c] : INT_MAX);
         return c < W ? (float)(hm[c] - mn) : 0.f;
     }
     if (form == TAP_FEAT_DIFF) return c < W - 1 ? (float)(hm[c + 1] - hm[c]) : 0.f;
@@ -324,7 +300,7 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_pack_rnn_forward(PrnArgs a)
             const int b = e0 + ew + e;
             const bool ev = b < B;
             const float lv = l[0][e];
-            const float m = prn_wave_fmax(incol ? lv : -INFINITY);
+            const float m = tap_wave_max(incol ? lv : -INFINITY);
             const u64 top = __ballot(incol && lv == m);
             const int pick = top ? __ffsll((long long)top) - 1 : 0;            // the first maximum (LG_RL.py:659)
             tap_wave_lds_sync();                                               // the x rows / the previous env's terms have been read
@@ -346,7 +322,7 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_pack_rnn_forward(PrnArgs a)
             const int x = do_step ? xl : 0, wd = do_step ? bw : 0;
             const bool inb = incol && lane >= x && lane < x + wd;
             const int hm0 = incol ? hrow[lane] : 0;
-            const int z = prn_wave_max(inb ? hm0 : 0);
+            const int z = tap_wave_max(inb ? hm0 : 0);
             const u64 wave_eq = __ballot(inb && hm0 == z);
             int hm = hm0, stab = 1;
             if (do_step) {
@@ -357,7 +333,7 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_pack_rnn_forward(PrnArgs a)
                 }
                 if (z + bh > a.d.H) er |= 1;                                   // the reference clips silently
             }
-            const int hsum = prn_wave_sum(incol ? hm : 0), hmax = prn_wave_max(incol ? hm : 0);
+            const int hsum = tap_wave_sum(incol ? hm : 0), hmax = tap_wave_max(incol ? hm : 0);
             if (do_step) {
                 valid[e] += bw * bh;
                 nstab[e] += stab;

@@ -37,6 +37,7 @@
 // the same bytes.
 #include <algorithm>
 
+#include "tap_bitshadow.h"
 #include "tap_common.h"
 #include "tap_pick.h"
 
@@ -68,7 +69,7 @@ inline size_t ptr_lds_floats(int nR, int rows, int Hd, int hck, int epb, int ct,
 inline PtrGeom ptr_geom(int B, int nR, int rows, int Hd, bool backward, int S = 0)
 {
     PtrGeom g;
-    g.planes = rows > 64 ? 2 : 1;
+    g.planes = tap_bit_planes(rows);
     g.hpl = (g.planes == 1 && Hd > 64) ? 2 : 1;
     g.hck = 64 * g.hpl;
     g.nch = Hd / g.hck;
@@ -108,19 +109,6 @@ struct PtrArgsPick : PtrArgsStatic {
     int64_t *ptr;                   // (B,)
     float *logp;                    // (B,)
 };
-
-__device__ __forceinline__ float ptr_wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v = v + __shfl_xor(v, o);                // every lane ends with the same sum
-    return v;
-}
-__device__ __forceinline__ float ptr_wave_max(float v)
-{
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
 
 // the static term of U in the static-rows form: what a phase keeps of its chunk's G and g, a column's xs, and
 // P[x0 + lane + 64 i, c] = g, then fmaf(G[., s], xs[b, s, c], .) for s ascending (tap_critic_value's order)
@@ -203,17 +191,13 @@ struct PtrSeg {
     // stand before (the previous chunk has been consumed) and after.
     __device__ void fill(const PtrArgs &a, float *lds, int seg, int ch, int tid, int lane)
     {
-        const int x0 = seg * a.Hd + ch * HCK, rows = a.rows;
-        for (int i = tid; i < HCK * rows; i += TAP_BLOCK) {
-            const int hl = i / rows, r = i - hl * rows;
-            lds[r * S + hl] = a.M[(size_t)x0 * rows + i];
-        }
+        const int x0 = seg * a.Hd + ch * HCK;
+        tap_fill_chunk(a.M, lds, x0, HCK, HCK, a.rows, tid);
 #pragma unroll
         for (int i = 0; i < HPL; ++i) kk[i] = a.k[x0 + i * 64 + lane];
         lw = lds;
-        // bits at positions >= rows are ignored: masked off each plane's word
-        m0 = rows >= 64 ? ~0ull : (1ull << rows) - 1;
-        m1 = rows >= 128 ? ~0ull : rows > 64 ? (1ull << (rows - 64)) - 1 : 0ull;
+        m0 = tap_rows_mask0(a.rows);
+        m1 = tap_rows_mask1(a.rows);
         st.fill(x0, tid, lane);
     }
 
@@ -236,22 +220,10 @@ struct PtrSeg {
     }
     __device__ __forceinline__ void finish(int lane, float (&u)[HPL], const unsigned long long (&w)[2]) const
     {
-        const unsigned long long w0 = w[0] & m0, w1 = w[1] & m1;
-        const unsigned piece[4] = {(unsigned)w0, (unsigned)(w0 >> 32), (unsigned)w1, (unsigned)(w1 >> 32)};
         float acc[HPL];
 #pragma unroll
         for (int i = 0; i < HPL; ++i) acc[i] = kk[i];
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {                                      // ascending rows: plane 0 before plane 1
-            unsigned x = (unsigned)__builtin_amdgcn_readfirstlane((int)piece[p]);
-            while (x) {                                                    // scalar: one trip per SET row
-                const int r = 32 * p + __builtin_ctz(x);
-                x &= x - 1;
-                const float *lp = lw + r * S + lane;
-#pragma unroll
-                for (int i = 0; i < HPL; ++i) acc[i] = acc[i] + lp[i * 64];
-            }
-        }
+        tap_add_set_rows<HPL>(lw, S, lane, w[0] & m0, w[1] & m1, acc);
 #pragma unroll
         for (int i = 0; i < HPL; ++i) u[i] = u[i] + acc[i];
     }
@@ -374,7 +346,7 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_pointer_scores(A a)
                 float p = vv[0] * tanhf(u[0] + qq[0]);
 #pragma unroll
                 for (int i = 1; i < HPL; ++i) p = p + vv[i] * tanhf(u[i] + qq[i]);
-                p = ptr_wave_sum(p);
+                p = tap_wave_sum(p);
                 if (lane == 0) sl[e * nR + c] = ch == 0 ? p : sl[e * nR + c] + p;
             });
         }
@@ -384,14 +356,14 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_pointer_scores(A a)
     for (int e = wave; e < ne; e += PTR_NW) {
         float m = -INFINITY;
         for (int c = lane; c < nR; c += 64) m = fmaxf(m, sl[e * nR + c]);
-        m = ptr_wave_max(m);
+        m = tap_wave_max(m);
         float z = 0.f;
         for (int c = lane; c < nR; c += 64) {
             const float x = expf(sl[e * nR + c] - m);
             sl[e * nR + c] = x;
             z = z + x;
         }
-        z = ptr_wave_sum(z);
+        z = tap_wave_sum(z);
         for (int c = lane; c < nR; c += 64) {
             const float x = sl[e * nR + c] / z;
             sl[e * nR + c] = x;
@@ -439,7 +411,7 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_pointer_scores(A a)
                 float p = vv[0] * tanhf(u[0] + tt[0]);
 #pragma unroll
                 for (int i = 1; i < HPL; ++i) p = p + vv[i] * tanhf(u[i] + tt[i]);
-                p = ptr_wave_sum(p);
+                p = tap_wave_sum(p);
                 if (lane == 0) sl[e * nR + c] = ch == 0 ? p : sl[e * nR + c] + p;
             });
         }
@@ -545,7 +517,7 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_pointer_scores_bw(A a)
                     for (int i = 1; i < HPL; ++i) p = p + dt[i] * u[i];
 #pragma unroll
                     for (int i = 0; i < HPL; ++i) tile[(i * 64 + lane) * TS + c - cb] = at * dt[i];
-                    p = ptr_wave_sum(p);
+                    p = tap_wave_sum(p);
                     if (lane == 0) dl[e * nR + c] = ch == 0 ? p : dl[e * nR + c] + p;
                 });
                 ptr_store_tile(tile, TS, ncol, HCK, a.dU + ((size_t)b * 3 * Hd + 2 * Hd + ch * HCK) * nR + cb, nR, tid);
@@ -558,7 +530,7 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_pointer_scores_bw(A a)
         const float *at = a.attn + (size_t)(e0 + e) * nR;
         float z = 0.f;
         for (int c = lane; c < nR; c += 64) z = z + at[c] * dl[e * nR + c];
-        z = ptr_wave_sum(z);
+        z = tap_wave_sum(z);
         for (int c = lane; c < nR; c += 64) dl[e * nR + c] = at[c] * (dl[e * nR + c] - z);
     }
     // phase 3, segment 0: A = U + q; dva += ds tanh(A); dA = ds va (1 - tanh^2) = dU[j]; dq[j] = sum_c dA[j, c]
@@ -618,82 +590,125 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_pointer_scores_bw_reduce(const fl
     else dvp[i - Hd] = s;
 }
 
-// the checks of both entries in tap_policy_pick's order: dimensions, then the empty batch, then the caller's null
-// check, then the shapes without a kernel
-int ptr_check_dims(tap_ctx *ctx, const char *what, int B, int nR, int rows, int Hd)
+// ---- host ----------------------------------------------------------------------------------------------------------
+// one call of the family, as its five entries describe it: the name in messages, which entry (the proj form has no S),
+// the dimensions, and which kernel: the forward (form = PTR_NOPICK, or the pick's PTR_GREEDY / PTR_DRAW) or the backward
+enum PtrKind { PTR_K_PROJ, PTR_K_STATIC, PTR_K_PICK };
+struct PtrCall {
+    const char *what;
+    PtrKind kind;
+    int B, nR, rows, Hd, S;         // S = 0 in the proj form
+    bool backward;
+    int form;
+};
+inline bool ptr_shape_ok(int nR, int rows, int Hd) { return tap_has_bit_shadow(rows, nR) && (Hd == 64 || Hd == 128 || Hd == 256); }
+inline PtrGeom ptr_geom(const PtrCall &c) { return ptr_geom(c.B, c.nR, c.rows, c.Hd, c.backward, c.S); }
+inline size_t ptr_scratch_bytes(int B, int nR, int rows, int Hd, int S)   // the backward's dva / dvp partials
 {
-    if (B < 0 || nR < 1 || rows < 1 || Hd < 1) return tap_fail(ctx, TAP_E_INVALID, "%s: B %d, nR %d, rows %d, Hd %d", what, B, nR, rows, Hd);
-    return TAP_OK;
+    return (size_t)ptr_geom(B, nR, rows, Hd, true, S).blocks * 2 * (size_t)Hd * sizeof(float);
 }
-inline bool ptr_shape_ok(int nR, int rows, int Hd) { return tap_bits_words(rows, nR) > 0 && (Hd == 64 || Hd == 128 || Hd == 256); }
-int ptr_check_shape(tap_ctx *ctx, const char *what, int nR, int rows, int Hd)
-{
-    if (!ptr_shape_ok(nR, rows, Hd))
-        return tap_fail(ctx, TAP_E_UNSUPPORTED, "%s: rows %d, nR %d, Hd %d (needs a bit shadow: rows <= 128, nR %% 4 == 0, nR <= 256; Hd 64, 128 or 256)",
-                        what, rows, nR, Hd);
-    return TAP_OK;
-}
-inline bool ptr_misaligned(const void *p, unsigned to) { return ((uintptr_t)p & (to - 1)) != 0; }
 
-// the static-rows form's launch: the instantiation (HPL, SS) of the forward or the backward
-template <int HPL, int SS>
-void ptr_launch_static_ss(bool backward, const PtrGeom &geo, hipStream_t st, const PtrArgsStatic &a)
+// the checks of all five entries, in tap_policy_pick's order: dimensions (the pick: and its form), then the empty batch --
+// TAP_OK, and the entry returns --, then the null check of `need`, the entry's own `extra` checks, the shapes without a
+// kernel, the backward's scratch, and the alignment of the a4 / a8 / a16 lists (a null optional buffer is aligned)
+template <class Extra>
+int ptr_check(tap_ctx *ctx, const PtrCall &c, TapPtrList need, TapPtrList a4, TapPtrList a8, TapPtrList a16, const void *scratch, size_t scratch_bytes,
+              Extra &&extra)
 {
-    if (backward) hipLaunchKernelGGL((k_pointer_scores_bw<HPL, SS, PtrArgsStatic>), dim3((unsigned)geo.blocks), dim3(TAP_BLOCK), geo.lds, st, a);
-    else hipLaunchKernelGGL((k_pointer_scores<HPL, SS, PtrArgsStatic>), dim3((unsigned)geo.blocks), dim3(TAP_BLOCK), geo.lds, st, a);
-}
-template <int HPL>
-void ptr_launch_static_hpl(bool backward, const PtrGeom &geo, hipStream_t st, const PtrArgsStatic &a)
-{
-    switch (ptr_static_ss(a.S)) {
-    case 2: ptr_launch_static_ss<HPL, 2>(backward, geo, st, a); break;
-    case 3: ptr_launch_static_ss<HPL, 3>(backward, geo, st, a); break;
-    case 4: ptr_launch_static_ss<HPL, 4>(backward, geo, st, a); break;
-    default: ptr_launch_static_ss<HPL, 0>(backward, geo, st, a); break;
+    const bool proj = c.kind == PTR_K_PROJ;
+    if (c.B < 0 || c.nR < 1 || c.rows < 1 || c.Hd < 1 || (!proj && c.S < 1))
+        return proj ? tap_fail(ctx, TAP_E_INVALID, "%s: B %d, nR %d, rows %d, Hd %d", c.what, c.B, c.nR, c.rows, c.Hd)
+                    : tap_fail(ctx, TAP_E_INVALID, "%s: B %d, nR %d, rows %d, Hd %d, S %d", c.what, c.B, c.nR, c.rows, c.Hd, c.S);
+    if (c.kind == PTR_K_PICK && c.form != PTR_GREEDY && c.form != PTR_DRAW) return tap_fail(ctx, TAP_E_INVALID, "%s: form %d", c.what, c.form);
+    if (c.B == 0) return TAP_OK; // an empty batch has no buffers to check (and leaves a backward's outputs as they are)
+    for (const void *p : need)
+        if (!p) return tap_fail(ctx, TAP_E_INVALID, "%s: null buffer", c.what);
+    if (const int rc = extra(); rc != TAP_OK) return rc;
+    if (!ptr_shape_ok(c.nR, c.rows, c.Hd) || c.S > PTR_SMAX)
+        return proj ? tap_fail(ctx, TAP_E_UNSUPPORTED, "%s: rows %d, nR %d, Hd %d (needs a bit shadow: rows <= 128, nR %% 4 == 0, nR <= 256; Hd 64, 128 or 256)",
+                               c.what, c.rows, c.nR, c.Hd)
+                    : tap_fail(ctx, TAP_E_UNSUPPORTED, "%s: rows %d, nR %d, Hd %d, S %d (needs a bit shadow: rows <= 128, nR %% 4 == 0, nR <= 256; Hd 64, 128 or 256; S <= 8)",
+                               c.what, c.rows, c.nR, c.Hd, c.S);
+    if (c.backward) {
+        const size_t have = scratch ? scratch_bytes : (size_t)0, needed = ptr_scratch_bytes(c.B, c.nR, c.rows, c.Hd, c.S);
+        if (!scratch || have < needed) return tap_fail(ctx, TAP_E_INVALID, "%s: scratch of %zu bytes, %zu needed", c.what, have, needed);
     }
-}
-void ptr_launch_static(bool backward, const PtrGeom &geo, hipStream_t st, const PtrArgsStatic &a)
-{
-    if (geo.hpl == 1) ptr_launch_static_hpl<1>(backward, geo, st, a);
-    else ptr_launch_static_hpl<2>(backward, geo, st, a);
-}
-int ptr_check_dims_static(tap_ctx *ctx, const char *what, int B, int nR, int rows, int Hd, int S)
-{
-    if (B < 0 || nR < 1 || rows < 1 || Hd < 1 || S < 1)
-        return tap_fail(ctx, TAP_E_INVALID, "%s: B %d, nR %d, rows %d, Hd %d, S %d", what, B, nR, rows, Hd, S);
+    if (tap_any_misaligned(a4, 4) || tap_any_misaligned(a8, 8) || tap_any_misaligned(a16, 16)) {
+        const char *rule = c.backward ? "bits must be 8-byte, dU 16-byte and the other float buffers 4-byte aligned" // dU leaves as float4s
+                           : c.kind == PTR_K_PICK ? "bits and ptr_out must be 8-byte and the float buffers 4-byte aligned"
+                                                  : "bits must be 8-byte and the float buffers 4-byte aligned";
+        return tap_fail(ctx, TAP_E_INVALID, "%s: %s", c.what, rule);
+    }
     return TAP_OK;
 }
-int ptr_check_shape_static(tap_ctx *ctx, const char *what, int nR, int rows, int Hd, int S)
+inline int ptr_check(tap_ctx *ctx, const PtrCall &c, TapPtrList need, TapPtrList a4, TapPtrList a8, TapPtrList a16, const void *scratch = nullptr,
+                     size_t scratch_bytes = 0)
 {
-    if (!ptr_shape_ok(nR, rows, Hd) || S > PTR_SMAX)
-        return tap_fail(ctx, TAP_E_UNSUPPORTED, "%s: rows %d, nR %d, Hd %d, S %d (needs a bit shadow: rows <= 128, nR %% 4 == 0, nR <= 256; Hd 64, 128 or 256; S <= 8)",
-                        what, rows, nR, Hd, S);
-    return TAP_OK;
+    return ptr_check(ctx, c, need, a4, a8, a16, scratch, scratch_bytes, [] { return TAP_OK; });
 }
-// the launch record of the static-rows form: the proj form's fields with S in the last one
-void ptr_hit_static(tap_ctx *ctx, const PtrGeom &geo, int backward, int S)
+
+// what every form's kernel takes, by name; the entry adds its own fields (everything else stays null / 0)
+template <class A>
+A ptr_args(const PtrCall &c, const PtrGeom &geo, const unsigned long long *bits, const float *M, const float *k, const float *q,
+           const float *va, const float *vp)
 {
-    const int32_t key[7] = {TAP_HIT_POINTER, 0, geo.hpl, geo.planes, geo.nch, backward, S};
+    A a{};
+    a.bits = bits; a.M = M; a.k = k; a.q = q; a.va = va; a.vp = vp;
+    a.B = c.B; a.nR = c.nR; a.rows = c.rows; a.Hd = c.Hd;
+    a.planes = geo.planes; a.epb = geo.epb; a.ct = geo.ct;
+    return a;
+}
+
+// the launch of the instantiation (HPL, SS) of the forward k_pointer_scores<., ., A, FORM> or the backward: HPL from the
+// geometry; SS = PTR_PROJ with PtrArgs, else the static rows' 0, 2, 3 or 4
+template <int V> using PtrInt = std::integral_constant<int, V>;
+template <class A, int FORM = PTR_NOPICK, bool BW = false>
+void ptr_launch(const PtrGeom &geo, hipStream_t st, const A &a)
+{
+    auto one = [&](auto hpl, auto ss) {
+        constexpr int HPL = decltype(hpl)::value, SS = decltype(ss)::value;
+        const dim3 grid((unsigned)geo.blocks), block(TAP_BLOCK);
+        if constexpr (BW) hipLaunchKernelGGL((k_pointer_scores_bw<HPL, SS, A>), grid, block, geo.lds, st, a);
+        else hipLaunchKernelGGL((k_pointer_scores<HPL, SS, A, FORM>), grid, block, geo.lds, st, a);
+    };
+    auto with = [&](auto ss) {
+        if (geo.hpl == 1) one(PtrInt<1>{}, ss);
+        else one(PtrInt<2>{}, ss);
+    };
+    if constexpr (std::is_same_v<A, PtrArgs>) with(PtrInt<PTR_PROJ>{});
+    else
+        switch (ptr_static_ss(a.S)) {
+        case 2: with(PtrInt<2>{}); break;
+        case 3: with(PtrInt<3>{}); break;
+        case 4: with(PtrInt<4>{}); break;
+        default: with(PtrInt<0>{}); break;
+        }
+}
+
+// the launch record (tapenv.h: tap_variant_hits): (28, FORM, HPL, PLANES, NCH, BACKWARD, S) -- with S = 0 what tap_variant_hit
+// makes of TapVariant{planes, nch, backward} and wt = 0
+void ptr_hit(tap_ctx *ctx, const PtrGeom &geo, const PtrCall &c)
+{
+    const int32_t key[7] = {TAP_HIT_POINTER, c.form, geo.hpl, geo.planes, geo.nch, c.backward ? 1 : 0, c.S};
     tap_variant_hit_key(ctx, key);
 }
 
-// the fused form's launch: the instantiation (HPL, SS, FORM)
-template <int HPL, int SS>
-void ptr_launch_pick_ss(int form, const PtrGeom &geo, hipStream_t st, const PtrArgsPick &a)
+// a checked call: the launch, the backward's second launch (dva | dvp from the workgroups' partials), the record
+template <class A, int FORM = PTR_NOPICK, bool BW = false>
+int ptr_run(tap_ctx *ctx, const PtrCall &c, const PtrGeom &geo, const A &a, void *stream, float *dva = nullptr, float *dvp = nullptr)
 {
-    const dim3 grid((unsigned)geo.blocks), block(TAP_BLOCK);
-    if (form == PTR_GREEDY) hipLaunchKernelGGL((k_pointer_scores<HPL, SS, PtrArgsPick, PTR_GREEDY>), grid, block, geo.lds, st, a);
-    else hipLaunchKernelGGL((k_pointer_scores<HPL, SS, PtrArgsPick, PTR_DRAW>), grid, block, geo.lds, st, a);
-}
-template <int HPL>
-void ptr_launch_pick_hpl(int form, const PtrGeom &geo, hipStream_t st, const PtrArgsPick &a)
-{
-    switch (ptr_static_ss(a.S)) {
-    case 2: ptr_launch_pick_ss<HPL, 2>(form, geo, st, a); break;
-    case 3: ptr_launch_pick_ss<HPL, 3>(form, geo, st, a); break;
-    case 4: ptr_launch_pick_ss<HPL, 4>(form, geo, st, a); break;
-    default: ptr_launch_pick_ss<HPL, 0>(form, geo, st, a); break;
+    static const char *const fw[] = {"k_pointer_scores", "k_pointer_scores (static rows)", "k_pointer_scores (pick)"};
+    static const char *const bw[] = {"k_pointer_scores_bw", "k_pointer_scores_bw (static rows)"};
+    hipStream_t st = (hipStream_t)stream;
+    ptr_launch<A, FORM, BW>(geo, st, a);
+    TAP_LAUNCH_CHECK(ctx, (BW ? bw : fw)[c.kind]);
+    if constexpr (BW) {
+        hipLaunchKernelGGL(k_pointer_scores_bw_reduce, dim3((unsigned)((2 * c.Hd + TAP_BLOCK - 1) / TAP_BLOCK)), dim3(TAP_BLOCK), 0, st,
+                           static_cast<const float *>(a.part), geo.blocks, c.Hd, dva, dvp);
+        TAP_LAUNCH_CHECK(ctx, "k_pointer_scores_bw_reduce");
     }
+    ptr_hit(ctx, geo, c);
+    return TAP_OK;
 }
 
 } // namespace
@@ -702,31 +717,21 @@ extern "C" int tap_pointer_scores(tap_ctx *ctx, const float *proj, const unsigne
                                   const float *M, const float *k, const float *q, const float *va, const float *vp,
                                   float *logits_out, float *attn_out, float *t_out, void *stream)
 {
-    int rc = ptr_check_dims(ctx, "pointer scores", B, nR, rows, Hd);
-    if (rc != TAP_OK) return rc;
-    if (B == 0) return TAP_OK; // an empty batch has no buffers to check
-    if (!proj || !bits || !M || !k || !q || !va || !vp || !logits_out || !attn_out || !t_out)
-        return tap_fail(ctx, TAP_E_INVALID, "pointer scores: null buffer");
-    if ((rc = ptr_check_shape(ctx, "pointer scores", nR, rows, Hd)) != TAP_OK) return rc;
-    const void *f32[] = {proj, M, k, q, va, vp, logits_out, attn_out, t_out};
-    bool bad = ptr_misaligned(bits, 8);
-    for (const void *p : f32) bad = bad || ptr_misaligned(p, 4);
-    if (bad) return tap_fail(ctx, TAP_E_INVALID, "pointer scores: bits must be 8-byte and the float buffers 4-byte aligned");
-    const PtrGeom geo = ptr_geom(B, nR, rows, Hd, false);
-    const PtrArgs a = {proj, bits, M, k, q, va, vp, logits_out, attn_out, t_out, nullptr, nullptr, nullptr, nullptr,
-                       B, nR, rows, Hd, geo.planes, geo.epb, 0};
-    hipStream_t st = (hipStream_t)stream;
-    if (geo.hpl == 1) hipLaunchKernelGGL((k_pointer_scores<1>), dim3((unsigned)geo.blocks), dim3(TAP_BLOCK), geo.lds, st, a);
-    else hipLaunchKernelGGL((k_pointer_scores<2>), dim3((unsigned)geo.blocks), dim3(TAP_BLOCK), geo.lds, st, a);
-    TAP_LAUNCH_CHECK(ctx, "k_pointer_scores");
-    tap_variant_hit(ctx, TAP_HIT_POINTER, 0, geo.hpl, TapVariant{geo.planes, geo.nch, 0}, 0);
-    return TAP_OK;
+    const PtrCall c = {"pointer scores", PTR_K_PROJ, B, nR, rows, Hd, 0, false, PTR_NOPICK};
+    const int rc = ptr_check(ctx, c, {proj, bits, M, k, q, va, vp, logits_out, attn_out, t_out},
+                             {proj, M, k, q, va, vp, logits_out, attn_out, t_out}, {bits}, {});
+    if (rc != TAP_OK || B == 0) return rc;
+    const PtrGeom geo = ptr_geom(c);
+    PtrArgs a = ptr_args<PtrArgs>(c, geo, bits, M, k, q, va, vp);
+    a.proj = proj;
+    a.logits = logits_out; a.attn = attn_out; a.t = t_out;
+    return ptr_run(ctx, c, geo, a, stream);
 }
 
 extern "C" size_t tap_pointer_scores_backward_scratch(int B, int nR, int rows, int Hd)
 {
     if (B < 1 || nR < 1 || rows < 1 || Hd < 1 || !ptr_shape_ok(nR, rows, Hd)) return 0;
-    return (size_t)ptr_geom(B, nR, rows, Hd, true).blocks * 2 * (size_t)Hd * sizeof(float);
+    return ptr_scratch_bytes(B, nR, rows, Hd, 0);
 }
 
 extern "C" int tap_pointer_scores_backward(tap_ctx *ctx, const float *proj, const unsigned long long *bits, int B, int nR, int rows,
@@ -734,34 +739,20 @@ extern "C" int tap_pointer_scores_backward(tap_ctx *ctx, const float *proj, cons
                                            const float *attn, const float *t, const float *g, float *dU_out, float *dq_out,
                                            float *dva_out, float *dvp_out, void *scratch, size_t scratch_bytes, void *stream)
 {
-    int rc = ptr_check_dims(ctx, "pointer scores backward", B, nR, rows, Hd);
-    if (rc != TAP_OK) return rc;
-    if (B == 0) return TAP_OK; // (an empty batch leaves the outputs as they are)
-    if (!proj || !bits || !M || !k || !q || !va || !vp || !attn || !t || !g || !dU_out || !dq_out || !dva_out || !dvp_out)
-        return tap_fail(ctx, TAP_E_INVALID, "pointer scores backward: null buffer");
-    if ((rc = ptr_check_shape(ctx, "pointer scores backward", nR, rows, Hd)) != TAP_OK) return rc;
-    const size_t need = tap_pointer_scores_backward_scratch(B, nR, rows, Hd);
-    if (!scratch || scratch_bytes < need)
-        return tap_fail(ctx, TAP_E_INVALID, "pointer scores backward: scratch of %zu bytes, %zu needed", scratch ? scratch_bytes : (size_t)0, need);
-    const void *f32[] = {proj, M, k, q, va, vp, attn, t, g, dU_out, dq_out, dva_out, dvp_out, scratch};
-    bool bad = ptr_misaligned(bits, 8) || ptr_misaligned(dU_out, 16);      // dU leaves as float4s
-    for (const void *p : f32) bad = bad || ptr_misaligned(p, 4);
-    if (bad) return tap_fail(ctx, TAP_E_INVALID, "pointer scores backward: bits must be 8-byte, dU 16-byte and the other float buffers 4-byte aligned");
-    const PtrGeom geo = ptr_geom(B, nR, rows, Hd, true);
-    const PtrArgs a = {proj, bits, M, k, q, va, vp, nullptr, const_cast<float *>(attn), const_cast<float *>(t), g, dU_out, dq_out,
-                       static_cast<float *>(scratch), B, nR, rows, Hd, geo.planes, geo.epb, geo.ct};
-    hipStream_t st = (hipStream_t)stream;
-    if (geo.hpl == 1) hipLaunchKernelGGL((k_pointer_scores_bw<1>), dim3((unsigned)geo.blocks), dim3(TAP_BLOCK), geo.lds, st, a);
-    else hipLaunchKernelGGL((k_pointer_scores_bw<2>), dim3((unsigned)geo.blocks), dim3(TAP_BLOCK), geo.lds, st, a);
-    TAP_LAUNCH_CHECK(ctx, "k_pointer_scores_bw");
-    hipLaunchKernelGGL(k_pointer_scores_bw_reduce, dim3((unsigned)((2 * Hd + TAP_BLOCK - 1) / TAP_BLOCK)), dim3(TAP_BLOCK), 0, st,
-                       static_cast<const float *>(scratch), geo.blocks, Hd, dva_out, dvp_out);
-    TAP_LAUNCH_CHECK(ctx, "k_pointer_scores_bw_reduce");
-    tap_variant_hit(ctx, TAP_HIT_POINTER, 0, geo.hpl, TapVariant{geo.planes, geo.nch, 1}, 0);
-    return TAP_OK;
+    const PtrCall c = {"pointer scores backward", PTR_K_PROJ, B, nR, rows, Hd, 0, true, PTR_NOPICK};
+    const int rc = ptr_check(ctx, c, {proj, bits, M, k, q, va, vp, attn, t, g, dU_out, dq_out, dva_out, dvp_out},
+                             {proj, M, k, q, va, vp, attn, t, g, dU_out, dq_out, dva_out, dvp_out, scratch}, {bits}, {dU_out}, scratch,
+                             scratch_bytes);
+    if (rc != TAP_OK || B == 0) return rc;
+    const PtrGeom geo = ptr_geom(c);
+    PtrArgs a = ptr_args<PtrArgs>(c, geo, bits, M, k, q, va, vp);
+    a.proj = proj;
+    a.attn = const_cast<float *>(attn); a.t = const_cast<float *>(t); a.g = g;
+    a.dU = dU_out; a.dq = dq_out; a.part = static_cast<float *>(scratch);
+    return ptr_run<PtrArgs, PTR_NOPICK, true>(ctx, c, geo, a, stream, dva_out, dvp_out);
 }
 
-// host only: what ptr_geom gives the four launchers, for tests that must know which geometry a batch runs with
+// host only: what ptr_geom gives the five entries, for tests that must know which geometry a batch runs with
 extern "C" int tap_pointer_scores_geometry(int B, int nR, int rows, int Hd, int S, int backward, int32_t out[4])
 {
     if (!out) return TAP_E_INVALID;
@@ -781,30 +772,21 @@ extern "C" int tap_pointer_scores_static(tap_ctx *ctx, const float *xs, const un
                                          const float *va, const float *vp, float *logits_out, float *attn_out, float *t_out,
                                          void *stream)
 {
-    int rc = ptr_check_dims_static(ctx, "pointer scores static", B, nR, rows, Hd, S);
-    if (rc != TAP_OK) return rc;
-    if (B == 0) return TAP_OK; // an empty batch has no buffers to check
-    if (!xs || !bits || !G || !g || !M || !k || !q || !va || !vp || !logits_out || !attn_out || !t_out)
-        return tap_fail(ctx, TAP_E_INVALID, "pointer scores static: null buffer");
-    if ((rc = ptr_check_shape_static(ctx, "pointer scores static", nR, rows, Hd, S)) != TAP_OK) return rc;
-    const void *f32[] = {xs, G, g, M, k, q, va, vp, logits_out, attn_out, t_out};
-    bool bad = ptr_misaligned(bits, 8);
-    for (const void *p : f32) bad = bad || ptr_misaligned(p, 4);
-    if (bad) return tap_fail(ctx, TAP_E_INVALID, "pointer scores static: bits must be 8-byte and the float buffers 4-byte aligned");
-    const PtrGeom geo = ptr_geom(B, nR, rows, Hd, false, S);
-    const PtrArgsStatic a = {{nullptr, bits, M, k, q, va, vp, logits_out, attn_out, t_out, nullptr, nullptr, nullptr, nullptr,
-                              B, nR, rows, Hd, geo.planes, geo.epb, 0},
-                             xs, G, g, S};
-    ptr_launch_static(false, geo, (hipStream_t)stream, a);
-    TAP_LAUNCH_CHECK(ctx, "k_pointer_scores (static rows)");
-    ptr_hit_static(ctx, geo, 0, S);
-    return TAP_OK;
+    const PtrCall c = {"pointer scores static", PTR_K_STATIC, B, nR, rows, Hd, S, false, PTR_NOPICK};
+    const int rc = ptr_check(ctx, c, {xs, bits, G, g, M, k, q, va, vp, logits_out, attn_out, t_out},
+                             {xs, G, g, M, k, q, va, vp, logits_out, attn_out, t_out}, {bits}, {});
+    if (rc != TAP_OK || B == 0) return rc;
+    const PtrGeom geo = ptr_geom(c);
+    PtrArgsStatic a = ptr_args<PtrArgsStatic>(c, geo, bits, M, k, q, va, vp);
+    a.xs = xs; a.Gs = G; a.gs = g; a.S = S;
+    a.logits = logits_out; a.attn = attn_out; a.t = t_out;
+    return ptr_run(ctx, c, geo, a, stream);
 }
 
 extern "C" size_t tap_pointer_scores_static_backward_scratch(int B, int nR, int rows, int Hd, int S)
 {
     if (B < 1 || nR < 1 || rows < 1 || Hd < 1 || S < 1 || S > PTR_SMAX || !ptr_shape_ok(nR, rows, Hd)) return 0;
-    return (size_t)ptr_geom(B, nR, rows, Hd, true, S).blocks * 2 * (size_t)Hd * sizeof(float);
+    return ptr_scratch_bytes(B, nR, rows, Hd, S);
 }
 
 extern "C" int tap_pointer_scores_static_backward(tap_ctx *ctx, const float *xs, const unsigned long long *bits, int B, int nR, int rows,
@@ -813,32 +795,17 @@ extern "C" int tap_pointer_scores_static_backward(tap_ctx *ctx, const float *xs,
                                                   const float *grad, float *dU_out, float *dq_out, float *dva_out, float *dvp_out,
                                                   void *scratch, size_t scratch_bytes, void *stream)
 {
-    int rc = ptr_check_dims_static(ctx, "pointer scores static backward", B, nR, rows, Hd, S);
-    if (rc != TAP_OK) return rc;
-    if (B == 0) return TAP_OK; // (an empty batch leaves the outputs as they are)
-    if (!xs || !bits || !G || !g || !M || !k || !q || !va || !vp || !attn || !t || !grad || !dU_out || !dq_out || !dva_out || !dvp_out)
-        return tap_fail(ctx, TAP_E_INVALID, "pointer scores static backward: null buffer");
-    if ((rc = ptr_check_shape_static(ctx, "pointer scores static backward", nR, rows, Hd, S)) != TAP_OK) return rc;
-    const size_t need = tap_pointer_scores_static_backward_scratch(B, nR, rows, Hd, S);
-    if (!scratch || scratch_bytes < need)
-        return tap_fail(ctx, TAP_E_INVALID, "pointer scores static backward: scratch of %zu bytes, %zu needed", scratch ? scratch_bytes : (size_t)0, need);
-    const void *f32[] = {xs, G, g, M, k, q, va, vp, attn, t, grad, dU_out, dq_out, dva_out, dvp_out, scratch};
-    bool bad = ptr_misaligned(bits, 8) || ptr_misaligned(dU_out, 16);      // dU leaves as float4s
-    for (const void *p : f32) bad = bad || ptr_misaligned(p, 4);
-    if (bad)
-        return tap_fail(ctx, TAP_E_INVALID, "pointer scores static backward: bits must be 8-byte, dU 16-byte and the other float buffers 4-byte aligned");
-    const PtrGeom geo = ptr_geom(B, nR, rows, Hd, true, S);
-    const PtrArgsStatic a = {{nullptr, bits, M, k, q, va, vp, nullptr, const_cast<float *>(attn), const_cast<float *>(t), grad, dU_out,
-                              dq_out, static_cast<float *>(scratch), B, nR, rows, Hd, geo.planes, geo.epb, geo.ct},
-                             xs, G, g, S};
-    hipStream_t st = (hipStream_t)stream;
-    ptr_launch_static(true, geo, st, a);
-    TAP_LAUNCH_CHECK(ctx, "k_pointer_scores_bw (static rows)");
-    hipLaunchKernelGGL(k_pointer_scores_bw_reduce, dim3((unsigned)((2 * Hd + TAP_BLOCK - 1) / TAP_BLOCK)), dim3(TAP_BLOCK), 0, st,
-                       static_cast<const float *>(scratch), geo.blocks, Hd, dva_out, dvp_out);
-    TAP_LAUNCH_CHECK(ctx, "k_pointer_scores_bw_reduce");
-    ptr_hit_static(ctx, geo, 1, S);
-    return TAP_OK;
+    const PtrCall c = {"pointer scores static backward", PTR_K_STATIC, B, nR, rows, Hd, S, true, PTR_NOPICK};
+    const int rc = ptr_check(ctx, c, {xs, bits, G, g, M, k, q, va, vp, attn, t, grad, dU_out, dq_out, dva_out, dvp_out},
+                             {xs, G, g, M, k, q, va, vp, attn, t, grad, dU_out, dq_out, dva_out, dvp_out, scratch}, {bits}, {dU_out},
+                             scratch, scratch_bytes);
+    if (rc != TAP_OK || B == 0) return rc;
+    const PtrGeom geo = ptr_geom(c);
+    PtrArgsStatic a = ptr_args<PtrArgsStatic>(c, geo, bits, M, k, q, va, vp);
+    a.xs = xs; a.Gs = G; a.gs = g; a.S = S;
+    a.attn = const_cast<float *>(attn); a.t = const_cast<float *>(t); a.g = grad;
+    a.dU = dU_out; a.dq = dq_out; a.part = static_cast<float *>(scratch);
+    return ptr_run<PtrArgsStatic, PTR_NOPICK, true>(ctx, c, geo, a, stream, dva_out, dvp_out);
 }
 
 extern "C" int tap_pointer_pick_static(tap_ctx *ctx, const float *xs, size_t xs_env_stride, const unsigned long long *bits, int B, int nR,
@@ -847,32 +814,23 @@ extern "C" int tap_pointer_pick_static(tap_ctx *ctx, const float *xs, size_t xs_
                                        const int64_t *state, uint32_t step, uint32_t env_offset, int64_t *ptr_out, float *logp_out,
                                        float *logits_out, void *stream)
 {
-    int rc = ptr_check_dims_static(ctx, "pointer pick static", B, nR, rows, Hd, S);
-    if (rc != TAP_OK) return rc;
-    if (form != TAP_PICK_GREEDY && form != TAP_PICK_DRAW) return tap_fail(ctx, TAP_E_INVALID, "pointer pick static: form %d", form);
-    if (B == 0) return TAP_OK; // an empty batch has no buffers to check
-    if (!xs || !bits || !G || !g || !M || !k || !q || !va || !vp || !mask || !ptr_out || !logp_out)
-        return tap_fail(ctx, TAP_E_INVALID, "pointer pick static: null buffer");
-    if (form == TAP_PICK_DRAW && (!state || ptr_misaligned(state, 8)))
-        return tap_fail(ctx, TAP_E_INVALID, "pointer pick static: state must be an 8-byte aligned int64[2]");
-    if (xs_env_stride < (size_t)S * (size_t)nR)
-        return tap_fail(ctx, TAP_E_INVALID, "pointer pick static: xs_env_stride %zu below S * nR = %zu", xs_env_stride, (size_t)S * (size_t)nR);
-    if ((rc = ptr_check_shape_static(ctx, "pointer pick static", nR, rows, Hd, S)) != TAP_OK) return rc;
-    const void *f32[] = {xs, G, g, M, k, q, va, vp, mask, logp_out, logits_out};
-    bool bad = ptr_misaligned(bits, 8) || ptr_misaligned(ptr_out, 8);
-    for (const void *p : f32) bad = bad || ptr_misaligned(p, 4);
-    if (bad) return tap_fail(ctx, TAP_E_INVALID, "pointer pick static: bits and ptr_out must be 8-byte and the float buffers 4-byte aligned");
     static_assert(PTR_GREEDY == TAP_PICK_GREEDY && PTR_DRAW == TAP_PICK_DRAW, "the entry's forms are the kernels'");
-    const PtrGeom geo = ptr_geom(B, nR, rows, Hd, false, S);
-    const PtrArgsPick a = {{{nullptr, bits, M, k, q, va, vp, logits_out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                             B, nR, rows, Hd, geo.planes, geo.epb, 0},
-                            xs, G, g, S},
-                           xs_env_stride, mask, (const long long *)state, step, env_offset, ptr_out, logp_out};
-    hipStream_t st = (hipStream_t)stream;
-    if (geo.hpl == 1) ptr_launch_pick_hpl<1>(form, geo, st, a);
-    else ptr_launch_pick_hpl<2>(form, geo, st, a);
-    TAP_LAUNCH_CHECK(ctx, "k_pointer_scores (pick)");
-    const int32_t key[7] = {TAP_HIT_POINTER, form, geo.hpl, geo.planes, geo.nch, 0, S};
-    tap_variant_hit_key(ctx, key);
-    return TAP_OK;
+    const PtrCall c = {"pointer pick static", PTR_K_PICK, B, nR, rows, Hd, S, false, form};
+    const int rc = ptr_check(ctx, c, {xs, bits, G, g, M, k, q, va, vp, mask, ptr_out, logp_out},
+                             {xs, G, g, M, k, q, va, vp, mask, logp_out, logits_out}, {bits, ptr_out}, {}, nullptr, 0, [&] {
+        if (form == TAP_PICK_DRAW && (!state || tap_misaligned(state, 8)))
+            return tap_fail(ctx, TAP_E_INVALID, "pointer pick static: state must be an 8-byte aligned int64[2]");
+        if (xs_env_stride < (size_t)S * (size_t)nR)
+            return tap_fail(ctx, TAP_E_INVALID, "pointer pick static: xs_env_stride %zu below S * nR = %zu", xs_env_stride, (size_t)S * (size_t)nR);
+        return (int)TAP_OK;
+    });
+    if (rc != TAP_OK || B == 0) return rc;
+    const PtrGeom geo = ptr_geom(c);
+    PtrArgsPick a = ptr_args<PtrArgsPick>(c, geo, bits, M, k, q, va, vp);
+    a.xs = xs; a.Gs = G; a.gs = g; a.S = S;
+    a.logits = logits_out;          // may be null; attn and t are not written
+    a.xs_env_stride = xs_env_stride; a.mask = mask;
+    a.state = (const long long *)state; a.step = step; a.env_offset = env_offset;
+    a.ptr = ptr_out; a.logp = logp_out;
+    return form == PTR_GREEDY ? ptr_run<PtrArgsPick, PTR_GREEDY>(ctx, c, geo, a, stream) : ptr_run<PtrArgsPick, PTR_DRAW>(ctx, c, geo, a, stream);
 }

@@ -34,18 +34,13 @@
 // element-to-thread map and the order of every sum are the same on both paths, so the bytes do not depend on the path.
 #include <cmath>
 
+#include "tap_bitshadow.h"
 #include "tap_common.h"
 
 namespace {
 
 constexpr int TR_NW = TAP_BLOCK / 64;
 
-__device__ __forceinline__ double tr_wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v = v + __shfl_xor(v, o);                // every lane ends with the same sum
-    return v;
-}
 // the workgroup's sum of K values per thread: butterflies, then the wavefronts in ascending order; every thread returns
 // with out[k] holding the sums.  red: TR_NW * K doubles of LDS.
 template <int K>
@@ -54,7 +49,7 @@ __device__ __forceinline__ void tr_block_sum(double (&val)[K], double *red)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        val[k] = tr_wave_sum(val[k]);
+        val[k] = tap_wave_sum(val[k]);
         if (lane == 0) red[wave * K + k] = val[k];
     }
     __syncthreads();
@@ -248,14 +243,13 @@ __global__ void __launch_bounds__(TAP_BLOCK) k_clip_adam_apply(const tap_adam_ch
     }
 }
 
-inline bool tr_misaligned(const void *p, unsigned to) { return ((uintptr_t)p & (to - 1)) != 0; }
 
 int ca_check(tap_ctx *ctx, const char *what, const void *table, int chunks, int groups, const void *ranges, const void *steps, const void *part)
 {
     if (chunks < 0 || groups < 0) return tap_fail(ctx, TAP_E_INVALID, "%s: %d chunks, %d groups", what, chunks, groups);
     if (chunks == 0) return TAP_OK;
     if (groups < 1 || !table || !ranges || !steps || !part) return tap_fail(ctx, TAP_E_INVALID, "%s: null buffer or no group", what);
-    if (tr_misaligned(table, 8) || tr_misaligned(ranges, 4) || tr_misaligned(steps, 8) || tr_misaligned(part, 8))
+    if (tap_misaligned(table, 8) || tap_misaligned(ranges, 4) || tap_misaligned(steps, 8) || tap_misaligned(part, 8))
         return tap_fail(ctx, TAP_E_INVALID, "%s: the table, the counters and the partials must be 8-byte aligned", what);
     return TAP_OK;
 }
@@ -281,8 +275,8 @@ extern "C" int tap_reinforce_losses(tap_ctx *ctx, const float *reward, const flo
     if (!scratch || scratch_bytes < need)
         return tap_fail(ctx, TAP_E_INVALID, "reinforce losses: scratch of %zu bytes, %zu needed", scratch ? scratch_bytes : (size_t)0, need);
     const void *f32[] = {reward, critic_est, tour_logp, adv_out, seed_logp_out, seed_est_out, stats_out};
-    bool bad = tr_misaligned(scratch, 8);
-    for (const void *p : f32) bad = bad || tr_misaligned(p, 4);
+    bool bad = tap_misaligned(scratch, 8);
+    for (const void *p : f32) bad = bad || tap_misaligned(p, 4);
     if (bad) return tap_fail(ctx, TAP_E_INVALID, "reinforce losses: the scratch must be 8-byte and the float buffers 4-byte aligned");
     const unsigned blocks = (unsigned)(((size_t)B + TAP_BLOCK - 1) / TAP_BLOCK);
     hipLaunchKernelGGL(k_reinforce_losses, dim3(blocks), dim3(TAP_BLOCK), 0, (hipStream_t)stream, reward, critic_est, tour_logp, B, n,
@@ -309,7 +303,7 @@ extern "C" int tap_clip_adam_apply(tap_ctx *ctx, const tap_adam_chunk *table, in
     const int rc = ca_check(ctx, "clip adam apply", table, chunks, groups, ranges, steps, partials);
     if (rc != TAP_OK || chunks == 0) return rc;
     if (!hyper || !norms_out || !skipped) return tap_fail(ctx, TAP_E_INVALID, "clip adam apply: null buffer");
-    if (tr_misaligned(hyper, 8) || tr_misaligned(norms_out, 4) || tr_misaligned(skipped, 4))
+    if (tap_misaligned(hyper, 8) || tap_misaligned(norms_out, 4) || tap_misaligned(skipped, 4))
         return tap_fail(ctx, TAP_E_INVALID, "clip adam apply: hyper must be 8-byte, norms and skipped 4-byte aligned");
     hipLaunchKernelGGL(k_clip_adam_apply, dim3((unsigned)chunks), dim3(TAP_BLOCK), 0, (hipStream_t)stream, table, ranges, hyper, steps,
                        partials, norms_out, skipped, zero_grads ? 1 : 0);

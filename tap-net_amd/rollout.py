@@ -463,9 +463,7 @@ def encode_dynamic_bits(bits, weight, bias=None, rows=None):
         raise ValueError("no bit shadow / encoder for rows %d, nR %d, H %d (rows <= 128, nR %% 4 == 0, nR <= 256, H <= 1024)" % (rows, nR, H))
     if bias is not None and (tuple(bias.shape) != (H,) or not bias.is_floating_point()):
         raise ValueError("bias must be a floating (%d,) tensor, got %s %s" % (H, bias.dtype, tuple(bias.shape)))
-    dev = _lib.resolve_device(bits.device)
-    if not bits.is_contiguous() or bits.device != dev:
-        bits = bits.to(dev).contiguous()
+    dev, bits = _bits_on_device(bits)
     weight = _prep_f32(weight, dev)
     bias = _prep_f32(bias, dev)
     if torch.is_grad_enabled() and (weight.requires_grad or (bias is not None and bias.requires_grad)):
@@ -478,6 +476,111 @@ def encode_dynamic_bits(bits, weight, bias=None, rows=None):
 def pointer_scores_supported(rows, nR, Hd):
     """whether tap_pointer_scores has a kernel for this shape: a window with a shadow and Hd 64, 128 or 256"""
     return int(Hd) in (64, 128, 256) and _lib.lib().tap_bits_words(int(rows), int(nR)) > 0
+
+
+def _bits_on_device(bits):
+    """-> (the device the launch runs on, the shadow contiguous on it)"""
+    dev = _lib.resolve_device(bits.device)
+    if not bits.is_contiguous() or bits.device != dev:
+        bits = bits.to(dev).contiguous()
+    return dev, bits
+
+
+def _shadow_inputs(bits, name, lead, M, rows, named, blocks=None):
+    """The shared opening of the wrappers on the bit shadow.  ``lead`` gives the batch and the window: ``proj`` (B, 3, nR, Hd)
+    (``name`` "proj"), the pointer's ``xs`` (B, S, nR) or the critic's ``x`` (B, S, nR); ``M`` (3 Hd, rows) -- the critic's
+    (H, rows) -- gives the hidden size and ``rows``; ``named(B, S, nR, Hd)`` lists the other tensors as (name, tensor, the shapes
+    it may have).  -> (B, S, nR, Hd or H, rows); S = 0 for ``proj``.  No device is touched: ``_bits_on_device`` follows, after the
+    caller's own refusals"""
+    if bits.dtype is not torch.int64:
+        raise TypeError("bits must be the int64 shadow (pack.dynamic_bits), got %s" % (bits.dtype,))
+    if name == "proj":
+        if lead.dim() != 4 or int(lead.shape[1]) != 3 or not lead.is_floating_point():
+            raise ValueError("proj must be a floating (B, 3, nR, Hd) tensor, got %s %s" % (lead.dtype, tuple(lead.shape)))
+        (B, _, nR, Hd), S = (int(v) for v in lead.shape), 0
+        m_ok, m_shape = M.dim() == 2 and int(M.shape[0]) == 3 * Hd, "(%d, rows)" % (3 * Hd)
+    else:
+        if lead.dim() != 3 or not lead.is_floating_point():
+            raise ValueError("%s must be a floating (B, S, nR) tensor, got %s %s" % (name, lead.dtype, tuple(lead.shape)))
+        B, S, nR = (int(v) for v in lead.shape)
+        if name == "xs" and not 1 <= S <= 8:
+            raise ValueError("xs has %d static rows; the kernel takes 1 .. 8" % S)
+        seg = 3 if name == "xs" else 1
+        m_ok, m_shape = M.dim() == 2 and int(M.shape[0]) % seg == 0, "(3 Hd, rows)" if seg == 3 else "(H, rows)"
+        Hd = int(M.shape[0]) // seg if m_ok else 0
+    if not m_ok or not M.is_floating_point():
+        raise ValueError("M must be a floating %s tensor, got %s %s" % (m_shape, M.dtype, tuple(M.shape)))
+    rows = int(M.shape[1]) if rows is None else int(rows)
+    if rows != int(M.shape[1]):
+        raise ValueError("M has %d rows' columns, rows is %d" % (int(M.shape[1]), rows))
+    for nm, v, *shapes in named(B, S, nR, Hd):
+        if tuple(v.shape) not in shapes or not v.is_floating_point():
+            raise ValueError("%s must be a floating %s tensor, got %s %s" % (nm, " or ".join(str(s) for s in shapes), v.dtype,
+                                                                           tuple(v.shape)))
+    planes = 2 if rows > 64 else 1
+    bits_ok = bits.dim() in (2, 3) and int(bits.shape[0]) == B and int(math.prod(bits.shape[1:])) == planes * nR and \
+        (bits.dim() == 2 or tuple(bits.shape[1:]) == (planes, nR))
+    # the static-rows forms name a wrong shadow before a shape without a kernel, the other two the other way round
+    if name == "xs" and not bits_ok:
+        raise ValueError("xs of shape %s and bits of shape %s are not (B, S, nR) and the shadow of B envs of a (%d, nR) window"
+                         % (tuple(lead.shape), tuple(bits.shape), rows))
+    if name == "x":
+        if rows < 1 or nR < 1 or not critic_value_supported(rows, nR, Hd, S, blocks):
+            raise ValueError("no critic kernel for rows %d, nR %d, H %d, S %d, blocks %d (rows <= 128, nR %% 4 == 0, nR <= 256, "
+                             "H 64 / 128 / 256, S 1..8, blocks 1..8)" % (rows, nR, Hd, S, blocks))
+    elif rows < 1 or nR < 1 or not pointer_scores_supported(rows, nR, Hd):   # (S is 1 .. 8 or the proj form's 0 here)
+        raise ValueError("no pointer kernel for rows %d, nR %d, Hd %d%s (rows <= 128, nR %% 4 == 0, nR <= 256, Hd 64 / 128 / 256%s)"
+                         % ((rows, nR, Hd) + ((", S %d" % S, ", S <= 8") if S else ("", ""))))
+    if not bits_ok:
+        raise ValueError("bits of shape %s is not the shadow of %d envs of a (%d, %d) window" % (tuple(bits.shape), B, rows, nR))
+    return B, S, nR, Hd, rows
+
+
+def _scores_outputs(B, nR, Hd, dev):
+    """logits (B, nR), attn (B, nR), t (B, Hd): what the pointer's forward launches write"""
+    f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    return f(B, nR), f(B, nR), f(B, Hd)
+
+
+def _backward_on_bits(bits, rows, dU, dM, dk, need, launch):
+    """The second half of the backwards on the bit shadow: ``launch(ctx, scratch pointer, need, stream)`` is the kernel's own
+    backward, which writes dU (B, X, nR) with ``need`` bytes of scratch; then tap_encode_bits_backward on dU, the encoder's backward
+    with H = X: dM[x, r] = sum over (b, c) of dU[b, x, c] bit[b, r, c], dk[x] = sum of dU.  One scratch serves both."""
+    B, X, nR = (int(v) for v in dU.shape)
+    dev = dU.device
+    L, c, st = _lib.lib(), _lib.ctx(dev), _lib.stream_of(dev)
+    need2 = int(L.tap_encode_bits_backward_scratch(B, nR, rows, X))
+    scratch = torch.empty(max(need, need2, 16) // 4, dtype=torch.float32, device=dev)
+    _lib.check(launch(c, _lib.ptr(scratch), need, st), c)
+    _lib.check(L.tap_encode_bits_backward(c, _lib.ptr(bits), _lib.ptr(dU), B, nR, rows, X, _lib.ptr(dM), _lib.ptr(dk),
+                                          _lib.ptr(scratch), need2, st), c)
+
+
+def _pointer_backward(lead, static, bits, M, k, q, va, vp, attn, t, g, rows):
+    """The pointer's backward for both forms: ``static`` None -- ``lead`` is proj, tap_pointer_scores_backward -- or (G, g) --
+    ``lead`` is xs, tap_pointer_scores_static_backward --, then ``_backward_on_bits``.  -> dU (B, 3 Hd, nR), dq, dva, dvp, dM, dk;
+    an empty batch gives zeros for the parameters' gradients"""
+    B, nR, Hd = int(lead.shape[0]), int(attn.shape[1]), int(q.shape[1])
+    dev = lead.device
+    p, L = _lib.ptr, _lib.lib()
+    f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    dU, dq, dva, dvp, dM, dk = f(B, 3 * Hd, nR), f(B, Hd), f(Hd), f(Hd), f(3 * Hd, rows), f(3 * Hd)
+    if B == 0:
+        for z in (dva, dvp, dM, dk):
+            z.zero_()
+        return dU, dq, dva, dvp, dM, dk
+    g = _prep_f32(g, dev)
+    common = (p(M), p(k), p(q), p(va), p(vp), p(attn), p(t), p(g), p(dU), p(dq), p(dva), p(dvp))
+    if static is None:
+        need = int(L.tap_pointer_scores_backward_scratch(B, nR, rows, Hd))
+        launch = lambda c, scratch, n, st: L.tap_pointer_scores_backward(c, p(lead), p(bits), B, nR, rows, Hd, *common, scratch, n, st)
+    else:
+        S = int(lead.shape[1])
+        need = int(L.tap_pointer_scores_static_backward_scratch(B, nR, rows, Hd, S))
+        launch = lambda c, scratch, n, st: L.tap_pointer_scores_static_backward(c, p(lead), p(bits), B, nR, rows, Hd, S, p(static[0]),
+                                                                                p(static[1]), *common, scratch, n, st)
+    _backward_on_bits(bits, rows, dU, dM, dk, need, launch)
+    return dU, dq, dva, dvp, dM, dk
 
 
 def _scores_into(proj, bits, M, k, q, va, vp, rows, logits, attn, t):
@@ -499,10 +602,7 @@ class _PointerScores(torch.autograd.Function):
     @staticmethod
     def forward(ctx, proj, bits, M, k, q, va, vp, rows):
         B, _, nR, Hd = (int(v) for v in proj.shape)
-        dev = proj.device
-        logits = torch.empty(B, nR, dtype=torch.float32, device=dev)
-        attn = torch.empty(B, nR, dtype=torch.float32, device=dev)
-        t = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+        logits, attn, t = _scores_outputs(B, nR, Hd, proj.device)
         _scores_into(proj, bits, M, k, q, va, vp, rows, logits, attn, t)
         ctx.save_for_backward(proj, bits.clone(), M, k, q, va, vp, attn, t)
         ctx.rows = rows
@@ -511,34 +611,11 @@ class _PointerScores(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        proj, bits, M, k, q, va, vp, attn, t = ctx.saved_tensors
-        B, _, nR, Hd = (int(v) for v in proj.shape)
-        rows, dev = ctx.rows, proj.device
-        L, c = _lib.lib(), _lib.ctx(dev)
-        dva = torch.empty(Hd, dtype=torch.float32, device=dev)
-        dvp = torch.empty(Hd, dtype=torch.float32, device=dev)
-        dM = torch.empty(3 * Hd, rows, dtype=torch.float32, device=dev)
-        dk = torch.empty(3 * Hd, dtype=torch.float32, device=dev)
-        dU = torch.empty(B, 3 * Hd, nR, dtype=torch.float32, device=dev)
-        dq = torch.empty(B, Hd, dtype=torch.float32, device=dev)
-        if B == 0:
-            for z in (dva, dvp, dM, dk):
-                z.zero_()
-            return dU.view(B, 3, Hd, nR).transpose(2, 3), None, dM, dk, dq, dva, dvp, None
-        g = _prep_f32(g, dev)
-        need = int(L.tap_pointer_scores_backward_scratch(B, nR, rows, Hd))
-        need2 = int(L.tap_encode_bits_backward_scratch(B, nR, rows, 3 * Hd))
-        scratch = torch.empty(max(need, need2, 16) // 4, dtype=torch.float32, device=dev)
-        st = _lib.stream_of(dev)
-        _lib.check(L.tap_pointer_scores_backward(c, _lib.ptr(proj), _lib.ptr(bits), B, nR, rows, Hd, _lib.ptr(M), _lib.ptr(k),
-                                                 _lib.ptr(q), _lib.ptr(va), _lib.ptr(vp), _lib.ptr(attn), _lib.ptr(t), _lib.ptr(g),
-                                                 _lib.ptr(dU), _lib.ptr(dq), _lib.ptr(dva), _lib.ptr(dvp), _lib.ptr(scratch), need,
-                                                 st), c)
-        # dM[x, r] = sum over (b, c) of dU[b, x, c] bit[b, r, c], dk[x] = sum of dU: the encoder's backward with H = 3 Hd
-        _lib.check(L.tap_encode_bits_backward(c, _lib.ptr(bits), _lib.ptr(dU), B, nR, rows, 3 * Hd, _lib.ptr(dM), _lib.ptr(dk),
-                                              _lib.ptr(scratch), need2, st), c)
+        proj, bits, *rest = ctx.saved_tensors
+        dU, dq, dva, dvp, dM, dk = _pointer_backward(proj, None, bits, *rest, g, ctx.rows)
+        B, Hd3, nR = dU.shape
         # dproj is dU read in proj's layout (B, 3, nR, Hd): a view, not a copy
-        return dU.view(B, 3, Hd, nR).transpose(2, 3), None, dM, dk, dq, dva, dvp, None
+        return dU.view(B, 3, Hd3 // 3, nR).transpose(2, 3), None, dM, dk, dq, dva, dvp, None
 
 
 def pointer_scores(proj, bits, M, k, q, va, vp, rows=None):
@@ -555,36 +632,14 @@ def pointer_scores(proj, bits, M, k, q, va, vp, rows=None):
     through a ``torch.autograd.Function`` whose backward is tap_pointer_scores_backward + tap_encode_bits_backward
     (deterministic: no atomics); per step it keeps a clone of ``bits``, ``attn`` (B, nR), ``t`` and ``q`` (B, Hd).  A shape
     without a kernel (``pointer_scores_supported``) raises ValueError."""
-    if bits.dtype is not torch.int64:
-        raise TypeError("bits must be the int64 shadow (pack.dynamic_bits), got %s" % (bits.dtype,))
-    if proj.dim() != 4 or int(proj.shape[1]) != 3 or not proj.is_floating_point():
-        raise ValueError("proj must be a floating (B, 3, nR, Hd) tensor, got %s %s" % (proj.dtype, tuple(proj.shape)))
-    B, _, nR, Hd = (int(v) for v in proj.shape)
-    if M.dim() != 2 or int(M.shape[0]) != 3 * Hd or not M.is_floating_point():
-        raise ValueError("M must be a floating (%d, rows) tensor, got %s %s" % (3 * Hd, M.dtype, tuple(M.shape)))
-    rows = int(M.shape[1]) if rows is None else int(rows)
-    if rows != int(M.shape[1]):
-        raise ValueError("M has %d rows' columns, rows is %d" % (int(M.shape[1]), rows))
-    for name, v, shape in (("k", k, (3 * Hd,)), ("q", q, (B, Hd)), ("va", va, (Hd,)), ("vp", vp, (Hd,))):
-        if tuple(v.shape) != shape or not v.is_floating_point():
-            raise ValueError("%s must be a floating %s tensor, got %s %s" % (name, shape, v.dtype, tuple(v.shape)))
-    planes = 2 if rows > 64 else 1
-    if rows < 1 or nR < 1 or not pointer_scores_supported(rows, nR, Hd):
-        raise ValueError("no pointer kernel for rows %d, nR %d, Hd %d (rows <= 128, nR %% 4 == 0, nR <= 256, Hd 64 / 128 / 256)"
-                         % (rows, nR, Hd))
-    if bits.dim() not in (2, 3) or int(bits.shape[0]) != B or int(math.prod(bits.shape[1:])) != planes * nR or \
-            (bits.dim() == 3 and tuple(bits.shape[1:]) != (planes, nR)):
-        raise ValueError("bits of shape %s is not the shadow of %d envs of a (%d, %d) window" % (tuple(bits.shape), B, rows, nR))
-    dev = _lib.resolve_device(bits.device)
-    if not bits.is_contiguous() or bits.device != dev:
-        bits = bits.to(dev).contiguous()
+    B, _, nR, Hd, rows = _shadow_inputs(bits, "proj", proj, M, rows, lambda B, S, nR, Hd: (
+        ("k", k, (3 * Hd,)), ("q", q, (B, Hd)), ("va", va, (Hd,)), ("vp", vp, (Hd,))))
+    dev, bits = _bits_on_device(bits)
     args = [_prep_f32(v, dev) for v in (proj, M, k, q, va, vp)]
     if torch.is_grad_enabled() and any(v.requires_grad for v in args):
         return _PointerScores.apply(args[0], bits, *args[1:], rows)
     proj, M, k, q, va, vp = (v.detach() for v in args)
-    logits = torch.empty(B, nR, dtype=torch.float32, device=dev)
-    attn = torch.empty(B, nR, dtype=torch.float32, device=dev)
-    t = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+    logits, attn, t = _scores_outputs(B, nR, Hd, dev)
     _scores_into(proj, bits, M, k, q, va, vp, rows, logits, attn, t)
     return logits
 
@@ -592,6 +647,12 @@ def pointer_scores(proj, bits, M, k, q, va, vp, rows=None):
 def pointer_scores_static_supported(rows, nR, Hd, S):
     """whether tap_pointer_scores_static has a kernel for this shape: ``pointer_scores_supported`` and 1 <= S <= 8 static rows"""
     return 1 <= int(S) <= 8 and pointer_scores_supported(rows, nR, Hd)
+
+
+def _static_named(G, g, k, q, va, vp, *more):
+    """the named shapes of the static-rows forms, for ``_shadow_inputs``; ``more``: (name, tensor) pairs of shape (B, nR)"""
+    return lambda B, S, nR, Hd: (("G", G, (3 * Hd, S)), ("g", g, (3 * Hd,)), ("k", k, (3 * Hd,)), ("q", q, (B, Hd)), ("va", va, (Hd,)),
+                                 ("vp", vp, (Hd,))) + tuple((nm, v, (B, nR)) for nm, v in more)
 
 
 def _scores_static_into(xs, bits, G, g, M, k, q, va, vp, rows, logits, attn, t):
@@ -614,10 +675,7 @@ class _PointerScoresStatic(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xs, bits, G, g, M, k, q, va, vp, rows):
         B, S, nR = (int(v) for v in xs.shape)
-        Hd, dev = int(q.shape[1]), xs.device
-        logits = torch.empty(B, nR, dtype=torch.float32, device=dev)
-        attn = torch.empty(B, nR, dtype=torch.float32, device=dev)
-        t = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+        logits, attn, t = _scores_outputs(B, nR, int(q.shape[1]), xs.device)
         _scores_static_into(xs, bits, G, g, M, k, q, va, vp, rows, logits, attn, t)
         ctx.save_for_backward(xs, bits.clone(), G, g, M, k, q, va, vp, attn, t)
         ctx.rows = rows
@@ -626,30 +684,9 @@ class _PointerScoresStatic(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad):
-        xs, bits, G, g, M, k, q, va, vp, attn, t = ctx.saved_tensors
-        B, S, nR = (int(v) for v in xs.shape)
-        Hd, rows, dev = int(q.shape[1]), ctx.rows, xs.device
-        L, c = _lib.lib(), _lib.ctx(dev)
-        f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
-        dva, dvp, dM, dk, dq = f(Hd), f(Hd), f(3 * Hd, rows), f(3 * Hd), f(B, Hd)
-        if B == 0:
-            for z in (dva, dvp, dM, dk):
-                z.zero_()
-            return None, None, torch.zeros_like(G), dk, dM, dk.clone(), dq, dva, dvp, None
-        grad = _prep_f32(grad, dev)
-        dU = f(B, 3 * Hd, nR)
-        need = int(L.tap_pointer_scores_static_backward_scratch(B, nR, rows, Hd, S))
-        need2 = int(L.tap_encode_bits_backward_scratch(B, nR, rows, 3 * Hd))
-        scratch = f(max(need, need2, 16) // 4)
-        st = _lib.stream_of(dev)
-        _lib.check(L.tap_pointer_scores_static_backward(c, _lib.ptr(xs), _lib.ptr(bits), B, nR, rows, Hd, S, _lib.ptr(G), _lib.ptr(g),
-                                                        _lib.ptr(M), _lib.ptr(k), _lib.ptr(q), _lib.ptr(va), _lib.ptr(vp),
-                                                        _lib.ptr(attn), _lib.ptr(t), _lib.ptr(grad), _lib.ptr(dU), _lib.ptr(dq),
-                                                        _lib.ptr(dva), _lib.ptr(dvp), _lib.ptr(scratch), need, st), c)
-        # dM[x, r] = sum over (b, c) of dU[b, x, c] bit[b, r, c], dk[x] = dg[x] = sum of dU: the encoder's backward with H = 3 Hd
-        _lib.check(L.tap_encode_bits_backward(c, _lib.ptr(bits), _lib.ptr(dU), B, nR, rows, 3 * Hd, _lib.ptr(dM), _lib.ptr(dk),
-                                              _lib.ptr(scratch), need2, st), c)
-        # dG = sum_b dU[b] xs[b]^T: one batched product that reads dU once, then the batch sum of (B, 3 Hd, S)
+        xs, bits, G, g, *rest = ctx.saved_tensors
+        dU, dq, dva, dvp, dM, dk = _pointer_backward(xs, (G, g), bits, *rest, grad, ctx.rows)
+        # dG = sum_b dU[b] xs[b]^T: one batched product that reads dU once, then the batch sum of (B, 3 Hd, S); dk[x] = dg[x]
         dG = torch.bmm(dU, xs.transpose(1, 2)).sum(0)
         return None, None, dG, dk, dM, dk.clone(), dq, dva, dvp, None
 
@@ -666,42 +703,14 @@ def pointer_scores_static(xs, bits, G, g, M, k, q, va, vp, rows=None):
     tap_encode_bits_backward and one batched product for dG (deterministic: no atomics); per step it keeps a clone of
     ``bits``, ``attn`` (B, nR), ``t`` and ``q`` (B, Hd), and ``xs`` by reference.  ``xs`` and ``bits`` get no gradient.  A
     shape without a kernel (``pointer_scores_static_supported``) raises ValueError."""
-    if bits.dtype is not torch.int64:
-        raise TypeError("bits must be the int64 shadow (pack.dynamic_bits), got %s" % (bits.dtype,))
-    if xs.dim() != 3 or not xs.is_floating_point():
-        raise ValueError("xs must be a floating (B, S, nR) tensor, got %s %s" % (xs.dtype, tuple(xs.shape)))
-    B, S, nR = (int(v) for v in xs.shape)
-    if not 1 <= S <= 8:
-        raise ValueError("xs has %d static rows; the kernel takes 1 .. 8" % S)
-    if M.dim() != 2 or int(M.shape[0]) % 3 or not M.is_floating_point():
-        raise ValueError("M must be a floating (3 Hd, rows) tensor, got %s %s" % (M.dtype, tuple(M.shape)))
-    Hd = int(M.shape[0]) // 3
-    rows = int(M.shape[1]) if rows is None else int(rows)
-    if rows != int(M.shape[1]):
-        raise ValueError("M has %d rows' columns, rows is %d" % (int(M.shape[1]), rows))
-    for name, v, shape in (("G", G, (3 * Hd, S)), ("g", g, (3 * Hd,)), ("k", k, (3 * Hd,)), ("q", q, (B, Hd)), ("va", va, (Hd,)),
-                           ("vp", vp, (Hd,))):
-        if tuple(v.shape) != shape or not v.is_floating_point():
-            raise ValueError("%s must be a floating %s tensor, got %s %s" % (name, shape, v.dtype, tuple(v.shape)))
-    planes = 2 if rows > 64 else 1
-    if bits.dim() not in (2, 3) or int(bits.shape[0]) != B or int(math.prod(bits.shape[1:])) != planes * nR or \
-            (bits.dim() == 3 and tuple(bits.shape[1:]) != (planes, nR)):
-        raise ValueError("xs of shape %s and bits of shape %s are not (B, S, nR) and the shadow of B envs of a (%d, nR) window"
-                         % (tuple(xs.shape), tuple(bits.shape), rows))
-    if rows < 1 or nR < 1 or not pointer_scores_static_supported(rows, nR, Hd, S):
-        raise ValueError("no pointer kernel for rows %d, nR %d, Hd %d, S %d (rows <= 128, nR %% 4 == 0, nR <= 256, Hd 64 / 128 / 256, "
-                         "S <= 8)" % (rows, nR, Hd, S))
-    dev = _lib.resolve_device(bits.device)
-    if not bits.is_contiguous() or bits.device != dev:
-        bits = bits.to(dev).contiguous()
+    B, S, nR, Hd, rows = _shadow_inputs(bits, "xs", xs, M, rows, _static_named(G, g, k, q, va, vp))
+    dev, bits = _bits_on_device(bits)
     xs = _prep_f32(xs.detach(), dev)
     args = [_prep_f32(v, dev) for v in (G, g, M, k, q, va, vp)]
     if torch.is_grad_enabled() and any(v.requires_grad for v in args):
         return _PointerScoresStatic.apply(xs, bits, *args, rows)
     args = [v.detach() for v in args]
-    logits = torch.empty(B, nR, dtype=torch.float32, device=dev)
-    attn = torch.empty(B, nR, dtype=torch.float32, device=dev)
-    t = torch.empty(B, Hd, dtype=torch.float32, device=dev)
+    logits, attn, t = _scores_outputs(B, nR, Hd, dev)
     _scores_static_into(xs, bits, *args, rows, logits, attn, t)
     return logits
 
@@ -752,38 +761,12 @@ def pointer_pick_static(xs, bits, G, g, M, k, q, va, vp, mask, source=None, rows
     The other arguments as ``pointer_scores_static`` takes them.  No autograd: with grad enabled, an input that requires grad
     raises ValueError (use ``pointer_scores_static`` and the head).  A shape without a kernel
     (``pointer_pick_static_supported``) raises ValueError."""
-    if bits.dtype is not torch.int64:
-        raise TypeError("bits must be the int64 shadow (pack.dynamic_bits), got %s" % (bits.dtype,))
-    if xs.dim() != 3 or not xs.is_floating_point():
-        raise ValueError("xs must be a floating (B, S, nR) tensor, got %s %s" % (xs.dtype, tuple(xs.shape)))
-    B, S, nR = (int(v) for v in xs.shape)
-    if not 1 <= S <= 8:
-        raise ValueError("xs has %d static rows; the kernel takes 1 .. 8" % S)
-    if M.dim() != 2 or int(M.shape[0]) % 3 or not M.is_floating_point():
-        raise ValueError("M must be a floating (3 Hd, rows) tensor, got %s %s" % (M.dtype, tuple(M.shape)))
-    Hd = int(M.shape[0]) // 3
-    rows = int(M.shape[1]) if rows is None else int(rows)
-    if rows != int(M.shape[1]):
-        raise ValueError("M has %d rows' columns, rows is %d" % (int(M.shape[1]), rows))
-    for name, v, shape in (("G", G, (3 * Hd, S)), ("g", g, (3 * Hd,)), ("k", k, (3 * Hd,)), ("q", q, (B, Hd)), ("va", va, (Hd,)),
-                           ("vp", vp, (Hd,)), ("mask", mask, (B, nR))):
-        if tuple(v.shape) != shape or not v.is_floating_point():
-            raise ValueError("%s must be a floating %s tensor, got %s %s" % (name, shape, v.dtype, tuple(v.shape)))
-    planes = 2 if rows > 64 else 1
-    if bits.dim() not in (2, 3) or int(bits.shape[0]) != B or int(math.prod(bits.shape[1:])) != planes * nR or \
-            (bits.dim() == 3 and tuple(bits.shape[1:]) != (planes, nR)):
-        raise ValueError("xs of shape %s and bits of shape %s are not (B, S, nR) and the shadow of B envs of a (%d, nR) window"
-                         % (tuple(xs.shape), tuple(bits.shape), rows))
-    if rows < 1 or nR < 1 or not pointer_pick_static_supported(rows, nR, Hd, S):
-        raise ValueError("no pointer kernel for rows %d, nR %d, Hd %d, S %d (rows <= 128, nR %% 4 == 0, nR <= 256, Hd 64 / 128 / 256, "
-                         "S <= 8)" % (rows, nR, Hd, S))
+    B, S, nR, Hd, rows = _shadow_inputs(bits, "xs", xs, M, rows, _static_named(G, g, k, q, va, vp, ("mask", mask)))
     if torch.is_grad_enabled() and any(v.requires_grad for v in (xs, G, g, M, k, q, va, vp, mask)):
         raise ValueError("pointer_pick_static has no backward: call it under torch.no_grad(), or use pointer_scores_static and "
                          "pointer_pick")
     rec = None if source is None else _pick_record(source)
-    dev = _lib.resolve_device(bits.device)
-    if not bits.is_contiguous() or bits.device != dev:
-        bits = bits.to(dev).contiguous()
+    dev, bits = _bits_on_device(bits)
     xs = xs.detach()
     stride = _rows_view_stride(xs) if xs.dtype is torch.float32 and xs.device == dev else None
     if stride is None:
@@ -845,7 +828,7 @@ class _CriticValue(torch.autograd.Function):
         x, bits, G, g, M, v, w2, z, p, xbar, q = ctx.saved_tensors
         B, S, nR, H, n, rows, q0_rows = ctx.dims
         dev = x.device
-        L, c = _lib.lib(), _lib.ctx(dev)
+        L, P = _lib.lib(), _lib.ptr
         f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
         if B == 0:
             zero = lambda t: torch.zeros_like(t)
@@ -854,16 +837,10 @@ class _CriticValue(torch.autograd.Function):
         relu = z.clamp_min(0)
         dz = gv.unsqueeze(1) * w2.unsqueeze(0) * (z > 0).to(torch.float32)
         dU, dq, dv, dM, dk = f(B, H, nR), f(B, n, H), f(H), f(H, rows), f(H)
-        need = int(L.tap_critic_value_backward_scratch(B, nR, rows, H, S, n))
-        need2 = int(L.tap_encode_bits_backward_scratch(B, nR, rows, H))
-        scratch = f(max(need, need2, 16) // 4)
-        st = _lib.stream_of(dev)
-        _lib.check(L.tap_critic_value_backward(c, _lib.ptr(x), _lib.ptr(bits), B, nR, rows, H, S, n, _lib.ptr(G), _lib.ptr(g),
-                                               _lib.ptr(M), _lib.ptr(v), _lib.ptr(q), _lib.ptr(p), _lib.ptr(dz), _lib.ptr(dU),
-                                               _lib.ptr(dq), _lib.ptr(dv), _lib.ptr(scratch), need, st), c)
-        # dM[j, r] = sum over (b, c) of dU[b, j, c] bit[b, r, c], dk[j] = sum of dU: the encoder's backward
-        _lib.check(L.tap_encode_bits_backward(c, _lib.ptr(bits), _lib.ptr(dU), B, nR, rows, H, _lib.ptr(dM), _lib.ptr(dk),
-                                              _lib.ptr(scratch), need2, st), c)
+        _backward_on_bits(bits, rows, dU, dM, dk, int(L.tap_critic_value_backward_scratch(B, nR, rows, H, S, n)),
+                          lambda c, scratch, need, st: L.tap_critic_value_backward(
+                              c, P(x), P(bits), B, nR, rows, H, S, n, P(G), P(g), P(M), P(v), P(q), P(p), P(dz), P(dU), P(dq), P(dv),
+                              scratch, need, st))
         dq1 = dq[:, 1:].reshape(-1, H)
         # dG0 = sum_b dU[b] x[b]^T: one batched product that reads dU once, then the batch sum of (B, H, S)
         dG = torch.cat((torch.bmm(dU, x.transpose(1, 2)).sum(0), dq1.t().matmul(xbar[:, :-1].reshape(-1, S)),
@@ -888,37 +865,15 @@ def critic_value(x, bits, G, g, M, q0, v, w2, b2, blocks, rows=None):
     tap_critic_value_backward + tap_encode_bits_backward (deterministic: no atomics); it keeps a clone of ``bits``, ``x``
     by reference, and z (B, H), p (B, blocks, nR), xbar (B, blocks, S), q (B, blocks, H).  ``x`` and ``bits`` get no
     gradient.  A shape without a kernel (``critic_value_supported``) raises ValueError."""
-    if bits.dtype is not torch.int64:
-        raise TypeError("bits must be the int64 shadow (pack.dynamic_bits), got %s" % (bits.dtype,))
-    if x.dim() != 3 or not x.is_floating_point():
-        raise ValueError("x must be a floating (B, S, nR) tensor, got %s %s" % (x.dtype, tuple(x.shape)))
-    B, S, nR = (int(d) for d in x.shape)
-    if M.dim() != 2 or not M.is_floating_point():
-        raise ValueError("M must be a floating (H, rows) tensor, got %s %s" % (M.dtype, tuple(M.shape)))
-    H = int(M.shape[0])
-    rows = int(M.shape[1]) if rows is None else int(rows)
-    if rows != int(M.shape[1]):
-        raise ValueError("M has %d rows' columns, rows is %d" % (int(M.shape[1]), rows))
     blocks = int(blocks)
     if q0.dim() == 1:
         q0 = q0.unsqueeze(0)
     if b2.dim() == 0:
         b2 = b2.reshape(1)
-    for name, t, shapes in (("G", G, ((3 * H, S),)), ("g", g, ((3 * H,),)), ("q0", q0, ((B, H), (1, H))), ("v", v, ((H,),)),
-                            ("w2", w2, ((H,),)), ("b2", b2, ((1,),))):
-        if tuple(t.shape) not in shapes or not t.is_floating_point():
-            raise ValueError("%s must be a floating %s tensor, got %s %s" % (name, " or ".join(str(s) for s in shapes), t.dtype,
-                                                                           tuple(t.shape)))
-    planes = 2 if rows > 64 else 1
-    if rows < 1 or nR < 1 or not critic_value_supported(rows, nR, H, S, blocks):
-        raise ValueError("no critic kernel for rows %d, nR %d, H %d, S %d, blocks %d (rows <= 128, nR %% 4 == 0, nR <= 256, "
-                         "H 64 / 128 / 256, S 1..8, blocks 1..8)" % (rows, nR, H, S, blocks))
-    if bits.dim() not in (2, 3) or int(bits.shape[0]) != B or int(math.prod(bits.shape[1:])) != planes * nR or \
-            (bits.dim() == 3 and tuple(bits.shape[1:]) != (planes, nR)):
-        raise ValueError("bits of shape %s is not the shadow of %d envs of a (%d, %d) window" % (tuple(bits.shape), B, rows, nR))
-    dev = _lib.resolve_device(bits.device)
-    if not bits.is_contiguous() or bits.device != dev:
-        bits = bits.to(dev).contiguous()
+    B, S, nR, H, rows = _shadow_inputs(bits, "x", x, M, rows, lambda B, S, nR, H: (
+        ("G", G, (3 * H, S)), ("g", g, (3 * H,)), ("q0", q0, (B, H), (1, H)), ("v", v, (H,)), ("w2", w2, (H,)), ("b2", b2, (1,))),
+        blocks)
+    dev, bits = _bits_on_device(bits)
     x = _prep_f32(x.detach(), dev)
     args = [_prep_f32(t, dev) for t in (G, g, M, q0, v, w2, b2)]
     if torch.is_grad_enabled() and any(t.requires_grad for t in args):
