@@ -104,7 +104,7 @@ const char *tap_last_error(const tap_ctx *ctx);
  * hipGraph counts once, at capture.  tap_variant_hits writes up to `cap` rows of 8 ints (the key, then the count) and
  * returns the number of rows the record holds (TAP_E_INVALID if a key found no slot since the last reset);
  * tap_variant_hits_reset empties it. */
-/* The whole-episode and rolling kernels count on the same record, under kinds 16 .. 32 (tap_common.h: TapHitKind; 25: trial.hip, 26: policy.hip, 27: encode.hip, 28: pointer.hip, 29: decoder.hip, 30: heightmap.hip, 31: critic.hip, 32: pack_rnn.hip), after
+/* The whole-episode and rolling kernels count on the same record, under kinds 16 .. 33 (tap_common.h: TapHitKind; 25: trial.hip, 26: policy.hip, 27: encode.hip, 28: pointer.hip, 29: decoder.hip, 30: heightmap.hip, 31: critic.hip, 32: pack_rnn.hip, 33: dqn.hip), after
  * the stream-wave kinds 0 .. 6.  Their keys, fields (kind, D, G, nc, mode, extra, wt):
  *   16 k_episode<D, G, SOFT>                      (16, D, G, SOFT, 0, 0, 0)
  *   17 k_episode_macs2<G, WIDE>                   (17, 2, G, WIDE, 0, 0, 0)
@@ -133,6 +133,7 @@ const char *tap_last_error(const tap_ctx *ctx);
  *   31 k_critic_value<HPL>                        (31, RES, HPL, PLANES, MALL, 0, 0) HPL = H / 64 hidden rows per lane, RES 1 = U resident in LDS (0: recomputed per block), MALL 1 = all of M staged (0: a 64-row slab at a time)
  *      k_critic_value_bw<HPL> + _bw_reduce        (31, RES, HPL, PLANES, MALL, 1, 0) RES 1 = dU accumulated in LDS (0: in dU_out) (one count per call)
  *   32 k_pack_rnn_forward<KIND>                   (32, 2, TE, KIND, CHUNKS, 0, 0) TE = 16 envs per workgroup, KIND 0 = G, 1 = LG (TAP_PACK_*), CHUNKS = D / 64 = 4 | 6
+ *   33 k_dqn_pick<TE>                             (33, 2, TE, DIFF, P, 0, 0)     TE = 16 | 8 envs per workgroup, DIFF 1 = the map's last entry is dropped, P = Wm + 2 positions
  * wt is the launch's RollArgs::wt (the window's fp32 stores; the init kernels store none), 0 for the episode kernels. */
 int tap_variant_hits(tap_ctx *ctx, int32_t *out, int cap);
 int tap_variant_hits_reset(tap_ctx *ctx);
@@ -1048,6 +1049,50 @@ typedef struct tap_pack_rnn_weights {
 int tap_pack_rnn_forward(tap_ctx *ctx, const tap_env_desc *d, void *state, const float *blocks, int T, int blocks_num,
                          int max_blocks, const tap_pack_rnn_weights *w, float *logp_out, float *reward_out,
                          float *feature_out /* or NULL */, void *stream);
+
+/* ---- the local pack-net's pick, one launch ---------------------------------------------------- */
+/* tools.DQN.forward (tools.py:3322-3367) in its eval form, then the pick, for B envs: pnet + block -> the column, the log of
+ * its probability and optionally the probabilities.  Notation: W columns, Wm = W - 1 map entries when the net drops the
+ * map's last one (is_diff_height) else W, P = Wm + 2 positions along the conv axis (the map's entries, then the block's two
+ * sides).
+ * Folds (the caller's, in torch, once; tools.DQN.fold; they add no parameter), with s_i = bn_i.weight / sqrt(bn_i.running_var
+ * + bn_i.eps):
+ *   c1 (128, 4): per channel (a_m, b_m, a_b, b_b), a_m = s1 conv_height_map.weight, b_m = s1 (conv_height_map.bias - mean1)
+ *      + bn1.bias, (a_b, b_b) the same from conv_block
+ *   W2 (256, 128) = s2[:, None] conv2.weight, b2 = s2 (conv2.bias - mean2) + bn2.bias; W3 (256, 256), b3 likewise
+ *   L1 (512, 256 P) = lin1.weight with its columns re-laid position-major (k = p 256 + c; the reference's flatten is c P + p)
+ *   l1b = lin1.bias, head_w (W, 512), head_b (W,) unchanged
+ * W2, W3 and L1 are handed over in the matrix cores' operand order, four steps of a lane together (T = 32, KS = 2 for W2 / W3;
+ * T = 16, KS = 4 for L1; lane l < 64, i < 4):  Xp[q][tile][l][i] = X[tile T + l % T][KS (4 q + i) + l / T].
+ * Per env b, fp32 unless said otherwise; every sum is ONE chain of fmaf in ascending term order from the bias (the f32-input
+ * MFMA is bit for bit that chain):
+ *   x_p = pnet[b pnet_stride + p] for p < Wm (the diff form's trailing entry is never read), block[b block_stride + p - Wm]
+ *         for the last two positions
+ *   h1[p][c] = max(0, fmaf(a[c], x_p, b[c])), the map's or the block's coefficients by position
+ *   h2[p][o] = max(0, chain over c < 128 from b2[o]); h3[p][o] = max(0, chain over c < 256 of h2 from b3[o])
+ *   y[o] = max(0, chain over k = p 256 + c from l1b[o]); l[c] = chain over the 512 terms of y from head_b[c]
+ *   m = max l; x_out[b] = the first c with l_c == m; s = sum_c exp((double)(l_c - m)), ascending, fp64;
+ *   logp_out[b] = (float)(-log(s)); probs_out[b, c] = (float)(exp((double)(l_c - m)) / s) when probs_out is given.
+ * No split-K, no atomics, nothing crosses an env: two calls give the same bytes, and an env's bytes do not depend on B or on
+ * its place in a tile.  One launch, no allocation, no host read, no stream synchronisation (capturable in a hipGraph).
+ * k_dqn_pick<TE> (dqn.hip): a workgroup takes TE = 16 envs up to P = 7 and 8 up to P = 14; launch record key
+ * (33, 2, TE, DIFF, P, 0, 0).  tap_dqn_pick_geometry (host only, no context) -> out[0] = TE, out[1] = P, out[2] = bytes of
+ * dynamic LDS, or TAP_E_UNSUPPORTED.
+ * Shapes: W >= 2 and P <= 14 (every W up to 12, and 13 in the diff form); anything else -> TAP_E_UNSUPPORTED.  Checks, in
+ * tap_pack_rnn_forward's order: null weights, B < 0, or weights whose Wm is neither W nor W - 1 or whose P is not Wm + 2 ->
+ * TAP_E_INVALID; B == 0 -> TAP_OK; a null required buffer, or an env stride below Wm / 2 floats -> TAP_E_INVALID; a shape
+ * outside the list -> TAP_E_UNSUPPORTED; a weight buffer that is not 16-byte aligned, an x_out that is not 8-byte aligned or
+ * another buffer that is not 4-byte aligned -> TAP_E_INVALID. */
+typedef struct tap_dqn_weights {
+    int32_t W, Wm, P, reserved;
+    const float *c1;                    /* (128, 4) */
+    const float *W2p, *b2, *W3p, *b3;   /* (16, 8, 64, 4), (256,), (32, 8, 64, 4), (256,) */
+    const float *L1p, *l1b;             /* (16 P, 32, 64, 4), (512,) */
+    const float *head_w, *head_b;       /* (W, 512), (W,) */
+} tap_dqn_weights;
+int tap_dqn_pick(tap_ctx *ctx, const tap_dqn_weights *w, const float *pnet, int pnet_stride, const float *block,
+                 int block_stride, int B, int64_t *x_out, float *logp_out, float *probs_out /* or NULL */, void *stream);
+int tap_dqn_pick_geometry(int W, int Wm, int32_t *out /* 3 ints, or NULL */);
 
 /* ---- the step object of a decoding loop ----------------------------------------------------- */
 /* DRL.forward's loop (model.py:342-496) runs its policy network between the environment steps, so the loop is

@@ -34,6 +34,7 @@ TAP_HIT_DECODER = 29                                           # decoder.hip: k_
 TAP_HIT_HEIGHTMAP = 30                                         # heightmap.hip: k_decoder_step_hm
 TAP_HIT_CRITIC = 31                                            # critic.hip: k_critic_value<HPL> / _bw<HPL> + _bw_reduce
 TAP_HIT_PACK_RNN = 32                                          # pack_rnn.hip: k_pack_rnn_forward<KIND> (key: 32, 2, TE, KIND, D / 64, 0, 0)
+TAP_HIT_DQN = 33                                               # dqn.hip: k_dqn_pick<TE> (key: 33, 2, TE, DIFF, P, 0, 0)
 TAP_PACK_G, TAP_PACK_LG = 0, 1
 TAP_P_GREEDY = 1
 TAP_PICK_GREEDY, TAP_PICK_DRAW = 1, 2                           # tap_pointer_pick_static's form (the launch record's second field)
@@ -78,6 +79,14 @@ PACK_RNN_WEIGHTS = ("Pe", "ce", "enc_w_hh", "enc_b_hh", "Pd_e", "Pd_b", "Pd_h", 
 class PackRnnWeights(C.Structure):
     """tapenv.h: tap_pack_rnn_weights"""
     _fields_ = [(k, C.c_int32) for k in ("kind", "Hb", "Hh", "W", "form", "reserved")] + [(k, _vp_t) for k in PACK_RNN_WEIGHTS]
+
+
+DQN_WEIGHTS = ("c1", "W2p", "b2", "W3p", "b3", "L1p", "l1b", "head_w", "head_b")
+
+
+class DqnWeights(C.Structure):
+    """tapenv.h: tap_dqn_weights"""
+    _fields_ = [(k, C.c_int32) for k in ("W", "Wm", "P", "reserved")] + [(k, _vp_t) for k in DQN_WEIGHTS]
 
 
 _lib = None
@@ -133,6 +142,8 @@ _PROTOS = {
     "tap_decoder_step_hm_dropout": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _i] + [_vp] * 12 + [_u32] * 4 + [_f, _f] + [_vp] * 7),
     "tap_decoder_step_dropout_backward": (_i, [_vp, _i, _i] + [_vp] * 5 + [_f, _f] + [_vp] * 4),
     "tap_pack_rnn_forward": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _i, _i, _i, C.POINTER(PackRnnWeights), _vp, _vp, _vp, _vp]),
+    "tap_dqn_pick": (_i, [_vp, C.POINTER(DqnWeights), _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "tap_dqn_pick_geometry": (_i, [_i, _i, C.POINTER(C.c_int32)]),
     "tap_env_feature": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp]),
     "tap_env_ratio": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp, _vp, _vp]),
     "tap_env_export": (_i, [_vp, C.POINTER(EnvDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -275,6 +286,15 @@ def pointer_scores_geometry(B, nR, rows, Hd, S=0, backward=False):
     if st != TAP_OK:
         raise TapError(st, "no pointer geometry for B %d, nR %d, rows %d, Hd %d, S %d" % (B, nR, rows, Hd, S))
     return tuple(out)
+
+
+def dqn_pick_geometry(W, is_diff_height):
+    """tap_dqn_pick_geometry (host only, no context) -> (envs per workgroup, positions, bytes of dynamic LDS), or None for a
+    shape tap_dqn_pick refuses."""
+    out = (C.c_int32 * 3)()
+    W = int(W)
+    st = lib().tap_dqn_pick_geometry(W, W - 1 if is_diff_height else W, out)
+    return tuple(out) if st == TAP_OK else None
 
 
 def encode_bits_geometry(B, nR, rows, H, backward=False):

@@ -931,7 +931,7 @@ def episode_scores_net(static, tour_indices, reward_type, container_size, net, i
     """tools.calc_positions_net (tools.py:3506-3598) for every sample of a batch, SL / RL types: blocks in tour order
     into an empty 2D container, each at the column ``net`` (a tools.DQN) picks from the raw height-map
     (tools.calc_one_position_net, tools.py:3371-3461).  n place-at launches (tapenv.h: TAP_AT_NET) with the net
-    between them; each launch also writes the net's next input, so nothing else runs in between.
+    between them (a net with ``fused`` set through its ``pick``: one launch, tapenv.h: tap_dqn_pick); each launch also writes the net's next input, so nothing else runs in between.
     -> (ratio (B,) float64 = (C+P+S)/3, scores (B, 5) int64 = valid_size, box_size, empty_size, stable_num, max height)
     [, the BatchedContainer with ``with_env``].  ``check``: raise like env.check() when a container overflowed."""
     from .env import BatchedContainer
@@ -958,7 +958,10 @@ def episode_scores_net(static, tour_indices, reward_type, container_size, net, i
     pnet = torch.zeros(B, 1, W, dtype=torch.float32, device=dev)           # the empty container's height-map
     with torch.no_grad():
         for t in range(n):
-            x = net(pnet, blocks_f[:, t:t + 1, :]).max(1)[1]                                       # :3411
+            if getattr(net, 'fused', False):
+                x = net.pick(pnet, blocks_f[:, t:t + 1, :])[0]                                     # tools.DQN.pick: one launch
+            else:
+                x = net(pnet, blocks_f[:, t:t + 1, :]).max(1)[1]                                   # :3411
             env.add_new_blocks_at(blocks[:, t], x, want_feature=False, pnet_out=pnet, pnet_form='full')
     ratio, scores = _net_scores(env, n, check)
     return (ratio, scores, env) if with_env else (ratio, scores)

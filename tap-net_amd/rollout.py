@@ -1555,7 +1555,8 @@ def _run_episode_pack(static, dynamic, policy, pack_policy, container_width, con
     ``pnet_input`` (B, 1, W) f32 is the height-map in DRL_L's heightmap_type form (model.py:1180-1196; 'diff' with its
     trailing 0), ``block`` = decoder_static transposed, (B, 1, 2).  pack_policy returns columns (B,) int64, or
     probabilities (B, W), which are argmaxed (model.py:1200-1202) and give ``pack_logp``, the log of the chosen
-    column's probability.  Nothing is read back to the host inside the loop, so the episode can be captured in a
+    column's probability.  A tools.DQN with ``fused`` set is asked through its ``pick`` instead (one launch: the column and
+    ``pack_logp``).  Nothing is read back to the host inside the loop, so the episode can be captured in a
     hipGraph.  Returns run_episode's dict plus ``place_x`` (B, steps) int64 [and ``pack_logp`` (B, steps)]."""
     if input_type in ('mul', 'mul-with'):
         raise NotImplementedError("the pack-net loop of the two-container input types is not implemented")
@@ -1583,6 +1584,8 @@ def _run_episode_pack(static, dynamic, policy, pack_policy, container_width, con
     decoder_static = torch.zeros(B, D, 1, device=dev)
     decoder_dynamic = torch.zeros(env._feature_shape(), device=dev)
     tour, xs, logps, feats, curs, msks, pins = [], [], [], [], [], [], []
+    from .tools import DQN
+    fused_pick = isinstance(pack_policy, DQN) and pack_policy.fused
     for step in range(nsteps):
         ptr = policy(step=step, static=masks.static, dynamic=masks.dynamic, current_mask=masks.current_mask,
                      mask=masks.mask, decoder_static=decoder_static, decoder_dynamic=decoder_dynamic).to(torch.int64)
@@ -1591,7 +1594,11 @@ def _run_episode_pack(static, dynamic, policy, pack_policy, container_width, con
         pin, pout = pnet[step % 2], pnet[(step + 1) % 2]
         if torch.is_grad_enabled():
             pin, = grad_copies(pin)
-        out = pack_policy(pin, decoder_static.transpose(2, 1))
+        if fused_pick:                                                                      # tools.DQN.pick: one launch
+            out, lp = pack_policy.pick(pin, decoder_static.transpose(2, 1))
+            logps.append(lp.unsqueeze(1))
+        else:
+            out = pack_policy(pin, decoder_static.transpose(2, 1))
         if out.dim() == 2:                                                                  # probabilities, model.py:1200-1202
             best = out.max(1)
             x = best[1]
@@ -1688,6 +1695,82 @@ def pack_rnn_forward_torch(fold, engine, blocks, blocks_num, want_input=True):
         if feat is not None:
             x = feat.to(dt)[:, :, 0]
     return torch.cat(logps, dim=1), feat
+
+
+# ---- the local pack-net's pick in one launch (tapenv.h: tap_dqn_pick has the contract) ----------------------------------
+def dqn_pick_supported(W, is_diff_height):
+    """whether tap_dqn_pick has a kernel for this net: W >= 2 and at most 14 positions (W <= 12, 13 in the diff form)"""
+    return _lib.dqn_pick_geometry(W, is_diff_height) is not None
+
+
+def _dqn_rows(fold, pnet, block):
+    """the two inputs as (B, >= Wm) and (B, 2) views: (B, 1, W) / (B, 1, 2) as DQN.forward takes them, or without the
+    middle axis"""
+    if pnet.dim() == 3 and pnet.shape[1] == 1:
+        pnet = pnet[:, 0]
+    if block.dim() == 3 and block.shape[1] == 1:
+        block = block[:, 0]
+    B = int(pnet.shape[0])
+    if pnet.dim() != 2 or block.dim() != 2 or int(block.shape[0]) != B or int(block.shape[1]) != 2 or \
+            int(pnet.shape[1]) != fold.W:
+        raise ValueError("the pack-net of %d columns takes a map (B, 1, %d) and a block (B, 1, 2), got %s and %s"
+                         % (fold.W, fold.W, tuple(pnet.shape), tuple(block.shape)))
+    return B, pnet, block
+
+
+def _dqn_view(t):
+    """t (B, k) as the launch reads it -- unit stride along a row, any env stride: the tensor itself where its strides allow"""
+    t = t.detach()
+    if t.shape[0] > 1 and (t.stride(1) != 1 or t.stride(0) < t.shape[1]):
+        t = t.contiguous()
+    elif t.shape[0] <= 1 and t.stride(1) != 1:
+        t = t.contiguous()
+    return t, (int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1]))
+
+
+def dqn_pick(fold, pnet, block, want_probs=False):
+    """DQN.forward's eval form and the pick in ONE launch (tap_dqn_pick): ``fold`` a ``tools.DqnFold`` of float32 tensors on
+    the GPU (``tools.DQN.fold``), ``pnet`` (B, 1, W) the map as DQN.forward takes it (the diff form's trailing entry is
+    never read), ``block`` (B, 1, 2), both float32 on the fold's device; views with a unit last stride are read in place
+    (``blocks_f[:, t:t + 1, :]``).  -> x (B,) int64 the first column of the largest probability, logp (B,) float32 its log
+    [, probs (B, W) float32].  No allocation beyond the outputs, no host read: capturable."""
+    B, pnet, block = _dqn_rows(fold, pnet, block)
+    if not dqn_pick_supported(fold.W, fold.is_diff_height):
+        raise _lib.TapError(_lib.TAP_E_UNSUPPORTED, "no pack-net pick kernel for W %d, diff %r" % (fold.W, fold.is_diff_height))
+    if pnet.dtype != torch.float32 or block.dtype != torch.float32:
+        raise TypeError("the fused pick takes float32 inputs, got %s and %s" % (pnet.dtype, block.dtype))
+    dev = _lib.resolve_device(pnet.device)
+    if block.device != pnet.device:
+        raise ValueError("the map is on %s, the block on %s" % (pnet.device, block.device))
+    w = fold.weights(dev)
+    pnet, ps = _dqn_view(pnet)
+    block, bs = _dqn_view(block)
+    x = torch.empty(B, dtype=torch.int64, device=dev)
+    logp = torch.empty(B, dtype=torch.float32, device=dev)
+    probs = torch.empty(B, fold.W, dtype=torch.float32, device=dev) if want_probs else None
+    c = _lib.ctx(dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().tap_dqn_pick(c, _lib.C.byref(w), _lib.ptr(pnet), ps, _lib.ptr(block), bs, B, _lib.ptr(x), _lib.ptr(logp),
+                                           _lib.ptr(probs), _lib.stream_of(dev)), c)
+    return (x, logp, probs) if want_probs else (x, logp)
+
+
+def dqn_pick_torch(fold, pnet, block, want_probs=False):
+    """``dqn_pick``'s contract in torch ops, in the fold's dtype on its device: the same fold, the same term order (lin1 over
+    k = p * 256 + c), the chains as matmuls.  In float64 it is the model the launch is tested against."""
+    B, pnet, block = _dqn_rows(fold, pnet, block)
+    f, dt = fold, fold.W2.dtype
+    xm, xb = pnet[:, :f.Wm].to(dt).unsqueeze(2), block.to(dt).unsqueeze(2)                    # (B, Wm, 1), (B, 2, 1)
+    h = torch.relu(torch.cat((f.a_m * xm + f.b_m, f.a_b * xb + f.b_b), 1))                      # (B, P, 128)
+    h = torch.relu(h @ f.W2.t() + f.b2)
+    h = torch.relu(h @ f.W3.t() + f.b3)
+    y = torch.relu(h.reshape(B, f.P * 256) @ f.L1.t() + f.l1b)
+    logit = y @ f.head_w.t() + f.head_b
+    m, x = logit.max(1)                                                      # the first maximum
+    e = torch.exp((logit - m.unsqueeze(1)).double())
+    s = e.sum(1)
+    logp = (-torch.log(s)).to(dt)
+    return (x, logp, (e / s.unsqueeze(1)).to(dt)) if want_probs else (x, logp)
 
 
 def _run_episode_rnn(static, dynamic, policy, net, container_width, reward_type, heightmap_type, input_type, allow_rot,

@@ -49,15 +49,59 @@ def is_stable_masks(bx, by, masks, use_lut=True, device='cuda'):
     return out.bool()
 
 
+class DqnFold(object):
+    """What ``DQN.fold`` returns, the parameters of ``rollout.dqn_pick`` / ``_torch`` (tapenv.h: tap_dqn_pick has the
+    algebra): the eval net with every batch-norm folded into the layer in front of it.  ``W`` columns, ``Wm`` map entries
+    read, ``P`` = Wm + 2 positions, ``is_diff_height``; layer 1 per channel ``a_m``, ``b_m`` (map positions) and ``a_b``,
+    ``b_b`` (block positions), ``c1`` (128, 4) their stack; ``W2`` (256, 128), ``b2``, ``W3`` (256, 256), ``b3``; ``L1``
+    (512, 256 P) = lin1.weight with its columns POSITION-MAJOR, k = p * 256 + c (the reference flattens (B, 256, P)
+    channel-major, c * P + p), ``l1b``; ``head_w`` (W, 512), ``head_b``.  ``W2p``, ``W3p``, ``L1p`` are W2, W3, L1 again in
+    the matrix cores' operand order (``pack_mfma_operand``), what the launch streams.  Detached and contiguous, in the net's
+    dtype on the net's device."""
+    __slots__ = ("W", "Wm", "P", "is_diff_height", "a_m", "b_m", "a_b", "b_b", "W2", "W3", "L1") + _lib.DQN_WEIGHTS + ("_struct",)
+
+    def weights(self, device):
+        """the launch's tap_dqn_weights (built once; the record keeps the tensors it points to alive)"""
+        if getattr(self, "_struct", None) is None:
+            w = _lib.DqnWeights()
+            w.W, w.Wm, w.P = self.W, self.Wm, self.P
+            for k in _lib.DQN_WEIGHTS:
+                t = getattr(self, k)
+                if t.dtype != torch.float32 or t.device != torch.device(device) or not t.is_contiguous():
+                    raise _lib.TapError(_lib.TAP_E_INVALID, "the fused pack-net pick takes contiguous float32 weights on %s, %s is %s on %s"
+                                        % (device, k, t.dtype, t.device))
+                if t.data_ptr() % 16:                                      # a view at an odd offset: the launch reads 16 bytes at a time
+                    t = t.clone()
+                    setattr(self, k, t)
+                setattr(w, k, t.data_ptr())
+            self._struct = w
+        return self._struct
+
+
+def pack_mfma_operand(X, T, KS):
+    """X (N, K) -> (K / (4 KS), N / T, 64, 4) contiguous, the f32-input MFMA's B operand with four steps of a lane together
+    (tapenv.h: tap_dqn_pick): out[q, tile, l, i] = X[tile * T + l % T, KS * (4 * q + i) + l // T]; T * KS = 64."""
+    N, K = X.shape
+    return X.reshape(N // T, T, K // (4 * KS), 4, KS).permute(2, 0, 4, 1, 3).reshape(K // (4 * KS), N // T, 64, 4).contiguous()
+
+
 class DQN(nn.Module):
     """The learned local pack-net ("L-Pnet", tools.DQN, tools.py:3322-3367): a column for a 2D block from the
     container's height-map.  Stock PyTorch; its parameter names and shapes are the reference's, so the SL / RL
     checkpoints load with ``load_state_dict(strict=True)``.  ``output_size`` = W columns; with ``is_diff_height`` the
     map's last entry (DRL_L's trailing 0 of the 'diff' form) is dropped.  forward(height_map (B, 1, W), block (B, 1, 2))
-    -> (B, W) softmax probabilities."""
+    -> (B, W) softmax probabilities.
 
-    def __init__(self, output_size, is_diff_height):
+    ``fused`` (also an attribute; default True, what profiles/dqn_pick.json measured; no parameter, no buffer): ``pick`` -- the column and the log of its
+    probability -- is ONE launch (``rollout.dqn_pick``; tapenv.h: tap_dqn_pick) when the module is in eval(), its output
+    needs no gradient (grad is disabled, or neither an input nor a parameter requires one), the inputs are float32 on the
+    GPU and the shape has a kernel (``rollout.dqn_pick_supported``).  In every other case ``pick`` is ``forward`` and a
+    ``max``.  ``forward`` itself is always the torch path."""
+
+    def __init__(self, output_size, is_diff_height, fused=True):
         super(DQN, self).__init__()
+        self.fused = bool(fused)
+        self._fold = None
         self.conv_height_map = nn.Conv1d(1, 128, kernel_size=1)
         self.conv_block = nn.Conv1d(1, 128, kernel_size=1)
         self.bn1 = nn.BatchNorm1d(128)
@@ -80,6 +124,73 @@ class DQN(nn.Module):
         h = F.relu(self.bn3(self.conv3(h)))
         h = F.relu(self.lin1(h.reshape(h.size(0), -1)))
         return F.softmax(self.head(h), dim=1)
+
+    def fold(self):
+        """-> a ``DqnFold``: the eval net, each batch-norm (its running statistics and its own eps) folded into the layer in
+        front of it, in torch, in the parameters' dtype (``net.double().fold()`` is the float64 model), detached; no
+        parameter is added and the state-dict keys stay the reference's.  Valid in eval() only.  The record is kept until a
+        parameter or a running statistic changes (its version, memory or dtype); one computed under hipGraph capture is
+        not kept."""
+        if self.training:
+            raise RuntimeError("DQN.fold folds the running statistics: the net must be in eval()")
+        tensors = list(self.parameters()) + list(self.buffers())
+        key = tuple((t.data_ptr(), t._version, t.dtype) for t in tensors) + tuple(bn.eps for bn in (self.bn1, self.bn2, self.bn3))
+        if self._fold is not None and self._fold[0] == key:
+            return self._fold[1]
+        with torch.no_grad():
+            f = DqnFold()
+            f.W, f.is_diff_height = int(self.head.out_features), bool(self.is_diff_height)
+            f.P = int(self.lin1.in_features) // 256
+            f.Wm = f.P - 2
+
+            def scale(bn):
+                return bn.weight / torch.sqrt(bn.running_var + bn.eps)
+            s1, s2, s3 = scale(self.bn1), scale(self.bn2), scale(self.bn3)
+            f.a_m = s1 * self.conv_height_map.weight[:, 0, 0]
+            f.b_m = s1 * (self.conv_height_map.bias - self.bn1.running_mean) + self.bn1.bias
+            f.a_b = s1 * self.conv_block.weight[:, 0, 0]
+            f.b_b = s1 * (self.conv_block.bias - self.bn1.running_mean) + self.bn1.bias
+            f.c1 = torch.stack((f.a_m, f.b_m, f.a_b, f.b_b), 1)
+            f.W2 = s2[:, None] * self.conv2.weight[:, :, 0]
+            f.b2 = s2 * (self.conv2.bias - self.bn2.running_mean) + self.bn2.bias
+            f.W3 = s3[:, None] * self.conv3.weight[:, :, 0]
+            f.b3 = s3 * (self.conv3.bias - self.bn3.running_mean) + self.bn3.bias
+            f.L1 = self.lin1.weight.reshape(512, 256, f.P).transpose(1, 2).reshape(512, 256 * f.P)   # c * P + p -> p * 256 + c
+            f.l1b, f.head_w, f.head_b = self.lin1.bias, self.head.weight, self.head.bias
+            f.W2p, f.W3p, f.L1p = pack_mfma_operand(f.W2, 32, 2), pack_mfma_operand(f.W3, 32, 2), pack_mfma_operand(f.L1, 16, 4)
+            for k in ("a_m", "b_m", "a_b", "b_b", "W2", "W3", "L1") + _lib.DQN_WEIGHTS:
+                setattr(f, k, getattr(f, k).detach().contiguous())
+        if not (tensors and tensors[0].is_cuda and torch.cuda.is_current_stream_capturing()):
+            self._fold = (key, f)
+        return f
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state['_fold'] = None                   # a cache holding device addresses: a copy folds again
+        return state
+
+    def _takes_launch(self, height_map, block):
+        """whether this pick is the one launch (the class docstring has the conditions)"""
+        if not getattr(self, 'fused', False) or self.training:
+            return False
+        if not (height_map.is_cuda and block.is_cuda and height_map.dtype == torch.float32 and block.dtype == torch.float32):
+            return False
+        if torch.is_grad_enabled() and (height_map.requires_grad or block.requires_grad or
+                                        any(p.requires_grad for p in self.parameters())):
+            return False
+        from .rollout import dqn_pick_supported
+        return self.lin1.weight.dtype == torch.float32 and self.lin1.weight.device == height_map.device and \
+            dqn_pick_supported(self.head.out_features, self.is_diff_height)
+
+    def pick(self, height_map, block):
+        """height_map (B, 1, W), block (B, 1, 2) -> x (B,) int64, the first column of the largest probability, and logp (B,),
+        the log of that probability (model.py:1200-1202): one launch under ``fused`` (the class docstring has the
+        conditions), else ``forward(...).max(1)`` and ``.log()``."""
+        if self._takes_launch(height_map, block):
+            from .rollout import dqn_pick
+            return dqn_pick(self.fold(), height_map, block)
+        best = self.forward(height_map, block).max(1)
+        return best[1], best[0].log()
 
 
 class DynamicBitsEncoder(nn.Module):
@@ -1277,7 +1388,8 @@ def load_pack_net(reward_type, container_width, device='cuda', container_height=
     types (tools.py:3488-3500).  The LG checkpoint is not shipped: FileNotFoundError, as the reference's torch.load.
     ``device=None`` leaves the network on the host.  A host PackRNN fed host blocks then needs a host engine
     injected (``net.engine_factory``): the default engine, env.PackEngines, has no CPU path and raises TapError.
-    ``fused`` is PackRNN's (the one-launch forward; the SL / RL nets have none and ignore it)."""
+    ``fused`` sets the net's ``fused`` attribute: PackRNN's one-launch forward, and for the SL / RL nets DQN's one-launch
+    ``pick`` (the loader's default stays False for both; a DQN built directly defaults to True)."""
     if reward_type not in PACK_NET_CHECKPOINTS:
         raise NotImplementedError("%s has no pack-net (tools.calc_positions_net)" % reward_type)
     W = int(container_width)
@@ -1285,7 +1397,7 @@ def load_pack_net(reward_type, container_width, device='cuda', container_height=
         H = _PACK_RNN_H if container_height is None else int(container_height)
         net = PackRNN(2, 128, W, 128, W, H, 'diff', pack_net_type=PACK_RNN_TYPES[reward_type], fused=fused)
     else:
-        net = DQN(W, True)
+        net = DQN(W, True, fused=fused)
     path = PACK_NET_CHECKPOINTS[reward_type]
     if not os.path.exists(path):
         raise FileNotFoundError("%s: the %s pack-net checkpoint (tools.py:3488-3553 loads it relative to the working "
