@@ -5,8 +5,11 @@ soft and hard rewards, B = 256 / 1 024 / 4 096.  One step = BatchedContainer.add
 
     python scripts/time_big_wg.py [--threads 256|512|1024] [--batches 256,1024,4096] [--out rows.jsonl]
 
---threads sets TAP_BIG_WG_THREADS (threads per container) for this process.  Blocks: 3D sides 4 .. 16 (the wide
-stability path above 8), 2D widths 100 .. 999, heights 1 .. 4 (no overflow within the episode)."""
+--threads sets TAP_BIG_WG_THREADS (threads per container) for this process.  Only a library built with -DTAP_AB_BUILD
+reads that variable (tap_common.h: tap_ab_env): point TAP_LIB_PATH at one (a copy of tap-net_amd/csrc built with
+-DTAP_AB_BUILD behind the Makefile's CXXFLAGS, given whole in the environment); on a library that ignores the variable --threads is refused, so no row gets a label it did not run
+with.  Blocks: 3D sides 4 .. 16 (the wide stability path above 8), 2D widths 100 .. 999, heights 1 .. 4 (no overflow
+within the episode)."""
 import argparse, json, os, sys, time
 ap = argparse.ArgumentParser()
 ap.add_argument("--threads", type=int, default=0)
@@ -22,6 +25,8 @@ sys.path.insert(0, ROOT)
 import numpy as np                    # noqa: E402
 import torch                          # noqa: E402
 import tap_net_amd as T               # noqa: E402
+if args.threads and b"TAP_BIG_WG_THREADS" not in open(T._lib.LIB_PATH, "rb").read():   # the name is only in a library that reads it
+    sys.exit("--threads: %s ignores TAP_BIG_WG_THREADS; set TAP_LIB_PATH to a -DTAP_AB_BUILD library" % T._lib.LIB_PATH)
 DEV = "cuda:0"
 assert torch.cuda.is_available(), "needs a GPU"
 SHAPES = [([100, 100, 60], (4, 17)), ([128, 128, 60], (4, 17)), ([8192, 100], (100, 1000))]

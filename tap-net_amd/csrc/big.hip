@@ -28,9 +28,7 @@ constexpr int TAP_BIG_WAVE_CELLS = 4096;
 // threads per container of those kernels, soft / hard rewards (measured at B = 1 024 over 256 / 512 / 1 024: DESIGN.md section 4)
 constexpr int TAP_BIG_WG_THREADS_SOFT = 512, TAP_BIG_WG_THREADS_HARD = 1024;
 
-#ifndef TAP_BIG_REGS
 #define TAP_BIG_REGS __attribute__((amdgpu_waves_per_eu(5, 8)))
-#endif
 
 struct BigCtx {
     int D, W, L, H, flags;
@@ -46,11 +44,7 @@ struct BigCtx {
 // the wide form cost the 10 x 10 step 15 % (c7: 23.1 against 20.1 us, round 5).
 __device__ __forceinline__ bool big_is_wide(int D, int bx, int by)
 {
-#ifdef TAP_AB_NO_WIDE_STABLE      // A/B builds: the wide instantiation compiled out (wide blocks then get wrong stability flags)
-    return false;
-#else
     return D == 2 ? bx > 64 : (bx > 8 || by > 8);
-#endif
 }
 
 template <bool WIDE>
@@ -828,11 +822,11 @@ __global__ void __launch_bounds__(NT) k_big_wg_episode(EpisodeArgs a)
     if (tid == 0) episode_finish(a, env, cnt, gmax, err);
 }
 
-// threads per container of the workgroup kernels (A/B runs: TAP_BIG_WG_THREADS = 256 / 512 / 1024, read once)
+// threads per container of the workgroup kernels (A/B builds, tap_ab_env: TAP_BIG_WG_THREADS = 256 / 512 / 1024, read once)
 static int big_wg_threads(bool hard)
 {
     static const int forced = [] {
-        const char *e = getenv("TAP_BIG_WG_THREADS");
+        const char *e = tap_ab_env("TAP_BIG_WG_THREADS");
         const int v = e ? atoi(e) : 0;
         return (v == 256 || v == 512 || v == 1024) ? v : 0;
     }();

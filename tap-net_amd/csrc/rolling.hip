@@ -46,11 +46,7 @@ struct RollArgs {
 // its 64-byte granule; `dy` = this instance's slab
 __device__ __forceinline__ LaneRole roll_lane_role(int v, const float *dy, int C4, int RP, int rows)
 {
-#ifdef TAP_STREAM_UNALIGNED
-    const int add = 0;
-#else
     const int add = ((RP * C4) & 3) == 0 ? (int)((reinterpret_cast<uintptr_t>(dy) >> 4) & 3) : 0;
-#endif
     return stream_lane_role(v, 0, C4, RP, 65536 / C4 + 1, 0, add, (rows + RP - 1) / RP);
 }
 
@@ -296,7 +292,7 @@ struct alignas(16) RollLds { // one wavefront's scratch: 4.8 KB, so that 8 workg
 };
 
 // one wavefront = one instance, lane v = node v; every lane of the wave must call this
-// -DTAP_PROF: per-phase shader-clock deltas of the first 8192 instances (scratch/prof_roll.py reads them)
+// -DTAP_PROF: per-phase shader-clock deltas of the first 8192 instances (tap_prof_read)
 #ifdef TAP_PROF
 __device__ unsigned int tap_prof_w[8192 * 8];
 extern "C" int tap_prof_read(unsigned int *out)
@@ -306,13 +302,6 @@ extern "C" int tap_prof_read(unsigned int *out)
 }
 #define PROF(i) do { const long long t_ = clock64(); if (v == 0 && inst < 8192) tap_prof_w[inst * 8 + (i)] = (unsigned)(t_ - tp); tp = t_; } while (0)
 #define PROF_BEGIN long long tp = clock64()
-#elif defined(TAP_ROLL_STOP)
-// -DTAP_ROLL_STOP: the wave returns at phase mark tap_roll_stop_at (scratch/valu_phases.py counts SQ_INSTS_VALU per
-// phase by differencing); results are garbage past the mark, the state must be restored by the caller
-__constant__ int tap_roll_stop_at = -1;
-extern "C" int tap_prof_set_stop(int i) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(tap_roll_stop_at), &i, sizeof(int)); }
-#define PROF(i) do { if (tap_roll_stop_at == (i)) return; } while (0)
-#define PROF_BEGIN do { } while (0)
 #else
 #define PROF(i) do { } while (0)
 #define PROF_BEGIN do { } while (0)
@@ -558,11 +547,7 @@ __device__ __forceinline__ void rolling_emit_fast_tail(const RollArgs &a, int in
         // instance.  The sb lanes that wrapped run one instruction late.
         constexpr int K = RP * C4;
         constexpr bool AL = (K & 3) == 0;
-#ifdef TAP_STREAM_UNALIGNED
-        const int sb = 0;
-#else
         const int sb = AL ? __builtin_amdgcn_readfirstlane((int)((reinterpret_cast<uintptr_t>(dy) >> 4) & 3)) : 0;
-#endif
         if (dy && v < K) {
             int role = v - sb;
             const int late = role < 0 ? 1 : 0;
@@ -789,9 +774,7 @@ __device__ inline void rolling_window_waveN(const RollArgs &a, int inst, int v, 
         else if (v == 0) pyset_order(S.lst, child, S.ord, S.tbl, S.tbl + PYSET_CAP);
     }
     tap_wave_lds_sync();
-#ifndef TAP_ROLL_LATEWAIT
     __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0) while only loads are outstanding (see rolling_window_wave)
-#endif
     if (v == 0) {
 #pragma unroll
         for (int k = 0; k < NW; ++k) { stp[k] = e[k]; stp[NW + k] = w[k]; }
@@ -1005,9 +988,7 @@ __device__ inline void rolling_window_wave(const RollArgs &a, int inst, int v, R
     // before it to be ACKNOWLEDGED (the round-3 ISA had five such vmcnt(0) between the state store and the fp32
     // expansion).  Waiting here, while only loads are outstanding -- they have had the whole set order to arrive --
     // leaves nothing for the stores to be waited on.
-#ifndef TAP_ROLL_LATEWAIT                                             // (A/B builds: the round-3 placement of the waits)
     __builtin_amdgcn_s_waitcnt(0x0F70);                              // vmcnt(0)
-#endif
     if (v == 0) {
         a.state[(size_t)inst * 2] = entered;
         a.state[(size_t)inst * 2 + 1] = window;
@@ -1066,11 +1047,9 @@ struct RollStepArgs {
     StepArgs s;
 };
 
-#ifndef TAP_ROLL_EPB
-#define TAP_ROLL_EPB 2      // A/B builds (-DTAP_ROLL_EPB=1 | 4).  Round 6, six processes per build, c5 M env-steps/s: 1: 426-478, 2: 542-558, 4: 483-533
-#endif
-constexpr int ROLL_EPB = TAP_ROLL_EPB;   // instances per workgroup of the fused step (2: 3-wave workgroups pack a CU's 28 wave slots
-                              // better than 6-wave ones: 9 x 3 = 27 against 4 x 6 = 24)
+constexpr int ROLL_EPB = 2;   // instances per workgroup of the fused step (2: 3-wave workgroups pack a CU's 28 wave slots
+                              // better than 6-wave ones: 9 x 3 = 27 against 4 x 6 = 24).  Round 6, six processes per build,
+                              // c5 M env-steps/s: 1: 426-478, 2: 542-558, 4: 483-533
 
 template <int D, int G, bool SOFT, int CH>
 __device__ __forceinline__ void rolling_step_body(const RollStepArgs &a, ROLL_HOT_PARAMS);
@@ -1100,12 +1079,8 @@ __device__ __forceinline__ void rolling_step_body(const RollStepArgs &a, ROLL_HO
     // The wave's index in a scalar register (as in transition.hip): the window wave's instance, and with it every address
     // it loads from and stores to, becomes scalar arithmetic.  c5 differs by +- 5 % from process to process (buffer
     // placement), so this A/B took eight processes per build in one session (profiles/r06_rolling_swave_ab.txt): median
-    // 507 -> 541 M env-steps/s, best 534 -> 557 M.  -DTAP_ROLL_VWAVE: the index as a vector value (A/B builds).
-#ifdef TAP_ROLL_VWAVE
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-#else
+    // 507 -> 541 M env-steps/s, best 534 -> 557 M.
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-#endif
     const int base = blockIdx.x * EPB;
     if (wave < ENV_WAVES) {
         __builtin_amdgcn_s_setprio(2);

@@ -299,12 +299,21 @@ __device__ __forceinline__ int tap_spread_env(int lpw, int B)
 // r06_rolling_swave_ab.txt, r06_wave_index_big_ab.txt): the fused step with two slabs per stream wave (c2) + 4 %, the
 // rolling step (c5) + 6 %, MACS 2D one wavefront per container (c9) + 5 % -- used there; one slab per stream wave (c3)
 // - 0.7 %, the MACS lane kernels (c4, c6) and MACS 3D one wavefront per container (c8) flat, LB_GREEDY one wavefront per
-// container (c7) - 4 % -- not used there.  -DTAP_WAVE_INDEX_VECTOR for A/B builds.
-#ifdef TAP_WAVE_INDEX_VECTOR
-#define TAP_WAVE_INDEX() ((int)(threadIdx.x >> 6))
-#else
+// container (c7) - 4 % -- not used there.
 #define TAP_WAVE_INDEX() (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)))
+
+// A tuning variable of the A/B builds (-DTAP_AB_BUILD): TAP_AB_NO_TIE (env.hip), TAP_WRITE_THROUGH (tap_masks.h), TAP_FORCE_G
+// (below), TAP_BIG_WG_THREADS (big.hip).  The product library reads none of them: a stray variable must not change which
+// kernel a training job runs.
+inline const char *tap_ab_env(const char *name)
+{
+#ifdef TAP_AB_BUILD
+    return getenv(name);
+#else
+    (void)name;
+    return nullptr;
 #endif
+}
 
 // TAP_NO_WAVE_KERNELS (read once): the wave-per-container kernels of big.hip / macs_big.hip / macs3_big.hip stand aside
 // and their fallbacks -- what runs when a container's tile does not fit the LDS -- take every launch (parity tests, A/B)
@@ -322,7 +331,7 @@ int tap_desc_validate(tap_ctx *ctx, const tap_env_desc *d);
 inline int tap_group_size(const tap_env_desc *d)
 {
     const int cells = d->W * d->L;
-    static const int forced = [] { const char *e = getenv("TAP_FORCE_G"); return e ? atoi(e) : 0; }();   // A/B runs only
+    static const int forced = [] { const char *e = tap_ab_env("TAP_FORCE_G"); return e ? atoi(e) : 0; }();   // A/B builds only
     if (forced >= cells && (forced == 8 || forced == 16 || forced == 32 || forced == 64)) return forced;
     return cells <= 8 ? 8 : cells <= 16 ? 16 : cells <= 32 ? 32 : cells <= 64 ? 64 : 0;
 }

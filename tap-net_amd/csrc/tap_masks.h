@@ -7,6 +7,7 @@
 #include <type_traits>
 #include <cstdlib>
 
+#include "tap_common.h"
 #include "tap_stream_variant.h"
 
 constexpr size_t TAP_WT_MAX_BYTES = 64u << 20;   // write-through up to this many bytes of fp32 tensor per launch (see store_stream)
@@ -159,7 +160,7 @@ __device__ __forceinline__ void tap_wave_lds_sync_m()
 //       dirty when the kernel ends is written back at the kernel boundary, after the last wave -- at c2 most of the
 //       19.7 MB a step writes (the eight L2s hold 32 MB).  A write-through store sends the bytes on while the kernel
 //       is still running and drops the line.  Round 4, B = 8192 / 4096, per launch inside the replayed graph
-//       (scripts/ab_transition.sh): c2 7.10-7.31 us nontemporal -> 6.70 (6.87 `sc1`, 8.03-8.12 plain, 8.69-8.86
+//       (A/B builds): c2 7.10-7.31 us nontemporal -> 6.70 (6.87 `sc1`, 8.03-8.12 plain, 8.69-8.86
 //       `sc1 nt`), c3 8.80-8.84 -> 8.33-8.36; whole passes c2 1 139 -> 1 221 M env-steps/s, c3 458 -> 485 M, c4 441 ->
 //       480 M, c6 125.5 -> 130.7 M.  Writing the step's SMALL outputs (masks, shadow words) through as well lost 4-8 %
 //       at c2 (4-byte `sc1` stores are one fabric write each).
@@ -184,10 +185,10 @@ __device__ __forceinline__ void store_stream(float4 *dst, const float4 &v, int w
 }
 
 // Which flavour a launch that writes `bytes` of expanded fp32 tensor takes.  TAP_WRITE_THROUGH=0|1 in the
-// environment forces one (A/B runs; read once).
+// environment forces one in an A/B build (tap_ab_env; read once).
 inline int tap_write_through(size_t bytes, size_t limit)
 {
-    static const int forced = [] { const char *e = getenv("TAP_WRITE_THROUGH"); return e ? (e[0] != '0') : -1; }();
+    static const int forced = [] { const char *e = tap_ab_env("TAP_WRITE_THROUGH"); return e ? (e[0] != '0') : -1; }();
     if (forced >= 0) return forced;
     return bytes <= limit;
 }
@@ -472,7 +473,6 @@ __device__ __forceinline__ void stream_build_bits(const MaskArgs &a, int senv0, 
 // lanes of a column quad in the wave's LDS tile (ds_or_b32), the words & ~clear written by the first_row lanes, both masks
 // from the per-column words as in the shadow form; elements that are neither 0 nor 1 are flagged per lane and counted on
 // the rare path only.  A lane stores only elements it loaded, after all the wave's loads have returned.
-// -DTAP_FIRST_STEP_LDS: stream_build_bits for these windows too (A/B builds).
 template <int NS, bool MERGED, int C4S>
 __device__ __forceinline__ void stream_wave_first_regs(const MaskArgs &a, int senv0, int lane, const bool (&on)[NS], float *lds)
 {
@@ -485,11 +485,7 @@ __device__ __forceinline__ void stream_wave_first_regs(const MaskArgs &a, int se
     static_assert(NS * nR <= 64 && NS * nR * sizeof(unsigned) <= NS * 3 * nR * sizeof(float), "the tile fits the wave's LDS and one lane zeroes a word");
     if (!on[0]) return;                                    // on[] is a prefix and wave-uniform
     const bool lane_on = lane < RP * C4;
-#ifdef TAP_STREAM_UNALIGNED
-    const LaneRole role = stream_lane_role(lane, 0, C4, RP, c4_magic, 0, 0, 0);
-#else
     const LaneRole role = stream_lane_role(lane, senv0, C4, RP, c4_magic, a.sb_mul, a.sb_add, 0);
-#endif
     const bool first_row = role.rsub == 0;
     unsigned *tile = reinterpret_cast<unsigned *>(lds);    // NS * nR words
     const void *any = static_cast<const void *>(a.dyn_in); // a readable address for the inputs a caller may leave out
@@ -545,11 +541,7 @@ __device__ __forceinline__ void stream_wave_first_regs(const MaskArgs &a, int se
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
         const bool valid_v = on[k] && has_ptr && praw[k] >= 0 && praw[k] < nR;  // no ptr: the initial mask (model.py:297-307)
-#ifdef TAP_STREAM_VPICK
-        constexpr bool SPICK = false;
-#else
         constexpr bool SPICK = NS > 1;
-#endif
         bool valid;
         int p, real;
         if constexpr (!SPICK) {
@@ -709,13 +701,11 @@ __device__ __forceinline__ void stream_wave_bits_r4(const MaskArgs &a, int senv0
 {
     static_assert(!(BUILD && INPLACE), "the first step on a fresh tensor writes all of it");
     static_assert(!NOMASK || (FULL && !BUILD && C4S != 0), "the mask wave exists beside the FULL step on a compiled-in shape only");
-#ifndef TAP_FIRST_STEP_LDS                                // A/B builds: the first step through stream_build_bits everywhere
     if constexpr (BUILD && (C4S == 5 || C4S == 15)) {
         static_assert(NC == 1 && !FULL, "the compiled-in 10-node windows have one column per lane; FULL is a shadow step's");
         stream_wave_first_regs<NS, MERGED, C4S>(a, senv0, lane, on_, lds);
         return;
     }
-#endif
     bool on[NS];
 #pragma unroll
     for (int k = 0; k < NS; ++k) on[k] = FULL ? true : on_[k];
@@ -725,14 +715,8 @@ __device__ __forceinline__ void stream_wave_bits_r4(const MaskArgs &a, int senv0
     // fetches it with four ds_bpermute per slab, behind the stores.  30-row windows only (the low word carries every row),
     // and one-slab waves only: same session, c3 549.6 -> 555.5 M env-steps/s, but c2 (two slabs: eight shuffles and their
     // selects in the tail) 1 499 -> 1 483 M although a timing build WITHOUT the second load and without a replacement read
-    // + 2.2 % there.  -DTAP_STREAM_LOAD_BJ: round 5's second load everywhere; -DTAP_STREAM_BJX_ALL: the shuffles for two-slab waves too.
-#if defined(TAP_STREAM_LOAD_BJ)
-    constexpr bool BJ_X = false;
-#elif defined(TAP_STREAM_BJX_ALL)
-    constexpr bool BJ_X = !BUILD && NC == 1 && (C4S == 5 || C4S == 15);
-#else
+    // + 2.2 % there.
     constexpr bool BJ_X = !BUILD && NC == 1 && NS == 1 && (C4S == 5 || C4S == 15);
-#endif
     // NOMASK waves (two slabs of the 2D window, mode 77) take their inputs with TWO vector loads instead of six.  The wave
     // needs 2 x (80 B of row 0 + 160 B of shadow words); the quad layout -- every lane loads the 32 bytes of its column quad,
     // per slab, twelve lanes to a quad -- brings 4.6 KB back through the CU's vector-memory return path for them.  Here
@@ -743,12 +727,7 @@ __device__ __forceinline__ void stream_wave_bits_r4(const MaskArgs &a, int senv0
     // contiguous bytes, all 64 bits of a word & ~clear) instead of four 16-byte stores of the first_row lanes.  The
     // expansion, its lane roles and its stores are what they were.  Same session, c2: 1 577 -> 1 616 M env-steps/s; the
     // wave's inputs arrive 0.68 instead of 1.12 us (median) after the launch's first wave.
-    // -DTAP_STREAM_QUAD_LOADS: the quad loads (A/B builds).
-#ifdef TAP_STREAM_QUAD_LOADS
-    constexpr bool LDSIN = false;
-#else
     constexpr bool LDSIN = NOMASK;
-#endif
     static_assert(!LDSIN || (NS == 2 && NC == 1 && C4S == 5 && MERGED && !INPLACE), "the mask wave's stream waves: two slabs of the 10-node 2D window");
     typedef unsigned long long u64;
     static_assert(NS <= 2, "a stream wave expands one or two slabs");
@@ -762,11 +741,7 @@ __device__ __forceinline__ void stream_wave_bits_r4(const MaskArgs &a, int senv0
     // rotated so that each store instruction starts on a 64-byte granule).  Same registers as the fixed (rsub, c4)
     // mapping of round 4 -- per-slab roles cost six more and a wave per SIMD (68 VGPRs, measured: 1 264 against
     // 1 450 M env-steps/s at B = 1 M).
-#ifdef TAP_STREAM_UNALIGNED   // A/B builds: round 4's fixed roles (store instructions start wherever the slab does)
-    const LaneRole role = stream_lane_role(lane, 0, C4, RP, c4_magic, 0, 0, 0);
-#else
     const LaneRole role = stream_lane_role(lane, senv0, C4, RP, c4_magic, a.sb_mul, a.sb_add, 0);
-#endif
     const bool first_row = role.rsub == 0;               // these lanes also write the slab's new shadow words
     u64 *tile = reinterpret_cast<u64 *>(lds);
     // a readable, 16-byte aligned address for the inputs a caller may leave out (ptr / static: the initial mask,
@@ -808,9 +783,6 @@ __device__ __forceinline__ void stream_wave_bits_r4(const MaskArgs &a, int senv0
 #pragma unroll
         for (int k = 0; k < NS; ++k) row0[k][0] = r0v;   // the pick reads it at lane k * nR + p
     }
-#ifdef TAP_STREAM_G2          // A/B builds: the shadow words requested only after the small inputs have arrived (round 3's order)
-    __builtin_amdgcn_s_waitcnt(0x0F70);
-#endif
     if (!BUILD && !LDSIN) {
 #pragma unroll
         for (int k = 0; k < NS; ++k) {
@@ -840,15 +812,12 @@ __device__ __forceinline__ void stream_wave_bits_r4(const MaskArgs &a, int senv0
     }
     // The OUTPUT addresses and the store flavour live in the argument block and the compiler fetches each at its first use,
     // AFTER the wait below (three scalar-cache reads inside the wave's critical path).  Forcing them into scalar registers
-    // here, while the vector loads are in flight, measured SLOWER (round 6, -DTAP_STREAM_EARLY_ARGS: c2 1 488 -> 1 450 M
+    // here, while the vector loads are in flight, measured SLOWER (round 6: c2 1 488 -> 1 450 M
     // env-steps/s with the rolled expansion, 1 502 -> 1 464 M with the unrolled one): the wait it puts in front of the
     // vector wait costs more than the late reads, which hit the scalar cache.
     float *o_dyn = a.dyn_out, *o_cur = a.cur_out, *o_mask = a.mask_out;
     unsigned long long *o_bits = a.bits_out;
     int o_wt = a.wt;
-#ifdef TAP_STREAM_EARLY_ARGS                              // A/B builds
-    asm volatile("" : "+s"(o_dyn), "+s"(o_cur), "+s"(o_mask), "+s"(o_bits), "+s"(o_wt));
-#endif
     __builtin_amdgcn_s_waitcnt(0x0F70);                  // vmcnt(0): every input of both slabs is here
 #ifdef TAP_PROF
     TL_STAMP(1);
@@ -879,7 +848,7 @@ __device__ __forceinline__ void stream_wave_bits_r4(const MaskArgs &a, int senv0
     // A slab's pick, its block id and the rows it clears are the same on every lane of the wave: kept in SCALAR registers
     // (v_readlane on the row-0 values the lanes hold instead of a shuffle through the LDS crossbar; the clear mask is
     // scalar shifts), they cost the stream wave's critical path -- this launch's, at the BASELINE batches -- no vector
-    // issue slots and no LDS round trip (round 6: c2 1 440 -> 1 470 M env-steps/s, scripts/ab_transition.sh)
+    // issue slots and no LDS round trip (round 6: c2 1 440 -> 1 470 M env-steps/s)
     constexpr int UR_C = C4S != 0 ? 3 : 0;                 // the compiled-in windows are 'bot' windows: rows = 3 n, update_rows = 3 (checked by the launchers)
     const int ur = UR_C ? UR_C : a.update_rows;
 #pragma unroll
@@ -887,11 +856,7 @@ __device__ __forceinline__ void stream_wave_bits_r4(const MaskArgs &a, int senv0
         const bool valid_v = on[k] && has_ptr && praw[k] >= 0 && praw[k] < nR;  // no ptr: the initial mask (model.py:297-307)
         // (two-slab waves only: with ONE slab per wave -- 3D windows, c3 -- the vector form below measured 1 % faster,
         //  538 against 543 M env-steps/s: there the chain is half as long and the scalar unit is the busier one)
-#ifdef TAP_STREAM_VPICK                                     // A/B builds: round 5's vector form everywhere
-        constexpr bool SPICK = false;
-#else
         constexpr bool SPICK = NS > 1;
-#endif
         bool valid;
         int p, real;
         if constexpr (!SPICK) {
@@ -950,13 +915,7 @@ __device__ __forceinline__ void stream_wave_bits_r4(const MaskArgs &a, int senv0
                     const int r = realk[k] + n * i;
                     if (!on[k] || realk[k] < 0 || r >= rows) continue;
                     float4 *dst = reinterpret_cast<float4 *>(o_dyn) + ((size_t)(senv0 + k) * rows + r) * C4 + c;
-#if defined(TAP_INPLACE_STORE) && TAP_INPLACE_STORE == 1      // A/B builds: always write-through / nontemporal like the expansion
-                    store_stream(dst, z, o_wt);
-#elif defined(TAP_INPLACE_STORE) && TAP_INPLACE_STORE == 2     // A/B builds: plain
-                    *dst = z;
-#else
                     if (o_wt) store_stream(dst, z, 1); else *dst = z;            // a row is a fraction of a line: never nontemporal
-#endif
                 }
             }
         }
@@ -1014,20 +973,7 @@ __device__ __forceinline__ void stream_wave_bits_r4(const MaskArgs &a, int senv0
                         store_stream(&dst[(size_t)ri * C4], v, decltype(wt_c)::value);
                     }
                 };
-#ifdef TAP_STREAM_ROLLED                                  // A/B builds: round 5's rolled loop
-                for (int i = 0; i < nq; ++i, rr += RP) {
-                    if ((unsigned)rr >= (unsigned)total) continue;
-                    const bool up = NS > 1 && rr >= rows;
-                    const int r = up ? rr - rows : rr;
-                    const unsigned m0 = up ? (unsigned)nw[NS - 1][0] : (unsigned)nw[0][0], m1 = up ? (unsigned)nw[NS - 1][1] : (unsigned)nw[0][1],
-                                   m2 = up ? (unsigned)nw[NS - 1][2] : (unsigned)nw[0][2], m3 = up ? (unsigned)nw[NS - 1][3] : (unsigned)nw[0][3];
-                    const float4 v = make_float4((float)((m0 >> r) & 1u), (float)((m1 >> r) & 1u),
-                                                 (float)((m2 >> r) & 1u), (float)((m3 >> r) & 1u));
-                    store_stream(&dst[(size_t)rr * C4], v, o_wt);
-                }
-#else
                 if (o_wt) run(std::integral_constant<int, 1>{}); else run(std::integral_constant<int, 0>{});
-#endif
             } else if (rows <= 32) {
                 // n <= 10 (every BASELINE window): the column words fit 32 bits -- a bit-field extract and a
                 // convert per element, no half selection
@@ -1102,133 +1048,15 @@ __device__ __forceinline__ void stream_wave_bits_r4(const MaskArgs &a, int senv0
 //  1 653 M env-steps/s at B = 128 k, 1 353 against 1 471 M at 512 k, 1 357 / 1 361 against 1 478 M at 1 M; c3's at 256 k
 //  514 / 500 against 558 M.  With every wave slot of the CU taken, the hardware's interleaving of many short-lived waves
 //  already overlaps loads and drains; fewer, longer-lived waves only lose.  git: "pipelined stream wave ... TAP_PIPE_ITERS".)
-// -DTAP_STREAM_R3: the round-3 form of the step (scripts/ab_transition.sh A/B builds only)
-#ifdef TAP_STREAM_R3
-template <int NS, int NC, bool BUILD = false>
-__device__ __forceinline__ void stream_wave_bits_r3(const MaskArgs &a, int senv0, int lane, const bool (&on)[NS],
-                                                 float *lds = nullptr)
-{
-    typedef unsigned long long u64;
-    const int nR = a.nR, C4 = nR >> 2, rows = a.rows;
-    const int rsub = (int)(((unsigned)lane * (unsigned)a.c4_magic) >> 16), c4 = lane - rsub * C4, RP = a.rp;
-    const bool lane_on = rsub < RP;
-    constexpr bool build = BUILD;
-    u64 *tile = reinterpret_cast<u64 *>(lds);
-    long p[NS];
-    float row0[NS][NC], keep[NS][NC];
-    u64 bj[NS][NC];
-    ulonglong2 w[NS][2];
-    // every small input is requested up front (in the first-step form the slab is read AFTER they have arrived:
-    // stream_build_bits' loop header waits for vmcnt(0) -- two round trips, see there)
-#pragma unroll
-    for (int k = 0; k < NS; ++k) {
-        const int env = senv0 + k;
-        p[k] = (on[k] && a.ptr) ? (long)a.ptr[env] : -1;   // no ptr: the initial mask (model.py:297-307)
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const int j = lane + 64 * c;
-            const bool ok = on[k] && j < nR;
-            row0[k][c] = (ok && a.static_) ? a.static_[(size_t)env * a.static_rows * nR + j] : 0.f;
-            keep[k][c] = ok ? (a.mask_in ? a.mask_in[(size_t)env * nR + j] : 1.f) : 0.f;
-        }
-    }
-    if (BUILD) stream_build_bits<NS>(a, senv0, lane, on, tile);
-#pragma unroll
-    for (int k = 0; k < NS; ++k) {
-        const int env = senv0 + k;
-        const size_t wbase = build ? (size_t)k * nR : (size_t)env * nR;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const int j = lane + 64 * c;
-            const bool ok = on[k] && j < nR;
-            if (BUILD) bj[k][c] = ok ? tile[wbase + j] : 0ull;
-            else bj[k][c] = ok ? a.bits_in[wbase + j] : 0ull;
-        }
-        const bool ok = on[k] && lane_on;
-        if (BUILD) {
-            const ulonglong2 *src = reinterpret_cast<const ulonglong2 *>(tile + wbase + c4 * 4);
-            w[k][0] = ok ? src[0] : make_ulonglong2(0, 0);
-            w[k][1] = ok ? src[1] : make_ulonglong2(0, 0);
-        } else {
-            const ulonglong2 *src = reinterpret_cast<const ulonglong2 *>(a.bits_in + wbase + c4 * 4);
-            w[k][0] = ok ? src[0] : make_ulonglong2(0, 0);
-            w[k][1] = ok ? src[1] : make_ulonglong2(0, 0);
-        }
-    }
-    const u64 nmask = (a.n >= 64) ? ~0ull : ((1ull << a.n) - 1ull);
-#pragma unroll
-    for (int k = 0; k < NS; ++k) {
-        if (!on[k]) continue;
-        const int env = senv0 + k;
-        float r0 = -1.f;                                                      // pack.py:339 via shuffle; stays -1
-#pragma unroll                                                                        // for an index outside [0, nR)
-        for (int c = 0; c < NC; ++c) {
-            const float t = __shfl(row0[k][c], (int)(p[k] & 63));
-            if ((p[k] >> 6) == c && p[k] >= 0 && p[k] < nR) r0 = t;
-        }
-        const long real = (long)r0;
-        u64 clr = 0;                                                          // pack.py:370-374
-        for (int i = 0; i < a.update_rows; ++i) {
-            const long r = real + (long)a.n * i;
-            if (real >= 0 && r < rows) clr |= 1ull << r;
-        }
-        if (lane_on) {
-            const u64 n0 = w[k][0].x & ~clr, n1 = w[k][0].y & ~clr, n2 = w[k][1].x & ~clr, n3 = w[k][1].y & ~clr;
-#ifdef TAP_PROF
-            if (k == 0) { TL_WAIT_VM(); TL_STAMP(1); }
-#endif
-            if (a.dyn_out) {
-                float4 *dst = reinterpret_cast<float4 *>(a.dyn_out + (size_t)env * rows * nR) + c4;
-                if (rows <= 32) {
-                    // n <= 10 (every BASELINE window): the column words fit 32 bits -- a bit-field extract and a
-                    // convert per element, no half selection
-                    const unsigned m0 = (unsigned)n0, m1 = (unsigned)n1, m2 = (unsigned)n2, m3 = (unsigned)n3;
-                    for (int r = rsub; r < rows; r += RP) {
-                        const float4 v = make_float4((float)((m0 >> r) & 1u), (float)((m1 >> r) & 1u),
-                                                     (float)((m2 >> r) & 1u), (float)((m3 >> r) & 1u));
-                        store_stream(&dst[(size_t)r * C4], v, a.wt);
-                    }
-                } else {
-                    for (int r = rsub; r < rows; r += RP) {
-                        const float4 v = make_float4(bit_as_float(n0, r), bit_as_float(n1, r), bit_as_float(n2, r),
-                                                     bit_as_float(n3, r));
-                        store_stream(&dst[(size_t)r * C4], v, a.wt);
-                    }
-                }
-            }
-            if (rsub == 0 && a.bits_out) {
-                ulonglong2 *dst = reinterpret_cast<ulonglong2 *>(a.bits_out + (size_t)env * nR + c4 * 4);
-                dst[0] = make_ulonglong2(n0, n1);
-                dst[1] = make_ulonglong2(n2, n3);
-            }
-        }
-        const long real_m = (p[k] >= 0 && p[k] < nR) ? tap_mod_col(p[k], a.n, a.nR) : -1 - (long)a.n * a.R; // pack.py:314-316
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const int j = lane + 64 * c;
-            if (j >= nR) continue;
-            const u64 nb = bj[k][c] & ~clr;
-            const int move = __popcll(nb & nmask), small = a.n >= 64 ? 0 : __popcll((nb >> a.n) & nmask);
-            const int large = a.n >= 32 ? 0 : __popcll((nb >> (2 * a.n)) & nmask); // rows <= 64
-            float kp = keep[k][c];
-            for (int r = 0; r < a.R; ++r)
-                if (j == real_m + (long)a.n * r) kp = 0.f;                    // pack.py:320-321
-            if (a.mask_out) a.mask_out[(size_t)env * nR + j] = kp;
-            if (a.cur_out) a.cur_out[(size_t)env * nR + j] = (small * large + move) != 0 ? 0.f : kp; // :327-329
-        }
-    }
-}
 
-#endif
+// What the kernels call.  It only forwards, and it stays: with the body under this name and no forwarder, seven kernels
+// come out of the compiler with other text (scripts/compare_device_code.py: k_mask_step<2, 1>, where one compare moves
+// and scalar pairs are renumbered, and k_transition<2, 8 | 16 | 32, 1, 4, 77> and <..., 2, 4, 5> -- c2's step among them);
+// presumably the body passes the inliner's simplification once more on its way through the forwarder.
 template <int NS, int NC, bool BUILD = false, bool MERGED = true, int C4S = 0, bool INPLACE = false, bool FULL = false, bool NOMASK = false>
 __device__ __forceinline__ void stream_wave_bits(const MaskArgs &a, int senv0, int lane, const bool (&on)[NS], float *lds = nullptr)
 {
-#ifdef TAP_STREAM_R3
-    static_assert(!NOMASK, "the round-3 stream wave always carries update_mask");
-    stream_wave_bits_r3<NS, NC, BUILD>(a, senv0, lane, on, lds);
-#else
     stream_wave_bits_r4<NS, NC, BUILD, MERGED, C4S, INPLACE, FULL, NOMASK>(a, senv0, lane, on, lds);
-#endif
 }
 
 // ---- the mask wave of the fused 2D step: update_mask (pack.py:314-329) for ALL the envs of a workgroup ------------------

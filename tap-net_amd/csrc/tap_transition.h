@@ -81,11 +81,7 @@ template <int G, int SW> struct TransGeom {
 // narrow stores at that wave's tail, on 20 of its 64 lanes.  The three kinds exchange nothing.
 template <int D, int G, int NC, int SW, int MODE> constexpr bool trans_mask_wave()
 {
-#ifdef TAP_NO_MASK_WAVE                                       // A/B builds: update_mask in the stream waves' tail everywhere
-    return false;
-#else
     return D == 2 && NC == 1 && TransGeom<G, SW>::SPW == 2 && MODE == (1 | TAP_MODE_MERGED | TAP_MODE_C4_5 | TAP_MODE_FULL);
-#endif
 }
 template <int D, int G, int NC, int SW, int MODE> constexpr int trans_threads()
 {

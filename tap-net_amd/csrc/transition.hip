@@ -42,15 +42,11 @@ __global__ void __launch_bounds__((trans_threads<D, G, NC, SW, MODE>())) k_trans
     __shared__ int s_new[64 * ENV_WAVES];
     // The wave's index in a SCALAR register (two-slab stream waves: 2D windows): everything a stream wave derives from it --
     // its envs, every load and store address -- is then scalar arithmetic + lane offsets instead of 64-bit vector
-    // multiplies in front of the first load.  Round 6, same session (scripts/ab_transition.sh): c2 1 380 -> 1 440 M
+    // multiplies in front of the first load.  Round 6, same session: c2 1 380 -> 1 440 M
     // env-steps/s; c3 (one slab per wave) 545 -> 541 M, the MACS steps flat, the rolling step 530 -> 491 M -- so only here,
-    // and only for SPW > 1.  -DTAP_VWAVE: the index as the compiler sees it (a VGPR) everywhere (A/B builds).
+    // and only for SPW > 1.
     const int tid = threadIdx.x, lane = tid & 63;
-#ifdef TAP_VWAVE
-    const int wave = tid >> 6;
-#else
     const int wave = TransGeom<G, SW>::SPW > 1 ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
-#endif
     const int env_base = blockIdx.x * EPB;
 
 #if defined(TAP_PROF) || defined(TAP_PROF_SWITCH)
@@ -58,9 +54,6 @@ __global__ void __launch_bounds__((trans_threads<D, G, NC, SW, MODE>())) k_trans
     if (wave >= ENV_WAVES ? (a.flags & TAP_T_PROF_NOSTREAM) : (a.flags & TAP_T_PROF_NOPLACE)) return;
 #endif
     if (wave >= ENV_WAVES) {
-#ifdef TAP_STREAM_PRIO                                       // A/B builds: the stream waves' issue priority (default 0)
-        __builtin_amdgcn_s_setprio(TAP_STREAM_PRIO);
-#endif
         const MaskArgs m = tap_mask_hot(a.m, (MODE & 3) == 1, TAP_MASK_HOT_NAMES);
         if constexpr (MASKW) {
             if (wave == ENV_WAVES + Geo::STREAM_WAVES) {     // at the stream waves' priority (raised ones starve the placement chain)
@@ -74,11 +67,7 @@ __global__ void __launch_bounds__((trans_threads<D, G, NC, SW, MODE>())) k_trans
     }
 
     // ---- placement waves (tools.py:3663-3744): their latency chain runs beside the stream --------
-#ifdef TAP_PLACE_PRIO                                        // A/B builds
-    __builtin_amdgcn_s_setprio(TAP_PLACE_PRIO);
-#else
     __builtin_amdgcn_s_setprio(2);
-#endif
     const int cell = tid % G;
     TL_STAMP(0);
     StepArgs sa = a.s;       // the gather's source is the update's: ptr, static and their sizes are already in SGPRs
@@ -164,12 +153,8 @@ template <int D, int G> static int launch_transition(tap_ctx *ctx, const TransAr
     // 1 216 M env-steps/s, 1 903 -> 1 753 M at B = 65 536).  3D windows (7 200-byte slabs): 8, one slab per wave -- c3
     // 507 -> 543 M at B = 4 096, 556 -> 598 M at 8 192, 549 -> 574 M at 16 384, 605 -> 620 M at 65 536, equal from 262 144
     // (round 5, on the kernels with the compiled-in window shape; round 4 had measured 4 as the best for both at c2's
-    // shape only).  -DTAP_TRANS_SW=n forces one value (scripts/ab_transition.sh).
-#ifdef TAP_TRANS_SW
-    return launch_transition_v<D, G, TAP_TRANS_SW>(ctx, a, st);
-#else
+    // shape only).
     return launch_transition_v<D, G, (D == 3 ? 8 : 4)>(ctx, a, st);
-#endif
 }
 
 static int transition_dispatch(tap_ctx *ctx, const tap_env_desc *d, const TransArgs &a, void *stream);

@@ -19,15 +19,13 @@
 //  them perfectly -- 23.6 us.  A window-maximum form of macs_adj (80 instead of 590 instructions, tie-break 5.1 k -> 2.6 k
 //  cycles stand-alone) crossed that line and was dropped; amdgpu_waves_per_eu(7, 8) brings either form to 72 VGPRs but
 //  costs 3 % by itself.)
-#ifndef TAP_MACS_SW
-#define TAP_MACS_SW 4   // stream waves per workgroup of the MACS fused steps (-DTAP_MACS_SW=8, measured in round 5: c4 503 -> 330 M
-                        // env-steps/s, c6 140 -> 129 M -- the wave slots are worth more to the placement waves)
-#endif
+constexpr int MACS_SW = 4;   // stream waves per workgroup of the MACS fused steps (8, measured in round 5: c4 503 -> 330 M
+                             // env-steps/s, c6 140 -> 129 M -- the wave slots are worth more to the placement waves)
 // WC: 0, or the container's width known at compile time (tap_macs_place; BASELINE configs[3]'s W = 7 with its n = 20 window)
 template <int G, int NC, int MODE, int WC = 0>
-__global__ void __launch_bounds__((TransGeom<G, TAP_MACS_SW>::THREADS)) k_transition_macs(TransArgs a)
+__global__ void __launch_bounds__((TransGeom<G, MACS_SW>::THREADS)) k_transition_macs(TransArgs a)
 {
-    using Geo = TransGeom<G, TAP_MACS_SW>;
+    using Geo = TransGeom<G, MACS_SW>;
     constexpr int EPB = Geo::EPB, SPW = Geo::SPW, ENV_WAVES = Geo::ENV_WAVES;
     extern __shared__ float trans_lds[];
     // (the wave index stays a vector value here: in a scalar register -- transition.hip, where it is worth 4 % at c2 -- it
@@ -115,32 +113,11 @@ __global__ void __launch_bounds__((TransGeom<G, TAP_MACS_SW>::THREADS)) k_transi
 }
 
 // ---- and for MACS / MUL 3D (tap_macs3.h): G = 8..64 lanes per env --------------------------------
-// -DTAP_M3_SPREAD (A/B builds): ONE container per placement wave at G = 32 -- the wave's second lane group idles on an
-// out-of-range env -- so that B = 4096 puts four placement waves on a SIMD instead of two, each running only its own
-// container's loop trips.
-#ifdef TAP_M3_SPREAD
-template <int G> struct M3Spread { static constexpr bool on = G == 32; };
-#else
-template <int G> struct M3Spread { static constexpr bool on = false; };
-#endif
-template <int G> struct M3Geo {
-    using Geo = TransGeom<G, TAP_MACS_SW>;
-    static constexpr bool SPREAD = M3Spread<G>::on;
-    static constexpr int EPB = SPREAD ? 4 : Geo::EPB, SPW = SPREAD ? 2 : Geo::SPW, ENV_WAVES = SPREAD ? 4 : Geo::ENV_WAVES;
-    static constexpr int GROUPS = SPREAD ? 8 : Geo::EPB;                      // LDS regions (the idle halves get one too)
-    static constexpr int THREADS = SPREAD ? 384 : Geo::THREADS;              // 4 placement + 2 stream waves
-};
-
-#ifdef TAP_M3_CAP6
-#define M3_OCC __attribute__((amdgpu_waves_per_eu(6, 6)))
-#else
-#define M3_OCC
-#endif
 // WL: 0, or the side of a WL x WL container known at compile time (tap_macs3_place; instantiated for the reference's 5 x 5)
 template <int G, int NC, int MODE, int WL = 0>
-__global__ void __launch_bounds__((M3Geo<G>::THREADS)) M3_OCC k_transition_macs3(TransArgs a)
+__global__ void __launch_bounds__((TransGeom<G, MACS_SW>::THREADS)) k_transition_macs3(TransArgs a)
 {
-    using Geo = M3Geo<G>;
+    using Geo = TransGeom<G, MACS_SW>;
     constexpr int EPB = Geo::EPB, SPW = Geo::SPW, ENV_WAVES = Geo::ENV_WAVES;
     extern __shared__ float trans_lds[];
     // (the wave index stays a vector value here: in a scalar register -- transition.hip, where it is worth 4 % at c2 -- it
@@ -155,18 +132,17 @@ __global__ void __launch_bounds__((M3Geo<G>::THREADS)) M3_OCC k_transition_macs3
     __builtin_amdgcn_s_setprio(2);
     int *macs_base = reinterpret_cast<int *>(trans_lds + (size_t)EPB * 3 * a.m.nR);
     const int grp = tid / G;
-    const int env = Geo::SPREAD ? ((grp & 1) ? a.s.d.B : env_base + (grp >> 1)) : env_base + grp;
-    tap_macs3_wave<G, WL>(a.s, a.flags, a.ratio_out, env, tid % G, lane,
+    tap_macs3_wave<G, WL>(a.s, a.flags, a.ratio_out, env_base + grp, tid % G, lane,
                           macs_base + grp * macs3_group_words(G, a.s.d.n_max, a.s.d.H));
 }
 
 template <int G> static int launch_transition_macs3(tap_ctx *ctx, const TransArgs &a, hipStream_t st)
 {
-    constexpr int EPB = M3Geo<G>::EPB, THREADS = M3Geo<G>::THREADS;
+    constexpr int EPB = TransGeom<G, MACS_SW>::EPB, THREADS = TransGeom<G, MACS_SW>::THREADS;
     const int grid = (a.s.d.B + EPB - 1) / EPB;
     if (grid == 0) return TAP_OK;
     const size_t lds = (size_t)EPB * 3 * a.m.nR * sizeof(float) +
-                       (size_t)M3Geo<G>::GROUPS * macs3_group_words(G, a.s.d.n_max, a.s.d.H) * sizeof(int);
+                       (size_t)EPB * macs3_group_words(G, a.s.d.n_max, a.s.d.H) * sizeof(int);
     if (lds > tap_lds_limit(ctx)) return tap_fail(ctx, TAP_E_UNSUPPORTED, "transition(MACS 3D): %zu bytes of LDS needed", lds);
     const TapVariant v = tap_stream_variant(TAP_SV_MACS3, tap_mask_facts(a.m), TapLaunchFacts{3, G, EPB, a.s.d.B, a.s.d.W, a.s.d.L, false});
     return tap_launch_variant<TAP_SV_MACS3, 3, G>(ctx, "k_transition_macs3", v, a.m.wt, [&](auto k) -> int {
@@ -181,7 +157,7 @@ int tap_macs_validate(tap_ctx *ctx, const tap_env_desc &d); // macs.hip
 
 template <int G> static int launch_transition_macs(tap_ctx *ctx, const TransArgs &a, hipStream_t st)
 {
-    constexpr int EPB = TransGeom<G, TAP_MACS_SW>::EPB, THREADS = TransGeom<G, TAP_MACS_SW>::THREADS;
+    constexpr int EPB = TransGeom<G, MACS_SW>::EPB, THREADS = TransGeom<G, MACS_SW>::THREADS;
     const int grid = (a.s.d.B + EPB - 1) / EPB;
     if (grid == 0) return TAP_OK;
     const size_t lds = (size_t)EPB * 3 * a.m.nR * sizeof(float) +

@@ -84,6 +84,17 @@ def test_product_does_not_import_oracle():
                 assert not re.search(r"^\s*(from|import)\s+oracle", text, flags=re.M), f
 
 
+def test_product_library_reads_no_tuning_variable():
+    """csrc calls getenv in tap_ab_env alone (a null pointer unless -DTAP_AB_BUILD) and by name for the two variables the
+    parity tests route the product's fallback kernels with: a stray variable cannot change which kernel a job runs."""
+    csrc = os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "csrc")
+    text = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h")))
+    assert set(re.findall(r'getenv\("(\w+)"\)', text)) == {"TAP_NO_WAVE_KERNELS", "TAP_MACS2D_WAVE_FROM"}
+    assert "tap_ab_env(const char *name)\n{\n#ifdef TAP_AB_BUILD\n    return getenv(name);\n#else\n" in text
+    assert text.count("getenv(") == 3                        # the helper's and the two above
+    assert set(re.findall(r'tap_ab_env\("(\w+)"\)', text)) == {"TAP_AB_NO_TIE", "TAP_WRITE_THROUGH", "TAP_FORCE_G", "TAP_BIG_WG_THREADS"}
+
+
 def test_packdataset_layout(tmp_path):
     """PACKDataset rebuilt from the reference's text files gives the reference's tensors."""
     import golden_util as G
