@@ -140,7 +140,7 @@ extern "C" int tap_dyn_colsum(tap_ctx *ctx, int B, int n, int nR, int rows, cons
 
 extern "C" int tap_bits_words(int rows, int nR)
 {
-    if (rows < 1 || rows > 128 || nR < 1 || nR > 256 || nR % 4 != 0) return 0;
+    if (rows < 1 || nR < 1 || !tap_window_has_shadow(rows, nR)) return 0;
     return mask_bit_planes(rows) * nR;
 }
 
@@ -170,11 +170,12 @@ extern "C" int tap_mask_step_bits(tap_ctx *ctx, int B, int n, int R, int rows, i
     if (!bits_in || (ptr && (!static_ || static_rows < 1)) || update_rows < 0 || update_rows > 3 ||
         (!ptr && update_rows != 0) || bits_in == bits_out || (!bits_out && !dyn_out && !current_out && !mask_out))
         return tap_fail(ctx, TAP_E_INVALID, "bad mask_step_bits arguments");
-    MaskArgs a = mask_finish(MaskArgs{B, n, R, n * R, rows, update_rows, static_rows, nullptr, dyn_out, static_, ptr,
-                  mask_in, nullptr, nullptr, current_out, mask_out, bits_in, bits_out});
-    if (!mask_bits_ok(a))
-        return tap_fail(ctx, TAP_E_UNSUPPORTED, "bit shadow needs nR %% 4 == 0, nR <= 256, rows <= 128, 16-byte aligned buffers");
-    return launch_mask_step(ctx, a, (hipStream_t)stream);
+    MaskArgs a = mask_window(B, n, R, rows, update_rows, static_rows);
+    a.bits_in = bits_in; a.bits_out = bits_out; a.dyn_out = dyn_out;
+    a.static_ = static_; a.ptr = ptr; a.mask_in = mask_in; a.cur_out = current_out; a.mask_out = mask_out;
+    a = mask_finish(a);
+    rc = mask_bits_check(ctx, a);
+    return rc ? rc : launch_mask_step(ctx, a, (hipStream_t)stream);
 }
 
 extern "C" int tap_mask_step_first(tap_ctx *ctx, int B, int n, int R, int rows, int update_rows,
@@ -188,11 +189,12 @@ extern "C" int tap_mask_step_first(tap_ctx *ctx, int B, int n, int R, int rows, 
     if (!dyn_in || !bits_out || (ptr && (!static_ || static_rows < 1)) || update_rows < 0 || update_rows > 3 ||
         (!ptr && update_rows != 0) || dyn_in == dyn_out)
         return tap_fail(ctx, TAP_E_INVALID, "bad mask_step_first arguments");
-    MaskArgs a = mask_finish(MaskArgs{B, n, R, n * R, rows, update_rows, static_rows, dyn_in, dyn_out, static_, ptr,
-                  mask_in, nullptr, nullptr, current_out, mask_out, nullptr, bits_out, nonbinary_out});
-    if (!mask_bits_ok(a))
-        return tap_fail(ctx, TAP_E_UNSUPPORTED, "bit shadow needs nR %% 4 == 0, nR <= 256, rows <= 128, 16-byte aligned buffers");
-    return launch_mask_step(ctx, a, (hipStream_t)stream);
+    MaskArgs a = mask_window(B, n, R, rows, update_rows, static_rows);
+    a.dyn_in = dyn_in; a.bits_out = bits_out; a.dyn_out = dyn_out; a.nonbinary = nonbinary_out;
+    a.static_ = static_; a.ptr = ptr; a.mask_in = mask_in; a.cur_out = current_out; a.mask_out = mask_out;
+    a = mask_finish(a);
+    rc = mask_bits_check(ctx, a);
+    return rc ? rc : launch_mask_step(ctx, a, (hipStream_t)stream);
 }
 
 extern "C" int tap_update_dynamic(tap_ctx *ctx, int B, int n, int nR, int rows, int update_rows,
@@ -208,9 +210,9 @@ extern "C" int tap_update_dynamic(tap_ctx *ctx, int B, int n, int nR, int rows, 
     if (dyn_in == dyn_out) return tap_fail(ctx, TAP_E_INVALID, "update_dynamic is out of place (pack.py:370)");
     if ((colsum_in == nullptr) != (colsum_out == nullptr))
         return tap_fail(ctx, TAP_E_INVALID, "colsum_in and colsum_out go together");
-    MaskArgs a = mask_finish(MaskArgs{B, n, nR / n, nR, rows, update_rows, static_rows, dyn_in, dyn_out, static_, ptr,
-                  nullptr, colsum_in, colsum_out, nullptr, nullptr});
-    return launch_mask_step(ctx, a, (hipStream_t)stream);
+    MaskArgs a = mask_window(B, n, nR / n, rows, update_rows, static_rows);     // (check_shape: nR % n == 0)
+    a.dyn_in = dyn_in; a.dyn_out = dyn_out; a.static_ = static_; a.ptr = ptr; a.cs_in = colsum_in; a.cs_out = colsum_out;
+    return launch_mask_step(ctx, mask_finish(a), (hipStream_t)stream);
 }
 
 extern "C" int tap_update_mask(tap_ctx *ctx, int B, int n, int R, const float *mask_in,
@@ -221,9 +223,9 @@ extern "C" int tap_update_mask(tap_ctx *ctx, int B, int n, int R, const float *m
     if (B == 0) return TAP_OK;
     if (!colsum || (!current_out && !mask_out)) return tap_fail(ctx, TAP_E_INVALID, "null pointer");
     if (ptr && !mask_in) return tap_fail(ctx, TAP_E_INVALID, "update_mask needs mask_in");
-    MaskArgs a = mask_finish(MaskArgs{B, n, R, n * R, 3 * n, 0, 0, nullptr, nullptr, nullptr, ptr, mask_in, colsum,
-                  nullptr, current_out, mask_out});
-    return launch_mask_step(ctx, a, (hipStream_t)stream);
+    MaskArgs a = mask_window(B, n, R, 3 * n, 0, 0);
+    a.ptr = ptr; a.mask_in = mask_in; a.cs_in = colsum; a.cur_out = current_out; a.mask_out = mask_out;
+    return launch_mask_step(ctx, mask_finish(a), (hipStream_t)stream);
 }
 
 extern "C" int tap_mask_step(tap_ctx *ctx, int B, int n, int R, int rows, int update_rows,
@@ -239,7 +241,8 @@ extern "C" int tap_mask_step(tap_ctx *ctx, int B, int n, int R, int rows, int up
         !current_out || !mask_out || static_rows < 1 || update_rows < 0 || update_rows > 3)
         return tap_fail(ctx, TAP_E_INVALID, "bad mask_step arguments");
     if (dyn_in == dyn_out) return tap_fail(ctx, TAP_E_INVALID, "mask_step is out of place (pack.py:370)");
-    MaskArgs a = mask_finish(MaskArgs{B, n, R, n * R, rows, update_rows, static_rows, dyn_in, dyn_out, static_, ptr,
-                  mask_in, colsum_in, colsum_out, current_out, mask_out});
-    return launch_mask_step(ctx, a, (hipStream_t)stream);
+    MaskArgs a = mask_window(B, n, R, rows, update_rows, static_rows);
+    a.dyn_in = dyn_in; a.dyn_out = dyn_out; a.cs_in = colsum_in; a.cs_out = colsum_out;
+    a.static_ = static_; a.ptr = ptr; a.mask_in = mask_in; a.cur_out = current_out; a.mask_out = mask_out;
+    return launch_mask_step(ctx, mask_finish(a), (hipStream_t)stream);
 }

@@ -1367,7 +1367,7 @@ static int rolling_window_impl(tap_ctx *ctx, int B, int D, int N, int child, con
     a.remove_ptr = remove_ptr; a.static_out = static_out; a.dynamic_out = dynamic_out;
     a.colsum_out = colsum_out; a.cur_mask_out = current_mask_out; a.nodes_out = nodes_out; a.err_out = err_out;
     a.bits_out = reinterpret_cast<unsigned long long *>(bits_out);
-    if (bits_out && (3 * child > 64 || (child * (D == 2 ? 2 : 6)) % 4 != 0 || child * (D == 2 ? 2 : 6) > 256))
+    if (bits_out && (3 * child > 64 || !tap_window_has_shadow(3 * child, child * (D == 2 ? 2 : 6))))
         return tap_fail(ctx, TAP_E_UNSUPPORTED, "bits_out needs 3*child <= 64, (child*R) %% 4 == 0, child*R <= 256");
     const int grid = (B + TAP_BLOCK / 64 - 1) / (TAP_BLOCK / 64);
     if (grid == 0) return TAP_OK;
@@ -1440,6 +1440,11 @@ struct RollAux {
     const int32_t *nodes_cur;
     int tour_stride, tour_col;
 };
+static void roll_aux_into(StepArgs &s, const RollAux &aux, int child)
+{
+    s.dec_static_out = aux.dec_static_out; s.tour_out = aux.tour_out; s.picked_out = aux.picked_out;
+    s.nodes_cur = aux.nodes_cur; s.child = child; s.tour_stride = aux.tour_stride; s.tour_col = aux.tour_col;
+}
 
 static int rolling_step_impl(tap_ctx *ctx, const tap_env_desc *d, void *env_state, int N, int child,
                              const int32_t *blocks, const uint64_t *rel, uint64_t *state,
@@ -1466,8 +1471,7 @@ static int rolling_step_impl(tap_ctx *ctx, const tap_env_desc *d, void *env_stat
         if (rc == TAP_OK && aux) {
             StepArgs s = {};
             s.d = *d; s.static_ = static_cur; s.static_rows = 1 + d->D; s.nR = child * (d->D == 2 ? 2 : 6); s.ptr = ptr;
-            s.dec_static_out = aux->dec_static_out; s.tour_out = aux->tour_out; s.picked_out = aux->picked_out;
-            s.nodes_cur = aux->nodes_cur; s.child = child; s.tour_stride = aux->tour_stride; s.tour_col = aux->tour_col;
+            roll_aux_into(s, *aux, child);
             rc = tap_step_aux_launch(ctx, s, (hipStream_t)stream);
         }
         return rc ? rc : rolling_window_impl(ctx, d->B, d->D, N, child, blocks, rel, state, ptr, static_next, dynamic_out,
@@ -1483,29 +1487,15 @@ static int rolling_step_impl(tap_ctx *ctx, const tap_env_desc *d, void *env_stat
     a.r.remove_ptr = ptr; a.r.static_out = static_next; a.r.dynamic_out = dynamic_out;
     a.r.colsum_out = colsum_out; a.r.cur_mask_out = current_mask_out; a.r.nodes_out = nodes_out; a.r.err_out = err_out;
     a.r.bits_out = reinterpret_cast<unsigned long long *>(bits_out);
-    if (bits_out && (3 * child > 64 || (child * R) % 4 != 0 || child * R > 256))
+    if (bits_out && (3 * child > 64 || !tap_window_has_shadow(3 * child, child * R)))
         return tap_fail(ctx, TAP_E_UNSUPPORTED, "bits_out needs 3*child <= 64, (child*R) %% 4 == 0, child*R <= 256");
     a.s.d = *d;
     tap_env_layout(d, env_state, &a.s.v);
     a.s.static_ = static_cur; a.s.static_rows = 1 + d->D; a.s.nR = child * R; a.s.ptr = ptr;
     a.s.feature_out = feature_out; a.s.flen = tap_env_feature_len(d);
     a.s.lut = ctx ? ctx->stab_lut : nullptr;
-    if (aux) {
-        a.s.dec_static_out = aux->dec_static_out; a.s.tour_out = aux->tour_out; a.s.picked_out = aux->picked_out;
-        a.s.nodes_cur = aux->nodes_cur; a.s.child = child; a.s.tour_stride = aux->tour_stride; a.s.tour_col = aux->tour_col;
-    }
-    const int Gs = tap_group_size(d);
-    hipStream_t st = (hipStream_t)stream;
-    if (d->D == 2) {
-        if (Gs == 8) return launch_rolling_step<2, 8>(ctx, a, st);
-        if (Gs == 16) return launch_rolling_step<2, 16>(ctx, a, st);
-        if (Gs == 32) return launch_rolling_step<2, 32>(ctx, a, st);
-        return launch_rolling_step<2, 64>(ctx, a, st);
-    }
-    if (Gs == 8) return launch_rolling_step<3, 8>(ctx, a, st);
-    if (Gs == 16) return launch_rolling_step<3, 16>(ctx, a, st);
-    if (Gs == 32) return launch_rolling_step<3, 32>(ctx, a, st);
-    return launch_rolling_step<3, 64>(ctx, a, st);
+    if (aux) roll_aux_into(a.s, *aux, child);
+    TAP_DISPATCH_DG(launch_rolling_step, d, ctx, a, (hipStream_t)stream);
 }
 
 extern "C" int tap_rolling_step(tap_ctx *ctx, const tap_env_desc *d, void *env_state, int N, int child,

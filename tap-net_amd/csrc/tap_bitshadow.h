@@ -22,8 +22,8 @@ inline bool tap_any_misaligned(TapPtrList ps, unsigned to)
     for (const void *p : ps) bad = bad || tap_misaligned(p, to);
     return bad;
 }
-// a (rows, nR) window has a bit shadow: rows <= 128, nR % 4 == 0, nR <= 256 (masks.hip: tap_bits_words)
-inline bool tap_has_bit_shadow(int rows, int nR) { return tap_bits_words(rows, nR) > 0; }
+// a (rows, nR) window has a bit shadow (tap_step_request.h); a shape that is not positive has none
+inline bool tap_has_bit_shadow(int rows, int nR) { return rows >= 1 && nR >= 1 && tap_window_has_shadow(rows, nR); }
 inline int tap_bit_planes(int rows) { return rows > 64 ? 2 : 1; }
 
 // ---- device -------------------------------------------------------------------------------------------------------

@@ -11,6 +11,7 @@
 #include <mutex>
 
 #include "tapenv.h"
+#include "tap_step_request.h"
 #include "tap_stream_variant.h"
 
 constexpr int TAP_CHK_SLOTS = 64;
@@ -173,24 +174,11 @@ struct EnvView {
 
 inline size_t tap_align256(size_t x) { return (x + 255) & ~size_t(255); }
 
-// LB_GREEDY containers beyond the lane-per-cell kernels (more than 64 cells, or a 3D side above 8): big.hip, up to
-// TAP_BIG_WG_CELLS cells (above 4 096: one workgroup per container with the height-map in its LDS)
-constexpr int TAP_BIG_WG_CELLS = 16384;
-inline bool tap_is_big(const tap_env_desc *d)
-{
-    return d->strategy == TAP_LB_GREEDY && (d->W * d->L > 64 || (d->D == 3 && (d->W > 8 || d->L > 8)));
-}
-
+// (tap_is_big and tap_is_big_macs3, the containers beyond the lane-per-cell kernels: tap_step_request.h)
 // MACS / MUL 2D containers beyond the lane-per-column kernels (more than 64 columns): macs_big.hip, one thread per
 // container with its candidate lists in a scratch section of the blob
 inline bool tap_is_big_macs(const tap_env_desc *d) { return d->strategy == TAP_MACS && d->D == 2 && d->W > 64; }
 size_t tap_macs_big_scratch_ints(const tap_env_desc *d);   // macs_big.hip
-// MACS / MUL 3D containers beyond the lane-per-cell kernel (more than 64 cells or a side above 8): macs3_big.hip, one
-// thread per container on the same state (height-map, history, free-list bit-grid) + candidate lists in the scratch section
-inline bool tap_is_big_macs3(const tap_env_desc *d)
-{
-    return d->strategy == TAP_MACS && d->D == 3 && (d->W * d->L > 64 || d->W > 8 || d->L > 8);
-}
 size_t tap_macs3_big_scratch_ints(const tap_env_desc *d);  // macs3_big.hip
 
 inline size_t tap_env_layout(const tap_env_desc *d, void *base, EnvView *v)

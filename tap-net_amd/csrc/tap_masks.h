@@ -67,6 +67,25 @@ inline MaskArgs mask_finish(MaskArgs a)
     return a;
 }
 
+// A MaskArgs is built by NAME (host): the window here, every buffer by an assignment at the caller, then mask_finish().
+// A pointer in the wrong slot is a GPU memory fault, not an exception, so no caller counts positions.
+inline MaskArgs mask_window(int B, int n, int R, int rows, int update_rows, int static_rows)
+{
+    MaskArgs a = {};
+    a.B = B; a.n = n; a.R = R; a.nR = n * R; a.rows = rows; a.update_rows = update_rows; a.static_rows = static_rows;
+    return a;
+}
+// a fused step's (tap_step_request.h: the fields a form does not use are null in the request, and stay null here);
+// `inplace` is not copied: only the route that knows the mode sets it (transition.hip: transition_impl)
+inline MaskArgs mask_args(const TapStepRequest &r, int B)
+{
+    MaskArgs a = mask_window(B, r.n, r.R, r.rows, r.update_rows, r.static_rows);
+    a.dyn_in = r.dyn_in; a.dyn_out = r.dyn_out; a.static_ = r.static_; a.ptr = r.ptr; a.mask_in = r.mask_in;
+    a.cs_in = r.colsum_in; a.cs_out = r.colsum_out; a.cur_out = r.current_out; a.mask_out = r.mask_out;
+    a.bits_in = r.bits_in; a.bits_out = r.bits_out; a.nonbinary = r.nonbinary_out;
+    return mask_finish(a);
+}
+
 // ---- which rows a lane expands, and when (round 5) ------------------------------------------------------------
 // The expansion's store instructions cover K = rp * (nR/4) consecutive float4 (rp whole rows) of a slab, but a
 // slab of rows * nR * 4 bytes starts wherever the previous one ended: at c2 (2 400 B) three slabs in four start 32
@@ -1268,10 +1287,16 @@ __device__ __forceinline__ void stream_wave_bits2(const MaskArgs &a, int env, in
 // carries the step), 65 .. 128: two (masks.hip's stand-alone step; the fused entry points run it as their first launch)
 inline bool mask_bits_ok(const MaskArgs &a)
 {
-    return (a.bits_in || mask_builds_bits(a)) && (a.ptr == nullptr || a.static_ != nullptr) && (a.nR % 4 == 0) &&
-           a.nR <= 256 && a.rows >= 1 && a.rows <= 128 &&
+    return (a.bits_in || mask_builds_bits(a)) && (a.ptr == nullptr || a.static_ != nullptr) && a.rows >= 1 &&
+           tap_window_has_shadow(a.rows, a.nR) &&
            ((reinterpret_cast<uintptr_t>(a.dyn_out) | reinterpret_cast<uintptr_t>(a.dyn_in)) % 16 == 0) &&
            ((reinterpret_cast<uintptr_t>(a.bits_in) | reinterpret_cast<uintptr_t>(a.bits_out)) % 16 == 0);
+}
+// the refusal of a launch on the bit shadow, for every entry point that makes one
+inline int mask_bits_check(tap_ctx *ctx, const MaskArgs &a)
+{
+    if (mask_bits_ok(a)) return TAP_OK;
+    return tap_fail(ctx, TAP_E_UNSUPPORTED, "bit shadow needs nR %% 4 == 0, nR <= 256, rows <= 128, 16-byte aligned buffers");
 }
 
 // columns per lane the fast path needs: 1, 2 or 4; 0 = use the generic element-wise path

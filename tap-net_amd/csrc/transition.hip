@@ -109,23 +109,14 @@ bool tap_macs3_wave_transition_ok(const tap_ctx *ctx, const tap_env_desc *d, int
 int tap_macs3_wave_transition(tap_ctx *ctx, const tap_env_desc *d, const TransArgs &a, hipStream_t st);
 int tap_macs2d_wave_from();                                                                                 // macs.hip
 
-// 0: no wave-per-container fused step; 1: big.hip (LB_GREEDY, handles fresh / ratio itself); 2 / 3: MACS 2D / 3D
-static int transition_wave_kind(const tap_ctx *ctx, const tap_env_desc *d, int nR, int rows)
-{
-    if (rows > 64) return 0;                                                      // the fused kernels carry the one-word shadow only
-    if (tap_is_big(d)) return tap_big_transition_ok(ctx, d, nR) ? 1 : 0;
-    if (d->strategy != TAP_MACS) return 0;
-    if (d->D == 2) return (d->W > 16 && d->W >= tap_macs2d_wave_from() && tap_macs_wave_transition_ok(ctx, d, nR)) ? 2 : 0;
-    return (tap_is_big_macs3(d) && tap_macs3_wave_transition_ok(ctx, d, nR)) ? 3 : 0;
-}
-
 // the step of a wave-per-container shape on the bit shadow: a.m is filled in
-static int transition_wave_launch(tap_ctx *ctx, const tap_env_desc *d, void *state, const TransArgs &a, int kind, void *stream)
+static int transition_wave_launch(tap_ctx *ctx, const tap_env_desc *d, void *state, const TransArgs &a, TapStepRoute route, void *stream)
 {
-    if (kind == 1) return tap_big_transition(ctx, d, a, (hipStream_t)stream);
+    if (route == TAP_ROUTE_WAVE_BIG) return tap_big_transition(ctx, d, a, (hipStream_t)stream);      // handles fresh / ratio itself
     int rc = TAP_OK;
     if ((a.flags & TAP_T_FRESH) && (rc = tap_env_reset(ctx, d, state, stream)) != TAP_OK) return rc;
-    rc = kind == 2 ? tap_macs_wave_transition(ctx, d, a, (hipStream_t)stream) : tap_macs3_wave_transition(ctx, d, a, (hipStream_t)stream);
+    rc = route == TAP_ROUTE_WAVE_MACS2 ? tap_macs_wave_transition(ctx, d, a, (hipStream_t)stream)
+                                       : tap_macs3_wave_transition(ctx, d, a, (hipStream_t)stream);
     if (rc == TAP_OK && (a.flags & TAP_T_RATIO)) rc = tap_env_ratio(ctx, d, state, a.ratio_out, nullptr, nullptr, stream);
     return rc;
 }
@@ -157,38 +148,35 @@ template <int D, int G> static int launch_transition(tap_ctx *ctx, const TransAr
     return launch_transition_v<D, G, (D == 3 ? 8 : 4)>(ctx, a, st);
 }
 
-static int transition_dispatch(tap_ctx *ctx, const tap_env_desc *d, const TransArgs &a, void *stream);
-
-// Shapes and strategies whose placement is one THREAD per container (legacy 'LB', LB_GREEDY and MACS 3D above 64
-// cells or with a 3D side above 8) or the wide MACS 2D form (17 .. 64 columns): no single kernel carries both halves of the step.  (For
-// wide MACS one was built and measured in round 3 -- tap_macs_wide_wave as the placement waves of a k_transition_macs
-// look-alike: 121 against 97 us per step at W = 20, n = 12, B = 8192, equal at W = 40: the placement is ~100 us of
-// register-heavy work, the stream waves hide nothing and their wave slots cost a quarter of the resident envs.)
-// The tap_transition* entry points then run the same step as its two launches (precedence update, placement) plus
-// reset / calc_ratio where the flags ask for them, so a caller drives every shape through one entry point.
-static bool transition_single_kernel(const tap_ctx *ctx, const tap_env_desc *d, int nR)
+// the lane-per-cell fused kernels (tap_step_request.h: TAP_ROUTE_FUSED)
+static int transition_dispatch(tap_ctx *ctx, const tap_env_desc *d, const TransArgs &a, void *stream)
 {
-    if (d->strategy == TAP_LB || tap_is_big(d) || tap_is_big_macs3(d) || (d->strategy == TAP_MACS && d->D == 2 && d->W > 16)) return false;
-    if (d->strategy == TAP_MACS) {
-        // the MACS placement keeps its lists in LDS: a container too tall (or an episode too long) for one workgroup's
-        // LDS (160 KiB on gfx950) next to the stream tiles takes the two launches as well (the stand-alone step runs
-        // fewer envs per workgroup)
+    if (d->strategy == TAP_MACS) return tap_transition_macs_launch(ctx, d, a, (hipStream_t)stream);
+    TAP_DISPATCH_DG(launch_transition, d, ctx, a, (hipStream_t)stream);
+}
+
+// What tap_step_route asks of the families' files (tap_step_request.h: TapStepCaps), each asked of the family whose
+// container this is: the wave kernels' own fits, and for the MACS lane kernels, which keep their lists in LDS, whether a
+// workgroup's envs fit its LDS (160 KiB on gfx950) next to the stream tiles
+static TapStepCaps transition_caps(const tap_ctx *ctx, const tap_env_desc *d, int nR)
+{
+    TapStepCaps c = {};
+    c.macs2d_wave_from = tap_macs2d_wave_from();
+    if (tap_is_big(d)) c.big_ok = tap_big_transition_ok(ctx, d, nR);
+    else if (d->strategy != TAP_MACS) return c;
+    else if (d->D == 2 && d->W > 16) c.macs_wave_ok = tap_macs_wave_transition_ok(ctx, d, nR);
+    else if (tap_is_big_macs3(d)) c.macs3_wave_ok = tap_macs3_wave_transition_ok(ctx, d, nR);
+    else {
         const int G = tap_group_size(d), epb = G == 64 ? 4 : 8;
         const size_t words = d->D == 3 ? (size_t)macs3_group_words(G, d->n_max, d->H)
                                        : (size_t)macs_group_words(d->W <= 8 ? 8 : 16, d->H, d->n_max, d->W);
-        if ((size_t)epb * 3 * nR * sizeof(float) + (size_t)epb * words * sizeof(int) > tap_lds_limit(ctx)) return false;
+        c.macs_lanes_fit = (size_t)epb * 3 * nR * sizeof(float) + (size_t)epb * words * sizeof(int) <= tap_lds_limit(ctx);
     }
-    return true;
+    return c;
 }
 
-// The by-products a decoding loop wants from the step's gather (tap_common.h: StepArgs::dec_static_out / tour_out):
-// the fused kernels' placement waves write them; for the shapes that run as two launches this kernel does.
-struct StepAux {
-    float *dec_static_out;
-    int64_t *tour_out;
-    int tour_stride, tour_col;
-};
-
+// the by-products a decoding loop wants from the step's gather, for the shapes that run as two launches (the fused
+// kernels' placement waves write them: tap_common.h, tap_step_aux)
 __global__ void __launch_bounds__(TAP_BLOCK) k_step_aux(StepArgs s)
 {
     const int env = blockIdx.x * TAP_BLOCK + threadIdx.x;
@@ -215,8 +203,9 @@ int tap_step_aux_launch(tap_ctx *ctx, const StepArgs &s, hipStream_t st)
 extern "C" int tap_transition_launches(const tap_ctx *ctx, const tap_env_desc *d, int n, int R, int rows, int on_bits)
 {
     if (!d || n < 1 || R < 1 || rows < 1) return TAP_E_INVALID;
-    if (on_bits && transition_wave_kind(ctx, d, n * R, rows)) return 1;
-    return (transition_single_kernel(ctx, d, n * R) && (!on_bits || rows <= 64)) ? 1 : 2;
+    TapStepRequest r = {};
+    r.form = on_bits ? TAP_STEP_BITS : TAP_STEP_COPY; r.rows = rows;
+    return tap_step_route_launches(tap_step_route(r, *d, transition_caps(ctx, d, n * R)));
 }
 
 static int transition_tail(tap_ctx *ctx, const tap_env_desc *d, void *state, const TransArgs &a, void *stream)
@@ -226,59 +215,43 @@ static int transition_tail(tap_ctx *ctx, const tap_env_desc *d, void *state, con
     return rc ? rc : tap_step_aux_launch(ctx, a.s, (hipStream_t)stream);
 }
 
-static int transition_common(tap_ctx *ctx, const tap_env_desc *d, void *state, int n, int R, int rows,
-                             int update_rows, const float *static_, int static_rows, const int64_t *ptr,
-                             const float *mask_in, float *current_out, float *mask_out, float *feature_out,
-                             float *ratio_out, int flags, TransArgs &a, const StepAux *aux = nullptr)
+// One step, whatever its form and its caller: check, route, then the wave launch, the fused dispatch or the two launches.
+static int transition_impl(tap_ctx *ctx, const tap_env_desc *d, void *state, const TapStepRequest &r, bool from_stepper, void *stream)
 {
     int rc = tap_desc_validate(ctx, d);
-    if (rc) return rc;
-    if (d->B == 0) return TAP_OK; // an empty batch has no buffers to check
+    if (rc || d->B == 0) return rc;     // an empty batch has no buffers to check
     if (d->strategy == TAP_MACS && (rc = tap_macs_validate(ctx, *d)) != TAP_OK) return rc;
-    // mask_in null = ones (the mask DRL.forward starts from, model.py:297): only the stepper's first step passes it
-    if (!state || !static_ || !ptr || (!mask_in && !aux) || !current_out || !mask_out || n < 1 || R < 1 || rows < 1 ||
-        static_rows < 1 + d->D || update_rows < 0 || update_rows > 3 || ((flags & TAP_T_RATIO) && !ratio_out))
-        return tap_fail(ctx, TAP_E_INVALID, "bad transition arguments");
+    const TapStepVerdict v = tap_step_request_check(r, d->B, d->D, from_stepper, state != nullptr);
+    if (v.status != TAP_OK) return tap_fail(ctx, v.status, "%s", v.msg);
+    TransArgs a = {};
     a.s.d = *d;
     tap_env_layout(d, state, &a.s.v);
-    a.s.static_ = static_; a.s.static_rows = static_rows; a.s.nR = n * R; a.s.ptr = ptr;
-    a.s.feature_out = feature_out; a.s.flen = tap_env_feature_len(d);
+    a.s.static_ = r.static_; a.s.static_rows = r.static_rows; a.s.nR = r.n * r.R; a.s.ptr = r.ptr;
+    a.s.feature_out = r.feature_out; a.s.flen = tap_env_feature_len(d);
     a.s.lut = ctx ? ctx->stab_lut : nullptr;
-    a.flags = flags;
-    a.ratio_out = ratio_out;
-    if (aux) {
-        a.s.dec_static_out = aux->dec_static_out;
-        a.s.tour_out = aux->tour_out;
-        a.s.tour_stride = aux->tour_stride;
-        a.s.tour_col = aux->tour_col;
-    }
-    return TAP_OK;
-}
+    a.s.dec_static_out = r.aux.dec_static_out; a.s.tour_out = r.aux.tour_out;
+    a.s.tour_stride = r.aux.tour_stride; a.s.tour_col = r.aux.tour_col;
+    a.flags = r.flags;
+    a.ratio_out = r.ratio_out;
 
-static int transition_copy_impl(tap_ctx *ctx, const tap_env_desc *d, void *state, int n, int R, int rows,
-                                int update_rows, const float *dyn_in, const float *static_,
-                                int static_rows, const int64_t *ptr, const float *mask_in,
-                                const float *colsum_in, float *dyn_out, float *colsum_out,
-                                float *current_out, float *mask_out, float *feature_out,
-                                float *ratio_out, int flags, void *stream, const StepAux *aux)
-{
-    if (d && d->B == 0) return tap_desc_validate(ctx, d); // an empty batch has no buffers to check
-    TransArgs a = {};
-    int rc = transition_common(ctx, d, state, n, R, rows, update_rows, static_, static_rows, ptr, mask_in,
-                               current_out, mask_out, feature_out, ratio_out, flags, a, aux);
-    if (rc) return rc;
-    if (!dyn_in || !colsum_in || !dyn_out || !colsum_out)
-        return tap_fail(ctx, TAP_E_INVALID, "bad transition arguments");
-    if (dyn_in == dyn_out) return tap_fail(ctx, TAP_E_INVALID, "transition is out of place (pack.py:370)");
-    if (!transition_single_kernel(ctx, d, n * R)) {
-        if ((flags & TAP_T_FRESH) && (rc = tap_env_reset(ctx, d, state, stream)) != TAP_OK) return rc;
-        rc = tap_mask_step(ctx, d->B, n, R, rows, update_rows, dyn_in, static_, static_rows, ptr, mask_in, colsum_in, dyn_out,
-                           colsum_out, current_out, mask_out, stream);
+    const TapStepRoute route = tap_step_route(r, *d, transition_caps(ctx, d, r.n * r.R));
+    if (route == TAP_ROUTE_TWO_LAUNCHES) {
+        if ((r.flags & TAP_T_FRESH) && (rc = tap_env_reset(ctx, d, state, stream)) != TAP_OK) return rc;
+        if (r.form == TAP_STEP_COPY)
+            rc = tap_mask_step(ctx, d->B, r.n, r.R, r.rows, r.update_rows, r.dyn_in, r.static_, r.static_rows, r.ptr, r.mask_in,
+                               r.colsum_in, r.dyn_out, r.colsum_out, r.current_out, r.mask_out, stream);
+        else if (r.form == TAP_STEP_BITS)
+            rc = tap_mask_step_bits(ctx, d->B, r.n, r.R, r.rows, r.update_rows, r.bits_in, r.static_, r.static_rows, r.ptr, r.mask_in,
+                                    r.bits_out, r.dyn_out, r.current_out, r.mask_out, stream);
+        else
+            rc = tap_mask_step_first(ctx, d->B, r.n, r.R, r.rows, r.update_rows, r.dyn_in, r.static_, r.static_rows, r.ptr, r.mask_in,
+                                     r.bits_out, r.dyn_out, r.current_out, r.mask_out, r.nonbinary_out, stream);
         return rc ? rc : transition_tail(ctx, d, state, a, stream);
     }
-    a.m = mask_finish(MaskArgs{d->B, n, R, n * R, rows, update_rows, static_rows, dyn_in, dyn_out, static_, ptr,
-                   mask_in, colsum_in, colsum_out, current_out, mask_out, nullptr, nullptr});
-    return transition_dispatch(ctx, d, a, stream);
+    a.m = mask_args(r, d->B);
+    if (route == TAP_ROUTE_FUSED) a.m.inplace = (r.inplace && r.dyn_out) ? 1 : 0;
+    if (r.form != TAP_STEP_COPY && (rc = mask_bits_check(ctx, a.m)) != TAP_OK) return rc;
+    return route == TAP_ROUTE_FUSED ? transition_dispatch(ctx, d, a, stream) : transition_wave_launch(ctx, d, state, a, route, stream);
 }
 
 extern "C" int tap_transition(tap_ctx *ctx, const tap_env_desc *d, void *state, int n, int R, int rows,
@@ -288,46 +261,15 @@ extern "C" int tap_transition(tap_ctx *ctx, const tap_env_desc *d, void *state, 
                               float *current_out, float *mask_out, float *feature_out,
                               float *ratio_out, int flags, void *stream)
 {
-    if (d && d->B > 0 && !mask_in) return tap_fail(ctx, TAP_E_INVALID, "bad transition arguments");
-    return transition_copy_impl(ctx, d, state, n, R, rows, update_rows, dyn_in, static_, static_rows, ptr, mask_in, colsum_in,
-                                dyn_out, colsum_out, current_out, mask_out, feature_out, ratio_out, flags, stream, nullptr);
-}
-
-static int transition_bits_impl(tap_ctx *ctx, const tap_env_desc *d, void *state, int n, int R, int rows,
-                                int update_rows, const unsigned long long *bits_in, const float *static_,
-                                int static_rows, const int64_t *ptr, const float *mask_in,
-                                unsigned long long *bits_out, float *dyn_out, float *current_out,
-                                float *mask_out, float *feature_out, float *ratio_out, int flags,
-                                void *stream, const StepAux *aux, int inplace = 0)
-{
-    // inplace: dyn_out holds update_dynamic's INPUT (the stepper's previous step wrote it there) -- the lane-per-cell fused
-    // kernels then write the cleared rows only; the other paths below write the whole tensor, which is the same tensor
-    if (d && d->B == 0) return tap_desc_validate(ctx, d); // an empty batch has no buffers to check
-    TransArgs a = {};
-    int rc = transition_common(ctx, d, state, n, R, rows, update_rows, static_, static_rows, ptr, mask_in,
-                               current_out, mask_out, feature_out, ratio_out, flags, a, aux);
-    if (rc) return rc;
-    if (!bits_in || !bits_out || bits_in == bits_out)
-        return tap_fail(ctx, TAP_E_INVALID, "bad transition_bits arguments");
-    if (const int kind = transition_wave_kind(ctx, d, n * R, rows)) {
-        a.m = mask_finish(MaskArgs{d->B, n, R, n * R, rows, update_rows, static_rows, nullptr, dyn_out, static_, ptr,
-                       mask_in, nullptr, nullptr, current_out, mask_out, bits_in, bits_out});
-        if (!mask_bits_ok(a.m))
-            return tap_fail(ctx, TAP_E_UNSUPPORTED, "bit shadow needs nR %% 4 == 0, nR <= 256, rows <= 128, 16-byte aligned buffers");
-        return transition_wave_launch(ctx, d, state, a, kind, stream);
-    }
-    if (!transition_single_kernel(ctx, d, n * R) || rows > 64) {      // the fused kernels carry the one-word shadow only
-        if ((flags & TAP_T_FRESH) && (rc = tap_env_reset(ctx, d, state, stream)) != TAP_OK) return rc;
-        rc = tap_mask_step_bits(ctx, d->B, n, R, rows, update_rows, bits_in, static_, static_rows, ptr, mask_in, bits_out,
-                                dyn_out, current_out, mask_out, stream);
-        return rc ? rc : transition_tail(ctx, d, state, a, stream);
-    }
-    a.m = mask_finish(MaskArgs{d->B, n, R, n * R, rows, update_rows, static_rows, nullptr, dyn_out, static_, ptr,
-                   mask_in, nullptr, nullptr, current_out, mask_out, bits_in, bits_out});
-    a.m.inplace = (inplace && dyn_out) ? 1 : 0;
-    if (!mask_bits_ok(a.m))
-        return tap_fail(ctx, TAP_E_UNSUPPORTED, "bit shadow needs nR %% 4 == 0, nR <= 256, rows <= 128, 16-byte aligned buffers");
-    return transition_dispatch(ctx, d, a, stream);
+    TapStepRequest r = {};
+    r.form = TAP_STEP_COPY;
+    r.n = n; r.R = R; r.rows = rows; r.update_rows = update_rows; r.static_rows = static_rows; r.flags = flags;
+    r.dyn_in = dyn_in; r.static_ = static_; r.ptr = ptr; r.mask_in = mask_in; r.colsum_in = colsum_in;
+    r.dyn_out = dyn_out; r.colsum_out = colsum_out; r.current_out = current_out; r.mask_out = mask_out;
+    r.feature_out = feature_out; r.ratio_out = ratio_out;
+    // (this entry point has always asked for its mask ahead of the descriptor's checks)
+    if (d && d->B > 0 && !mask_in) return tap_fail(ctx, TAP_E_INVALID, "%s", tap_step_request_check(r, d->B, d->D, false, state != nullptr).msg);
+    return transition_impl(ctx, d, state, r, false, stream);
 }
 
 extern "C" int tap_transition_bits(tap_ctx *ctx, const tap_env_desc *d, void *state, int n, int R, int rows,
@@ -337,41 +279,13 @@ extern "C" int tap_transition_bits(tap_ctx *ctx, const tap_env_desc *d, void *st
                                    float *mask_out, float *feature_out, float *ratio_out, int flags,
                                    void *stream)
 {
-    return transition_bits_impl(ctx, d, state, n, R, rows, update_rows, bits_in, static_, static_rows, ptr, mask_in, bits_out,
-                                dyn_out, current_out, mask_out, feature_out, ratio_out, flags, stream, nullptr);
-}
-
-static int transition_first_impl(tap_ctx *ctx, const tap_env_desc *d, void *state, int n, int R, int rows,
-                                 int update_rows, const float *dyn_in, const float *static_, int static_rows,
-                                 const int64_t *ptr, const float *mask_in, unsigned long long *bits_out,
-                                 float *dyn_out, float *current_out, float *mask_out, float *feature_out,
-                                 float *ratio_out, int32_t *nonbinary_out, int flags, void *stream, const StepAux *aux)
-{
-    if (d && d->B == 0) return tap_desc_validate(ctx, d); // an empty batch has no buffers to check
-    TransArgs a = {};
-    int rc = transition_common(ctx, d, state, n, R, rows, update_rows, static_, static_rows, ptr, mask_in,
-                               current_out, mask_out, feature_out, ratio_out, flags, a, aux);
-    if (rc) return rc;
-    if (!dyn_in || !bits_out || dyn_in == dyn_out)
-        return tap_fail(ctx, TAP_E_INVALID, "bad transition_first arguments");
-    if (const int kind = transition_wave_kind(ctx, d, n * R, rows)) {
-        a.m = mask_finish(MaskArgs{d->B, n, R, n * R, rows, update_rows, static_rows, dyn_in, dyn_out, static_, ptr,
-                       mask_in, nullptr, nullptr, current_out, mask_out, nullptr, bits_out, nonbinary_out});
-        if (!mask_bits_ok(a.m))
-            return tap_fail(ctx, TAP_E_UNSUPPORTED, "bit shadow needs nR %% 4 == 0, nR <= 256, rows <= 128, 16-byte aligned buffers");
-        return transition_wave_launch(ctx, d, state, a, kind, stream);
-    }
-    if (!transition_single_kernel(ctx, d, n * R) || rows > 64) {
-        if ((flags & TAP_T_FRESH) && (rc = tap_env_reset(ctx, d, state, stream)) != TAP_OK) return rc;
-        rc = tap_mask_step_first(ctx, d->B, n, R, rows, update_rows, dyn_in, static_, static_rows, ptr, mask_in, bits_out,
-                                 dyn_out, current_out, mask_out, nonbinary_out, stream);
-        return rc ? rc : transition_tail(ctx, d, state, a, stream);
-    }
-    a.m = mask_finish(MaskArgs{d->B, n, R, n * R, rows, update_rows, static_rows, dyn_in, dyn_out, static_, ptr,
-                   mask_in, nullptr, nullptr, current_out, mask_out, nullptr, bits_out, nonbinary_out});
-    if (!mask_bits_ok(a.m))
-        return tap_fail(ctx, TAP_E_UNSUPPORTED, "bit shadow needs nR %% 4 == 0, nR <= 256, rows <= 128, 16-byte aligned buffers");
-    return transition_dispatch(ctx, d, a, stream);
+    TapStepRequest r = {};
+    r.form = TAP_STEP_BITS;
+    r.n = n; r.R = R; r.rows = rows; r.update_rows = update_rows; r.static_rows = static_rows; r.flags = flags;
+    r.bits_in = bits_in; r.static_ = static_; r.ptr = ptr; r.mask_in = mask_in;
+    r.bits_out = bits_out; r.dyn_out = dyn_out; r.current_out = current_out; r.mask_out = mask_out;
+    r.feature_out = feature_out; r.ratio_out = ratio_out;
+    return transition_impl(ctx, d, state, r, false, stream);
 }
 
 extern "C" int tap_transition_first(tap_ctx *ctx, const tap_env_desc *d, void *state, int n, int R, int rows,
@@ -380,24 +294,13 @@ extern "C" int tap_transition_first(tap_ctx *ctx, const tap_env_desc *d, void *s
                                     float *dyn_out, float *current_out, float *mask_out, float *feature_out,
                                     float *ratio_out, int32_t *nonbinary_out, int flags, void *stream)
 {
-    return transition_first_impl(ctx, d, state, n, R, rows, update_rows, dyn_in, static_, static_rows, ptr, mask_in, bits_out,
-                                 dyn_out, current_out, mask_out, feature_out, ratio_out, nonbinary_out, flags, stream, nullptr);
-}
-
-static int transition_dispatch(tap_ctx *ctx, const tap_env_desc *d, const TransArgs &a, void *stream)
-{
-    const int Gs = tap_group_size(d);
-    if (d->strategy == TAP_MACS) return tap_transition_macs_launch(ctx, d, a, (hipStream_t)stream);
-    if (d->D == 2) {
-        if (Gs == 8) return launch_transition<2, 8>(ctx, a, (hipStream_t)stream);
-        if (Gs == 16) return launch_transition<2, 16>(ctx, a, (hipStream_t)stream);
-        if (Gs == 32) return launch_transition<2, 32>(ctx, a, (hipStream_t)stream);
-        return launch_transition<2, 64>(ctx, a, (hipStream_t)stream);
-    }
-    if (Gs == 8) return launch_transition<3, 8>(ctx, a, (hipStream_t)stream);
-    if (Gs == 16) return launch_transition<3, 16>(ctx, a, (hipStream_t)stream);
-    if (Gs == 32) return launch_transition<3, 32>(ctx, a, (hipStream_t)stream);
-    return launch_transition<3, 64>(ctx, a, (hipStream_t)stream);
+    TapStepRequest r = {};
+    r.form = TAP_STEP_FIRST;
+    r.n = n; r.R = R; r.rows = rows; r.update_rows = update_rows; r.static_rows = static_rows; r.flags = flags;
+    r.dyn_in = dyn_in; r.static_ = static_; r.ptr = ptr; r.mask_in = mask_in;
+    r.bits_out = bits_out; r.dyn_out = dyn_out; r.current_out = current_out; r.mask_out = mask_out;
+    r.feature_out = feature_out; r.ratio_out = ratio_out; r.nonbinary_out = nonbinary_out;
+    return transition_impl(ctx, d, state, r, false, stream);
 }
 
 // ---- tap_stepper: the step object of a decoding loop (tapenv.h) --------------------------------------------------
@@ -440,7 +343,7 @@ extern "C" int tap_stepper_create(tap_ctx *ctx, const tap_env_desc *d, void *sta
         return tap_fail(ctx, TAP_E_INVALID, "bad stepper arguments");
     if (d->B > 0) {                                  // an empty batch has no buffers to check
         if (!state) return tap_fail(ctx, TAP_E_INVALID, "bad stepper arguments");
-        const bool shadow = n * R % 4 == 0 && n * R <= 256 && rows <= 128;
+        const bool shadow = tap_window_has_shadow(rows, n * R);
         for (int w = 0; w < 2; ++w)
             if ((shadow && !buf->bits[w]) || !buf->current[w] || !buf->mask[w])
                 return tap_fail(ctx, TAP_E_INVALID, "stepper needs both phases of bits / current / mask");
@@ -462,7 +365,6 @@ extern "C" int tap_stepper_create(tap_ctx *ctx, const tap_env_desc *d, void *sta
             buf->mask[0] == buf->mask[1] || !buf->ratio)
             return tap_fail(ctx, TAP_E_INVALID, "stepper phases must be distinct buffers (dyn may be one buffer on the bit shadow) and ratio is required");
     }
-    const int nR = n * R;
     if (buf->tour_stride < 0 || buf->tour_col0 < 0 || (buf->tour_stride > 0 && buf->tour_col0 + steps > buf->tour_stride))
         return tap_fail(ctx, TAP_E_INVALID, "stepper tour columns [col0, col0 + steps) must fit tour_stride");
     tap_stepper *s = new (std::nothrow) tap_stepper();
@@ -471,7 +373,7 @@ extern "C" int tap_stepper_create(tap_ctx *ctx, const tap_env_desc *d, void *sta
     s->n = n; s->R = R; s->rows = rows; s->update_rows = update_rows; s->static_rows = static_rows; s->steps = steps;
     s->b = *buf;
     s->static_ = nullptr; s->dyn_in = nullptr; s->bits0 = nullptr; s->mask0 = nullptr; s->k = 0; s->keep = 0;
-    s->copy_form = (nR % 4 != 0 || nR > 256 || rows > 128) ? 1 : 0;
+    s->copy_form = tap_window_has_shadow(rows, n * R) ? 0 : 1;
     s->inplace = (!s->copy_form && buf->dyn[0] && buf->dyn[0] == buf->dyn[1]) ? 1 : 0;
     *out = s;
     return TAP_OK;
@@ -540,23 +442,27 @@ extern "C" int tap_stepper_step(tap_stepper *s, const int64_t *ptr, void *stream
     if (s->d.B == 0) { s->k += 1; return TAP_OK; }
     const int k = s->k, w = k & 1, r = w ^ 1;
     const int flags = ((k == 0 && !s->keep) ? TAP_T_FRESH : 0) | (k == s->steps - 1 ? TAP_T_RATIO : 0);
-    const StepAux aux = {s->b.decoder_static, s->b.tour, s->b.tour_stride > 0 ? s->b.tour_stride : s->steps, s->b.tour_col0 + k};
+    TapStepRequest q = {};
+    q.n = s->n; q.R = s->R; q.rows = s->rows; q.update_rows = s->update_rows; q.static_rows = s->static_rows; q.flags = flags;
+    q.static_ = s->static_; q.ptr = ptr; q.mask_in = k == 0 ? s->mask0 : s->b.mask[r];
+    q.dyn_out = s->b.dyn[w]; q.current_out = s->b.current[w]; q.mask_out = s->b.mask[w];
+    q.feature_out = s->b.feature; q.ratio_out = s->b.ratio;
+    q.aux = {s->b.decoder_static, s->b.tour, s->b.tour_stride > 0 ? s->b.tour_stride : s->steps, s->b.tour_col0 + k};
+    if (s->copy_form) {
+        q.form = TAP_STEP_COPY;
+        q.dyn_in = k == 0 ? s->dyn_in : s->b.dyn[r];
+        q.colsum_in = s->b.colsum[k == 0 ? 1 : r]; q.colsum_out = s->b.colsum[w];
+    } else if (k == 0 && !s->bits0) {
+        q.form = TAP_STEP_FIRST;
+        q.dyn_in = s->dyn_in; q.mask_in = nullptr;
+        q.bits_out = s->b.bits[w]; q.nonbinary_out = s->b.nonbinary;
+    } else {
+        q.form = TAP_STEP_BITS;
+        q.bits_in = k == 0 ? s->bits0 : s->b.bits[r]; q.bits_out = s->b.bits[w];
+        q.inplace = (k > 0 && s->inplace) ? 1 : 0;
+    }
     DeviceGuard g(s->ctx->device);
-    int rc;
-    if (s->copy_form)
-        rc = transition_copy_impl(s->ctx, &s->d, s->state, s->n, s->R, s->rows, s->update_rows, k == 0 ? s->dyn_in : s->b.dyn[r],
-                                  s->static_, s->static_rows, ptr, k == 0 ? s->mask0 : s->b.mask[r], s->b.colsum[k == 0 ? 1 : r],
-                                  s->b.dyn[w], s->b.colsum[w], s->b.current[w], s->b.mask[w], s->b.feature, s->b.ratio, flags,
-                                  stream, &aux);
-    else if (k == 0 && !s->bits0)
-        rc = transition_first_impl(s->ctx, &s->d, s->state, s->n, s->R, s->rows, s->update_rows, s->dyn_in, s->static_,
-                                   s->static_rows, ptr, nullptr, s->b.bits[w], s->b.dyn[w], s->b.current[w], s->b.mask[w],
-                                   s->b.feature, s->b.ratio, s->b.nonbinary, flags, stream, &aux);
-    else
-        rc = transition_bits_impl(s->ctx, &s->d, s->state, s->n, s->R, s->rows, s->update_rows,
-                                  k == 0 ? s->bits0 : s->b.bits[r], s->static_, s->static_rows, ptr,
-                                  k == 0 ? s->mask0 : s->b.mask[r], s->b.bits[w], s->b.dyn[w], s->b.current[w], s->b.mask[w],
-                                  s->b.feature, s->b.ratio, flags, stream, &aux, (k > 0 && s->inplace) ? 1 : 0);
+    const int rc = transition_impl(s->ctx, &s->d, s->state, q, true, stream);
     if (rc == TAP_OK) s->k = k + 1;
     return rc;
 }

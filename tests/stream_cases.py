@@ -4,23 +4,23 @@ k_mask_step), and the concrete cases the GPU suite runs
 (tests/test_stream_variants_gpu.py) with the entries they reach (tests/test_stream_variant_reach_cpu.py).
 
 The facts each launch hands to tap_stream_variant (tap-net_amd/csrc/tap_stream_variant.h) come from these rules:
-- tap_write_through (tap_masks.h:188-194): write-through when the launch's fp32 tensor, B * rows * nR * 4 bytes, is at
-  most TAP_WT_MAX_BYTES = 64 MB (tap_masks.h:12); mask_finish (tap_masks.h:56) sets MaskArgs::wt for every launch.
-- mask_fast_path_cols (tap_masks.h:1111-1118): on the bit shadow nc = 1 / 2 / 4 for nR <= 64 / 128 / 256; on the fp32
+- tap_write_through (tap_masks.h): write-through when the launch's fp32 tensor, B * rows * nR * 4 bytes, is at
+  most TAP_WT_MAX_BYTES = 64 MB (tap_masks.h); mask_finish (tap_masks.h) sets MaskArgs::wt for every launch.
+- mask_fast_path_cols (tap_masks.h): on the bit shadow nc = 1 / 2 / 4 for nR <= 64 / 128 / 256; on the fp32
   copy the same when nR % 4 == 0 and nR <= 256 and dyn_out, ptr, static and the column sums are given, else 0.
 - tap_group_size (tap_common.h): G = 8 / 16 / 32 / 64 for containers of <= 8 / 16 / 32 / 64 cells; EPB (TransGeom,
-  tap_transition.h:68) = 4 envs per workgroup for G = 64, else 8.
-- transition_single_kernel (transition.hip:175): LB_GREEDY containers of at most 64 cells (3D: sides <= 8), MACS 2D of
-  at most 16 columns and MACS 3D of at most 64 cells (sides <= 8) run the step as ONE k_transition / k_transition_macs /
-  k_transition_macs3 launch; the bit-shadow entry points do so for rows <= 64 only (transition.hip:339, 383), and
-  above that run tap_mask_step_bits / _first (k_mask_step on the two-word shadow) and the placement.
-- transition_wave_kind (transition.hip:115): on the bit shadow with rows <= 64, LB_GREEDY above 64 cells runs
+  tap_transition.h) = 4 envs per workgroup for G = 64, else 8.
+- tap_step_route (tap_step_request.h), TAP_ROUTE_FUSED: LB_GREEDY containers of at most 64 cells (3D: sides <= 8), MACS 2D
+  of at most 16 columns and MACS 3D of at most 64 cells (sides <= 8) run the step as ONE k_transition / k_transition_macs /
+  k_transition_macs3 launch; the bit-shadow entry points do so for rows <= 64 only, and above that take
+  TAP_ROUTE_TWO_LAUNCHES: tap_mask_step_bits / _first (k_mask_step on the two-word shadow) and the placement.
+- tap_step_route, TAP_ROUTE_WAVE_*: on the bit shadow with rows <= 64, LB_GREEDY above 64 cells runs
   k_big_transition, MACS 2D above 16 columns k_macs2d_wave_transition, MACS 3D above 64 cells (or a side above 8)
   k_macs3d_wave_transition; their fp32-copy steps (tap_transition) are two launches (k_mask_step + placement).
-- transition_macs.hip:205: the MACS steps stay write-through up to 128 MB per launch.
-- the stepper (transition.hip: tap_stepper_create / _begin / _step): a window without a bit shadow (nR % 4 != 0,
-  nR > 256 or rows > 128) is carried as the fp32 copy with column sums (copy form: begin launches tap_update_mask,
-  k_mask_step on no tensor, then every step is tap_transition's fp32 copy); otherwise begin(initial_mask=True) launches
+- transition_macs.hip (tap_transition_macs_launch): the MACS steps stay write-through up to 128 MB per launch.
+- the stepper (transition.hip: tap_stepper_create / _begin / _step): a window without a bit shadow
+  (tap_step_request.h: tap_window_has_shadow -- nR % 4 != 0, nR > 256 or rows > 128) is carried as the fp32 copy with
+  column sums (copy form: begin launches tap_update_mask, k_mask_step on no tensor, then every step is tap_transition's fp32 copy); otherwise begin(initial_mask=True) launches
   tap_mask_step_first with no ptr / static / mask_in, step 0 then reads that shadow and mask (all inputs given),
   and begin(initial_mask=False) makes step 0 build the shadow from fp32 with no mask_in; the in-place form
   (dyn[0] == dyn[1]) sets MaskArgs::inplace from step 1 on.
@@ -103,9 +103,10 @@ def group_size(c):
 
 def fused_kind(c):
     """The launcher of a one-launch step on this container (None: the step is tap_mask_step* + the placement):
-    transition.hip: transition_single_kernel / transition_wave_kind, tap_common.h: tap_is_big / tap_is_big_macs3.
-    The LDS fits (transition_single_kernel's MACS check, big_transition_pw, macs*_transition_pw) hold for every shape
-    here (small heights and n <= 129); the GPU file's launch record checks the prediction."""
+    tap_step_request.h: tap_step_route, tap_is_big / tap_is_big_macs3.  The LDS fits (TapStepCaps: transition.hip's
+    transition_caps for the MACS lane kernels, big_transition_pw, macs*_transition_pw) hold for every shape here (small
+    heights and n <= 129); tests/test_step_request_cpu.py holds tap_step_route to this model on the host, and the GPU
+    file's launch record checks the prediction."""
     if c.strategy == "MACS":
         if c.D == 2:
             return MACS if c.W <= 16 else MACS_WAVE
@@ -148,7 +149,7 @@ def launches(c, steps=None):
             G = group_size(c)
             out.append((TRANSITION, c.D, G, dict(f, D=c.D, G=G, EPB=4 if G == 64 else 8, B=c.B, W=0, L=0, hard=0)))
         elif fk in (MACS, MACS3):
-            # transition_macs.hip:205: write-through up to 128 MB; G = 8 / 16 by width (2D), tap_group_size (3D)
+            # tap_transition_macs_launch: write-through up to 128 MB; G = 8 / 16 by width (2D), tap_group_size (3D)
             G = (8 if c.W <= 8 else 16) if fk == MACS else group_size(c)
             f = dict(f, wt=_wt(c, f["rows"], 2 * WT_MAX_BYTES))
             out.append((fk, c.D, G, dict(f, D=c.D, G=G, EPB=8, B=c.B, W=c.W, L=c.L, hard=0)))
@@ -164,8 +165,8 @@ def launches(c, steps=None):
     if c.path == "seam_mask_step":
         mstep(_facts(c, _copy_cols(c), 0))
         return out
-    single = fk in (TRANSITION, MACS, MACS3)                # transition_single_kernel
-    if c.path == "seam_transition":                         # transition_copy_impl
+    single = fk in (TRANSITION, MACS, MACS3)                # the lane-per-cell fused kernels
+    if c.path == "seam_transition":                         # tap_transition: the fp32-copy form
         (fused if single else mstep)(_facts(c, _copy_cols(c), 0))
         return out
     if c.path == "seam_transition_bits":

@@ -12,7 +12,7 @@ DG = {TRANSITION: [(D, G) for D in (2, 3) for G in (8, 16, 32, 64)], MACS: [(2, 
       MACS3: [(3, G) for G in (8, 16, 32, 64)]}
 
 # Built entries (kind, D, G, nc, mode, extra) the API never launches.  All are 2D windows on the bit shadow with nc = 4:
-# the one-launch steps carry rows <= 64 (transition.hip:339, 383), so 'bot' has n <= 21 (nR <= 42) and 'rot' n <= 64
+# the one-launch steps carry rows <= 64 (tap_step_request.h: tap_step_route), so 'bot' has n <= 21 (nR <= 42) and 'rot' n <= 64
 # (nR <= 128), which gives nc <= 2.  The fp32-copy entries {4, 0} ARE reachable: 'bot' n = 65 .. 128 is the stepper's
 # copy form (rows > 128) with nR = 130 .. 256, and tap_transition takes any window.
 _BITS = "2D step on the bit shadow: rows <= 64 bounds nR by 128"
